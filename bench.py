@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: augmented PCG samples/s of the drop-in ``augment()`` on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,13 @@ blocks wait for the index records the host writes: DESIGN.md §3.6 "armed").  Ev
 its own batch (no collective on the data path: weak scaling) and pins itself to CPUs of its GPU's
 NUMA node (``config.host_affinity``; PCGMIX_BENCH_NO_AFFINITY=1 leaves it to the scheduler).
 
-One JSON line is printed by rank 0.  Besides the contract keys it carries
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the K steps and prints
+the contract keys (ms_per_step = milliseconds of one timed step).  --dump-outputs DIR then writes
+what the last timed step returned (the output batch, the targets, the partner indices) as
+DIR/<name>.npy in float32/float64, at most 64 MB in all (a seeded sample of the batch's rows
+beyond that); the inputs are seeded, so two builds can be compared output for output.  With
+--full the line also carries
+  call_trace    host-side return time of each timed call (first / last / median, drain)
   roofline      the splice kernel against the HBM roofline (12*C*T algorithmic bytes/sample and the
                 bytes this batch needs), kernel time measured with HIP events on the launch stream
                 around back-to-back launches of the same splice body (the timed steps' own kernel
@@ -22,6 +28,7 @@ One JSON line is printed by rank 0.  Besides the contract keys it carries
   cpu_baseline  the CPU oracle (reference structure: per-sample Python loop) timed on this
                 host on a bounded number of batches of the same workload
   extra         secondary measurements (other shapes/methods, saturating batch, train step/s)
+  train         the captured training step (and, N > 1, train_cfg5)
 """
 import argparse
 import gc
@@ -75,6 +82,32 @@ def strict_json(obj):
             return clean(o.item())
         return o
     return json.dumps(clean(obj), allow_nan=False)
+
+
+DUMP_BUDGET = 64 << 20
+
+
+def dump_outputs(dirname, outputs, budget=DUMP_BUDGET):
+    """Write ``outputs`` ({name: tensor / array / list}) as DIR/<name>.npy: floating arrays in
+    float32 (float64 stays float64), integer ones as float64 (exact below 2**53).  If they
+    exceed ``budget`` bytes, every array whose first dimension is the batch keeps the same
+    seeded, sorted sample of batch rows, written beside them as rows.npy."""
+    arrs = {}
+    for name, v in outputs.items():
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        arrs[name] = a.astype(a.dtype if a.dtype == np.float64 else
+                              np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    B = max(a.shape[0] for a in arrs.values() if a.ndim)
+    per_row = sum(a.nbytes // B for a in arrs.values() if a.ndim and a.shape[0] == B)
+    fixed = sum(a.nbytes for a in arrs.values() if not (a.ndim and a.shape[0] == B))
+    if fixed + per_row * B > budget:
+        keep = max(1, (budget - fixed - 8 * B) // per_row)
+        rows = np.sort(np.random.RandomState(0).choice(B, min(B, keep), replace=False))
+        arrs = {k: a[rows] if a.ndim and a.shape[0] == B else a for k, a in arrs.items()}
+        arrs["rows"] = rows.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrs.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def make_device_batch(B, C, T, rate, seed, device):
@@ -744,9 +777,13 @@ def main():
     ap.add_argument("--channels", type=int, default=4)
     ap.add_argument("--sig-len", type=int, default=5000)
     ap.add_argument("--method", default="durratiomixup")
-    ap.add_argument("--no-extra", action="store_true", help="skip secondary measurements")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-train", action="store_true", help="skip the train-step leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also the call trace, roofline, train, secondary and CPU-baseline legs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip secondary measurements")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the train-step leg")
     ap.add_argument("--kernels-only", action="store_true",
                     help="only the back-to-back kernel table (diagnostic)")
     ap.add_argument("--profile-host", action="store_true",
@@ -814,14 +851,44 @@ def main():
         pr.disable()
         pstats.Stats(pr, stream=sys.stderr).sort_stats("cumtime").print_stats(25)
     # the timed region carries nothing but the drop-in calls (no event recording inside it)
-    headline_trace = {}
-    dt, _ = run_augment_steps(a.method, data, tgt, frames, wav, device, a.steps, a.warmup, barrier,
-                              trace=headline_trace)
+    headline_trace = {} if a.full else None
+    dt, out = run_augment_steps(a.method, data, tgt, frames, wav, device, a.steps, a.warmup, barrier,
+                                trace=headline_trace)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"data": out[0], "target": out[1], "mix": out[2]})
+    del out
     if dist is not None:
         t = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     value = world * B * a.steps / dt
+    result = {
+        "metric": "augmented PCG samples/s", "value": value, "unit": "samples/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"{a.method} augment() on synthetic 2.5 s @ 2 kHz PCG cycles, "
+                               f"({B},{C},{T}) float32 per GPU (BASELINE.json configs[1])",
+                   "batch_per_gpu": B, "channels": C, "sig_len": T, "method": a.method,
+                   "parallelism": f"dp{world}",
+                   "host_affinity": HOST_AFFINITY,
+                   "pre_settle": "before the W warm-up steps of every leg: heap collected + frozen, then 40 ms of "
+                                 "neutral GPU work (GEMM + streaming add) to reach loaded clocks, see "
+                                 "bench.settle_clocks"},
+    }
+    if a.full:
+        full_legs(a, result, world, rank, dist, barrier, device, data, tgt, frames, labels, wav, headline_trace)
+    if rank == 0:
+        print(strict_json(result))
+    if dist is not None:
+        dist.destroy_process_group()
+
+
+def full_legs(a, result, world, rank, dist, barrier, device, data, tgt, frames, labels, wav, headline_trace):
+    """What --full adds to the line: the headline's call trace, the roofline, the train legs, the
+    secondary measurements and the CPU baseline."""
+    B, C, T, rate = a.batch, a.channels, a.sig_len, 2000
+    value = result["value"]
 
     # Kernel time for the roofline: one HIP event pair on the launch stream around 200 launches
     # of the same kernel on this workload, issued back to back so the GPU never waits for the
@@ -847,22 +914,8 @@ def main():
                     "therefore contains the host's reaction (label arg-max 1.0 + host 4.4 + relay 1.0 us of ~12, "
                     "profiles/r4_armed_step.txt); `kernel` above is the two-launch instantiation of the same "
                     "body issued back to back, which is what a roofline can be read from"}
-    result = {
-        "metric": "augmented PCG samples/s", "value": value, "unit": "samples/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * dt / a.steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": f"{a.method} augment() on synthetic 2.5 s @ 2 kHz PCG cycles, "
-                               f"({B},{C},{T}) float32 per GPU (BASELINE.json configs[1])",
-                   "batch_per_gpu": B, "channels": C, "sig_len": T, "method": a.method,
-                   "parallelism": f"dp{world}",
-                   "host_affinity": HOST_AFFINITY,
-                   "pre_settle": "before the W warm-up steps of every leg: heap collected + frozen, then 40 ms of "
-                                 "neutral GPU work (GEMM + streaming add) to reach loaded clocks, see "
-                                 "bench.settle_clocks"},
-        "roofline": roof,
-        "call_trace": headline_trace,
-    }
+    result["roofline"] = roof
+    result["call_trace"] = headline_trace
 
     # train step/s (second half of BASELINE.json's metric): 1D-CNN, bs 256 per GPU; N>1: one
     # gradient all-reduce per step.  N>1 also runs BASELINE.json configs[4]'s per-rank workload
@@ -1036,10 +1089,6 @@ def main():
                 print(f"[bench] cpu_baseline failed: {e!r}", file=sys.stderr)
                 result["cpu_baseline"] = {"value": None, "unit": "samples/s", "cores": 0,
                                           "kind": "port", "sample": "failed: " + repr(e)[:200]}
-    if rank == 0:
-        print(strict_json(result))
-    if dist is not None:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

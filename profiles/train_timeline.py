@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One captured Potes train step out of a rocprofv3 kernel trace of `bench.py --no-cpu --no-extra`
+"""One captured Potes train step out of a rocprofv3 kernel trace of `bench.py --full --no-cpu --no-extra`
 (profiles/run_r2_bench_profile.sh): the launches from one optimiser kernel to the next in the
 graphed train leg, with start offsets and durations, written to profiles/r2_train_step_timeline.txt.
 

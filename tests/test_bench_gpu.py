@@ -1,9 +1,11 @@
 """bench.py prints ONE JSON line that honours the driver's contract (a short run)."""
+import glob
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -13,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_line_contract(device):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20",
-                          "--warmup", "3", "--no-extra", "--no-cpu"],
+                          "--warmup", "3", "--full", "--no-extra", "--no-cpu"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -33,3 +35,35 @@ def test_bench_line_contract(device):
     assert r["bound"] == "hbm" and r["unit"] == "GB/s" and r["peak"] == 8000.0
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-9
     assert abs(d["value"] - 256 * 20 / (d["ms_per_step"] * 20 / 1e3)) / d["value"] < 1e-6
+
+
+def test_bench_plain_run_dumps_last_step(device, tmp_path):
+    """A plain run times the K steps and nothing else; --dump-outputs writes what the last timed
+    step returned, the same on every run and equal to the CPU oracle at that step."""
+    from pcgmix_amd import synthetic
+    from oracle import pcgmix_oracle as O
+    steps, warmup, lines = 7, 2, []
+    for tag in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                              "--warmup", str(warmup), "--dump-outputs", str(tmp_path / tag)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines += [json.loads(l) for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 2
+    d = lines[0]
+    assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0
+    assert abs(d["value"] - 256 * steps / (d["ms_per_step"] * steps / 1e3)) / d["value"] < 1e-6
+    for k in ("roofline", "call_trace", "train", "extra", "cpu_baseline"):
+        assert k not in d, k
+    files = sorted(os.path.basename(f) for f in glob.glob(str(tmp_path / "a" / "*.npy")))
+    assert files == ["data.npy", "mix.npy", "target.npy"]
+    a = {f[:-4]: np.load(str(tmp_path / "a" / f)) for f in files}
+    b = {f[:-4]: np.load(str(tmp_path / "b" / f)) for f in files}
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    # bench.py's workload (rank 0's batch) and the step counter of the last timed call
+    x, frames, labels, wav = synthetic.make_batch(256, 4, 5000, sample_rate=2000, seed=0)
+    ref = O.augment(d["config"]["method"], x, labels, frames, wav, warmup + steps - 1)
+    assert np.array_equal(a["mix"], ref["mix"].astype(np.float64))
+    assert np.array_equal(a["data"], ref["y"]) and np.array_equal(a["target"], ref["target"])

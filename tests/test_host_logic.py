@@ -520,10 +520,16 @@ def test_logmel_tables_are_the_windowed_transform(sr, n_fft):
     assert used == max(0, min(lay["n_left"], hi_bin - (bin_lo + 32 * tpp) + 1))
 
 
-def test_bind_host_threads_is_a_noop_where_the_topology_is_unreadable():
-    """No GPU here: the helper must leave the mask alone and say why (bench.py prints the string)."""
+def test_bind_host_threads_is_a_noop_where_the_topology_is_unreadable(monkeypatch):
+    """Where the GPU's NUMA node cannot be read (no sysfs, no GPU) the helper must leave the mask
+    alone and say why (bench.py prints the string).  The read fails on purpose, so the test does
+    not depend on the machine it runs on (with a GPU the helper would pin this process)."""
     import os
     from pcgmix_amd import hostprep
+
+    def unreadable(torch, device_index):
+        raise FileNotFoundError("/sys/bus/pci/devices")
+    monkeypatch.setattr(hostprep, "_gpu_numa_node", unreadable)
     before = os.sched_getaffinity(0)
     msg = hostprep.bind_host_threads(0)
     assert os.sched_getaffinity(0) == before

@@ -272,9 +272,16 @@ def test_celoss_matches_reference_golden():
 
 def test_train_epoch_reproduces_reference_trajectory_cpu():
     """train_epoch here == the reference's train_epoch (train_model.py:490-589) run on the same
-    10 batches: per-step loss, lr, mean loss, accuracy, every parameter after step 10."""
+    10 batches: per-step loss, lr, mean loss, accuracy, every parameter after step 10.  torch splits
+    its CPU reductions by the intra-op thread count, so the run uses the 8 threads the golden was
+    recorded with, whatever the machine's default."""
     import train_replay
-    res = train_replay.trajectory(torch.device("cpu"), "epoch")
+    n = torch.get_num_threads()
+    torch.set_num_threads(8)
+    try:
+        res = train_replay.trajectory(torch.device("cpu"), "epoch")
+    finally:
+        torch.set_num_threads(n)
     train_replay.check_trajectory(res, loss_tol=2e-6, param_tol=2e-5)
 
 

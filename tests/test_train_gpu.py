@@ -423,7 +423,7 @@ def test_bench_self_launches_two_ranks(device):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["PCGMIX_DIST_BACKEND"] = "gloo"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-                          "--warmup", "3"], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                          "--warmup", "3", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                          env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
