@@ -31,7 +31,7 @@ extern "C" {
  * language binding does not need the HIP headers). */
 typedef struct ihipStream_t* pcgmix_stream_t;
 
-#define PCGMIX_ABI_VERSION 17
+#define PCGMIX_ABI_VERSION 18
 
 /* ABI version of the loaded library (== PCGMIX_ABI_VERSION it was built with). */
 int pcgmix_abi_version(void);
@@ -774,6 +774,55 @@ int pcgmix_bnrp_bwd_f32(const float* y, const float* dz, const float* gamma, con
                         const float* mean, const float* invstd, float* dx, float* dgamma,
                         float* dbeta, float* dzero, float* workspace, int B, int H, int W, int C,
                         int ph, int pw, pcgmix_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The paper's 1D comparison augmentations.                                        [device]
+ *
+ * One launch each for the O(B*C*T) part of the reference's baseline branches of augment();
+ * the RNG, the parsing and the host arrays stay in hostprep.py.  B == 0 returns 0 and
+ * launches nothing.
+ *
+ * pcgmix_blend_rows_f32 — mixup(same) / mixup(mix), augmentations.py:838-861:
+ *     y[b] = x[b]*lam + x[mix[b]]*(1-lam)   over the whole (C, T) plane; fp32 mul, mul, add,
+ *     (1-lam) formed in float32.  mix: device int32 (B), values in [0, B).
+ * pcgmix_warp_rows_f32 — magnitude_warp over whole rows, augmentations.py:674-683, 1026-1048:
+ *     y[b,c,t] = float(double(x[b,c,t]) * S_bc(t)), S_bc the not-a-knot spline through
+ *     (linspace(0, T-1, n_knots), knots[b,:,c]); knots device float64 (B, n_knots, C) as numpy
+ *     drew them, spline_op the device copy of pcgmix_spline_operator_f64(T, n_knots).  Same
+ *     coefficients and evaluation as the warp stage of pcgmix_mix_warp_f32.
+ * pcgmix_scale_rows_f32 — respiratoryscale, augmentations.py:777-804:
+ *     y[b,c,t] = float(double(x[b,c,t]) * s[t]),  s device float64 (T) (the numpy sinusoid).
+ * pcgmix_zero_spans_f32 — timemask, augmentations.py:807-827, IN PLACE:
+ *     x[b, :, spans[b][0] : spans[b][1]] = 0,  spans device int32 (B, 2), clipped to [0, T).
+ * pcgmix_time_warp_f32 — time_warp, augmentations.py:685-696, 1002-1024: per row (b, c)
+ *     tw    = CubicSpline(brk, brk * knots[b,:,c])(arange(T))       (products first, fp64)
+ *     xp    = clip(((T-1) / tw[T-1]) * tw, 0, T-1)
+ *     y     = float(np.interp(arange(T), xp, double(x[b,c,:])))
+ *   np.interp restated exactly, including xp that decreases somewhere (numpy's search with the
+ *   previous query's result as its guess).  workspace: device, pcgmix_time_warp_workspace_bytes
+ *   (B, C, T) bytes (0 = none needed: the row lives in LDS); n_knots 2..64, T >= 2.
+ * x and y are distinct (B, C, T) float32 tensors.                                             */
+int pcgmix_blend_rows_f32(const float* x, float* y, const int32_t* mix, float lam, int B, int C,
+                          int T, pcgmix_stream_t stream);
+int pcgmix_warp_rows_f32(const float* x, float* y, const double* knots, const double* spline_op,
+                         int n_knots, int B, int C, int T, pcgmix_stream_t stream);
+int pcgmix_scale_rows_f32(const float* x, float* y, const double* s, int B, int C, int T,
+                          pcgmix_stream_t stream);
+int pcgmix_zero_spans_f32(float* x, const int32_t* spans, int B, int C, int T,
+                          pcgmix_stream_t stream);
+long long pcgmix_time_warp_workspace_bytes(int B, int C, int T);
+int pcgmix_time_warp_f32(const float* x, float* y, const double* knots, const double* spline_op,
+                         int n_knots, void* workspace, int B, int C, int T, pcgmix_stream_t stream);
+
+/* Host twins of the time warp, built from the same __host__ __device__ code as the kernel.  [host]
+ * pcgmix_np_interp_f64: out = np.interp(x, xp, fp) for any xp (numpy's query-order search with
+ *   guess, its NaN-slope retry, left/right = fp[0]/fp[n-1]); n >= 1.
+ * pcgmix_time_warp_row_f64: one row of time_warp — spline_op of (T, n_knots), knots (n_knots)
+ *   of that row, x (T) float32 -> y (T) float32; xp_out (T, may be NULL) receives xp.          */
+int pcgmix_np_interp_f64(const double* x, long long nx, const double* xp, const double* fp,
+                         long long n, double* out);
+int pcgmix_time_warp_row_f64(const double* spline_op, const double* knots, int n_knots,
+                             const float* x, int T, float* y, double* xp_out);
 
 #ifdef __cplusplus
 }

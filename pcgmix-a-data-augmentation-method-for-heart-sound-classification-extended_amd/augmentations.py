@@ -9,7 +9,10 @@ per batch from train_model.py:507):
 Implemented methods (the PCGmix hot path): ``durratiomixup`` (augmentations.py:931-981) and
 ``durmixmagwarp(sigma,knot)`` (augmentations.py:864-929) with the selectors ``(rand)``,
 ``(alpha=a)``, ``(samePCG)``, ``(sameDataset)``, ``(mixAll)``, ``(saloptenv…)``,
-``(saloptsum…)`` and the ``+p`` probability gate.  The host part (RNG, partner indices) is in
+``(saloptsum…)`` and the ``+p`` probability gate.  The paper's 1D comparison baselines
+``mixup(same)``, ``mixup(mix)``, ``magnitudewarp``, ``timewarp``, ``timemask`` and
+``respiratoryscale`` (augmentations.py:777-862, 1002-1048) run through ``make_plan`` /
+``apply_plan`` with one kernel each (csrc/pcgmix_baselines.hip).  The host part (RNG, partner indices) is in
 ``hostprep``; the O(B*C*T) part is ONE launch of ``pcgmix_mix_warp_f32`` (HIP, gfx950) on the
 current torch stream, with no host synchronisation after the labels have been read.
 
@@ -208,6 +211,8 @@ def apply_plan(plan: MixPlan, data: torch.Tensor, frames: np.ndarray,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Run the device part of a fired plan; returns the new (B,C,T) tensor (``out`` if given:
     a static buffer a captured hipGraph reads from)."""
+    if plan.kind != "splice":
+        return _apply_baseline(plan, data, out)
     B, C, T = data.shape
     device = data.device
     if B == 0:                        # nothing to launch (and an empty tensor has no storage)
@@ -254,6 +259,81 @@ def apply_plan(plan: MixPlan, data: torch.Tensor, frames: np.ndarray,
         # caching allocator reuses them in stream order, so dropping the references is safe
         del keep
     return out
+
+
+def _apply_baseline(plan: MixPlan, data: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    """Device part of a comparison baseline (csrc/pcgmix_baselines.hip): one launch on the current
+    stream after the plan's small arrays went up through the pinned staging ring.  timemask zeroes
+    its spans IN PLACE in ``data`` (augmentations.py:826) — or, with ``out``, in a copy of ``data``
+    there; every other method writes a new tensor (``out`` if given)."""
+    B, C, T = data.shape
+    device = data.device
+    if out is not None and not _fresh_out_ok(out, data):
+        raise ValueError("out must be a distinct contiguous tensor shaped like data")
+    lib = _lib.load()
+    kind = plan.kind
+    if kind == "timemask":
+        dst = data if out is None else out.copy_(data)
+        if B:
+            with torch.cuda.device(device):
+                spans = upload_array(plan.spans, device)
+                _lib.check(lib.pcgmix_zero_spans_f32(dst.data_ptr(), spans.data_ptr(), B, C, T,
+                                                     ctypes.c_void_p(_raw_stream(device))),
+                           "pcgmix_zero_spans_f32")
+        return dst
+    if out is None:
+        out = torch.empty_like(data)
+    if B == 0:
+        return out
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(_raw_stream(device))
+        if kind == "mixup":
+            mix = upload_array(plan.mix.astype(np.int32), device)
+            _lib.check(lib.pcgmix_blend_rows_f32(data.data_ptr(), out.data_ptr(), mix.data_ptr(),
+                                                 _c_float(float(plan.lam32)), B, C, T, stream),
+                       "pcgmix_blend_rows_f32")
+        elif kind in ("magnitudewarp", "timewarp"):
+            knots = upload_array(plan.knots, device)
+            op = spline_operator(device, T, plan.n_knots)
+            if kind == "magnitudewarp":
+                _lib.check(lib.pcgmix_warp_rows_f32(data.data_ptr(), out.data_ptr(), knots.data_ptr(),
+                                                    op.data_ptr(), plan.n_knots, B, C, T, stream),
+                           "pcgmix_warp_rows_f32")
+            else:
+                nws = lib.pcgmix_time_warp_workspace_bytes(B, C, T)
+                ws = torch.empty(max(1, (nws + 7) // 8), dtype=torch.float64, device=device) if nws > 0 else None
+                _lib.check(lib.pcgmix_time_warp_f32(data.data_ptr(), out.data_ptr(), knots.data_ptr(),
+                                                    op.data_ptr(), plan.n_knots,
+                                                    ws.data_ptr() if ws is not None else None,
+                                                    B, C, T, stream), "pcgmix_time_warp_f32")
+        elif kind == "respiratoryscale":
+            if plan.scale_row.shape != (T,):
+                raise ValueError("respiratoryscale: the sinusoid row does not match the signal length")
+            row = upload_array(plan.scale_row, device)
+            _lib.check(lib.pcgmix_scale_rows_f32(data.data_ptr(), out.data_ptr(), row.data_ptr(), B, C, T,
+                                                 stream), "pcgmix_scale_rows_f32")
+        else:                                                   # pragma: no cover
+            raise NotImplementedError(kind)
+    return out
+
+
+def _augment_baseline(args, data: torch.Tensor, target_ohe, frames, wav, step: int, host_labels):
+    """One call of a comparison baseline (augmentations.py:777-862, 1002-1048): mixup returns its
+    partners (and, for '(mix)', blended targets), the others ``[]``; timemask returns ``data``
+    itself, zeroed in place."""
+    B, C, T = data.shape
+    frames_np = _as_numpy_frames(frames)
+    labels = (lambda: labels_from_ohe(target_ohe)) if host_labels is None else np.asarray(host_labels)
+    plan = hostprep.make_plan(args.method, labels, frames_np, wav, step, B, C,
+                              sample_rate=getattr(args, "sample_rate", None), sig_len=T)
+    if not plan.fired:
+        return data, target_ohe, [], None
+    out = apply_plan(plan, data, frames_np)
+    if plan.kind != "mixup":
+        return out, target_ohe, [], None
+    if plan.mix_all:
+        target_ohe = blend_targets(target_ohe, plan)
+    return out, target_ohe, plan.mix, None
 
 
 _SPLICE_ERRORS = {-1: _PACK_ERRORS[1], -2: _PACK_ERRORS[2], -3: _PACK_ERRORS[3]}
@@ -518,6 +598,8 @@ def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RE
         return data, target_ohe, [], None
     _check_data(data, 3)
     B, C, T = data.shape
+    if recipe is None and hostprep.select_method(method, False) in hostprep.BASELINE_METHODS_1D:
+        return _augment_baseline(args, data, target_ohe, frames, wav, step, host_labels)
     if recipe is not None and B > 0:              # the common case: one library call
         if not gate_passes(recipe, method, step, data.device.index):
             return data, target_ohe, [], None

@@ -25,8 +25,11 @@ import numpy as np
 
 from . import _lib
 
-# Methods this package implements, in the reference's dispatch order (augmentations.py:864, 931).
-PCGMIX_METHODS_1D = ("durmixmagwarp", "durratiomixup")
+# Methods this package implements: the PCGmix splices (augmentations.py:864, 931) and the paper's
+# 1D comparison baselines (augmentations.py:777, 807, 829, 1002, 1026).
+SPLICE_METHODS_1D = ("durmixmagwarp", "durratiomixup")
+BASELINE_METHODS_1D = ("respiratoryscale", "timemask", "mixup", "timewarp", "magnitudewarp")
+PCGMIX_METHODS_1D = SPLICE_METHODS_1D + BASELINE_METHODS_1D
 # 2D dispatch order: augmentations2d.py:286 (cutout), :325 (timemask), :361 (freqmask), :397
 PCGMIX_METHODS_2D = ("durmixcutout", "durmixtimemask", "durmixfreqmask", "durratiomixup")
 
@@ -43,9 +46,24 @@ _REFERENCE_METHODS_1D = (
 _REFERENCE_METHODS_2D = (
     "durratiocutmix", "cutmix", "mixup", "latentmixup", "freqmask", "timemask", "cutout",
     "durratiomixup", "durmixfreqmask", "durmixtimemask", "durmixcutout")
-# Branches the reference tests BEFORE ours (augmentations.py:731-862; augmentations2d.py:286-395)
-_EARLIER_1D = ("durmixrespscale", "respiratoryscale", "timemask")
-_EARLIER_2D = ()
+
+def _has(name):
+    return lambda m: name in m
+
+
+# The reference's 1D if-chain up to the last branch served here, in its order (augmentations.py:734,
+# 777, 807, 829, 864, 931, 983, 1002, 1026); everything behind it is refused.
+_CHAIN_1D = (
+    (_has("durmixrespscale"), "durmixrespscale"),
+    (_has("respiratoryscale"), "respiratoryscale"),
+    (_has("timemask"), "timemask"),
+    (lambda m: "mixup" in m and "latentmixup" not in m and "durratiomixup" not in m, "mixup"),
+    (_has("durmixmagwarp"), "durmixmagwarp"),
+    (_has("durratiomixup"), "durratiomixup"),
+    (_has("wav-durratiocutmix"), "wav-durratiocutmix"),
+    (_has("timewarp"), "timewarp"),
+    (_has("magnitudewarp"), "magnitudewarp"),
+)
 _UNSUPPORTED_SELECTORS = ("(sameCVD)", "(closestbins=", "(closestknn=")
 
 
@@ -64,6 +82,27 @@ class MixPlan:
     n_knots: int = 0
     mix_all: bool = False                      # '(mixAll)': targets are blended too
     zero_rect: Optional[np.ndarray] = None     # int32 (B,4) [row0,row1,col0,col1): 2D mask variants
+    spans: Optional[np.ndarray] = None         # int32 (B,2) [t0,t1): timemask, zeroed in place
+    scale_row: Optional[np.ndarray] = None     # float64 (T,): respiratoryscale's sinusoid
+
+    @property
+    def kind(self) -> str:
+        """"splice" (durratiomixup / durmixmagwarp) or the baseline's name."""
+        return self.name if self.name in BASELINE_METHODS_1D else "splice"
+
+
+def _branch_1d(method: str) -> Optional[str]:
+    """The reference's 1D if-chain (augmentations.py:734-1618): the name of the first branch that
+    returns, or "" when that branch is not implemented here.  Every branch draws the same gate
+    (``Random(step).uniform(0, 1) < p``), so a branch that falls through — ``mixup`` without
+    ``(same)`` or ``(mix)``, augmentations.py:829-862 — leaves the decision to the next one."""
+    for cond, name in _CHAIN_1D:
+        if not cond(method):
+            continue
+        if name == "mixup" and "(same)" not in method and "(mix)" not in method:
+            continue
+        return name if name in PCGMIX_METHODS_1D else ""
+    return ""                   # falls off the end: the reference returns None
 
 
 @functools.lru_cache(maxsize=256)
@@ -75,14 +114,16 @@ def select_method(method: str, is2d: bool) -> Optional[str]:
     known = _REFERENCE_METHODS_2D if is2d else _REFERENCE_METHODS_1D
     if not any(m in method for m in known):
         return None                                            # augmentations.py:731-732
-    earlier = _EARLIER_2D if is2d else _EARLIER_1D
-    hit = next((m for m in ours if m in method), None)
-    if hit is None or any(e in method for e in earlier):
+    if is2d:
+        hit = next((m for m in ours if m in method), None)
+    else:
+        hit = _branch_1d(method) or None
+    if hit is None:
         raise NotImplementedError(
             f"method {method!r} selects a reference augmentation outside the PCGmix hot path; "
             f"this package implements {ours} only")
     for sel in _UNSUPPORTED_SELECTORS:
-        if sel in method and not is2d:
+        if sel in method and not is2d and hit in SPLICE_METHODS_1D:
             raise NotImplementedError(f"partner selector {sel!r} is out of scope (SURVEY.md §2)")
     return hit
 
@@ -113,12 +154,74 @@ def parse_magwarp(method: str):
 
 
 @functools.lru_cache(maxsize=256)
+def parse_warp(method: str, name: str):
+    """'magnitudewarp(sigma,knot)' (augmentations.py:1039-1042; defaults 0.2, 4) and
+    'timewarp(sigma,knot)' (:1015-1018; defaults 0.05, 2).  As in the reference, the knot count is
+    read behind the method string's FIRST comma."""
+    sigma, knot = (0.05, 2) if name == "timewarp" else (0.2, 4)
+    parts = method.split(name + "(")
+    if len(parts) > 1:
+        sigma = float(parts[1].split(",")[0])
+        knot = int(method.split(",")[1].split(")")[0])
+    return sigma, knot
+
+
+@functools.lru_cache(maxsize=256)
+def parse_timemask(method: str) -> float:
+    """'timemask(max)' (augmentations.py:816-819): default 0.2, clamped to [0, 1]."""
+    parts = method.split("timemask(")
+    if len(parts) > 1:
+        return min(max(float(parts[1].split(")")[0]), 0), 1)
+    return 0.2
+
+
+@functools.lru_cache(maxsize=256)
+def parse_respscale(method: str):
+    """'respiratoryscale(min,max)' in breaths per minute -> (min, max) in Hz (augmentations.py:
+    791-795): min through float(), max through int() and from behind the string's FIRST comma —
+    so 'respiratoryscale(12,20.5)' raises ValueError as the reference does."""
+    lo, hi = 12 / 60, 20 / 60
+    parts = method.split("respiratoryscale(")
+    if len(parts) > 1:
+        lo = float(parts[1].split(",")[0]) / 60
+        hi = int(method.split(",")[1].split(")")[0]) / 60
+    return lo, hi
+
+
+def mask_spans(method: str, frames: np.ndarray, step: int, sig_len: int) -> np.ndarray:
+    """timemask's zeroed span per sample (augmentations.py:816-826): ``gap =
+    Random(step+131071).uniform(0, max)``, ``f1 = Random(step+13119).uniform(0, 1-gap)``, span
+    ``[int(f1*beat), int((f1+gap)*beat))`` with ``beat = frames[b, -1]``; int32 (B, 2), clipped
+    to the row as the reference's slice is."""
+    gap = random.Random(step + 131071).uniform(0, parse_timemask(method))
+    frac1 = random.Random(step + 13119).uniform(0, 1 - gap)
+    frac2 = frac1 + gap
+    beat = np.asarray(frames)[:, -1].astype(np.float64)
+    spans = np.empty((beat.shape[0], 2), dtype=np.int64)
+    spans[:, 0] = (frac1 * beat).astype(np.int64)              # int() truncation
+    spans[:, 1] = (frac2 * beat).astype(np.int64)
+    return np.clip(spans, 0, sig_len).astype(np.int32)
+
+
+def respiration_row(method: str, step: int, sig_len: int, sample_rate) -> np.ndarray:
+    """respiratoryscale's sinusoid (augmentations.py:796-799), with numpy as the reference builds
+    it: the gate's own ``u = Random(step).random()`` gives rate = min + (max-min)*u and phase =
+    2*pi*u (``Random(step).uniform`` twice on fresh generators)."""
+    lo, hi = parse_respscale(method)
+    u = _lib.load().pcgmix_py_uniform01(int(step))
+    rate = lo + (hi - lo) * u
+    phase = 0 + (2 * np.pi - 0) * u
+    t = np.linspace(0, sig_len / sample_rate, sig_len)
+    return np.sin(2 * np.pi * rate * t + phase)
+
+
+@functools.lru_cache(maxsize=256)
 def plain_recipe(method: str, is2d: bool):
     """(name, p, alpha, sigma, knots) when ``method`` is a plain splice — same-label partners, no
     '(rand)' offsets, no saliency, no 2D mask — i.e. what ``pcgmix_splice_same_label_f32`` does in
     one call; None otherwise (the general ``make_plan`` path handles those)."""
     name = select_method(method, is2d)
-    if name is None:
+    if name is None or (not is2d and name not in SPLICE_METHODS_1D):
         return None
     if is2d:
         if name != "durratiomixup" or "(salopt" in method:
@@ -136,7 +239,7 @@ def salopt_recipe(method: str):
     partners — what ``pcgmix_ctx_salopt_begin/_finish`` do around the saliency pass; None otherwise
     ('(samePCG)', '(sameDataset)', '(mixAll)': the general ``make_plan`` path)."""
     name = select_method(method, False)
-    if name is None or "(salopt" not in method:
+    if name is None or name not in SPLICE_METHODS_1D or "(salopt" not in method:
         return None
     if any(t in method for t in ("(samePCG)", "(sameDataset)", "(mixAll)")):
         return None
@@ -148,6 +251,17 @@ def salopt_recipe(method: str):
         raise NotImplementedError("only (saloptenv…) and (saloptsum…) exist in the reference")
     sigma, knot = parse_magwarp(method) if name == "durmixmagwarp" else (0.0, -2)
     return mode, parse_alpha(method, name), sigma, knot + 2
+
+
+def soft_targets(method: str) -> bool:
+    """True when a fired step blends the one-hot targets into floats: '(mixAll)' (augmentations.py:
+    915-917, 978-980) and 'mixup(mix)' (:857).  A training step then needs the float targets."""
+    if "(mixAll)" in method:
+        return True
+    try:
+        return select_method(method, False) == "mixup" and "(same)" not in method
+    except NotImplementedError:
+        return False
 
 
 def gate_fires(method: str, step: int) -> bool:
@@ -339,18 +453,23 @@ def validate_frames(frames: np.ndarray, sig_len: int) -> None:
 
 
 def make_plan(method: str, labels, frames: np.ndarray, wav: Sequence[str], step: int,
-              batch: int, channels: int, is2d: bool = False, n_cols: int = 0) -> MixPlan:
+              batch: int, channels: int, is2d: bool = False, n_cols: int = 0,
+              sample_rate=None, sig_len: Optional[int] = None) -> MixPlan:
     """Everything random/integer for one step, in the reference's RNG order.
 
     ``labels`` may be an array or a zero-argument callable returning one: they are needed only
     when the gate fires (on a GPU they cost a device->host sync, augmentations.py:501), so a
-    callable lets rejected steps skip the sync."""
+    callable lets rejected steps skip the sync.  ``sample_rate`` (``args.sample_rate``) and
+    ``sig_len`` (T) are needed by respiratoryscale; timemask clips its spans to ``sig_len``."""
     name = select_method(method, is2d)
     if name is None or not gate_fires(method, step):
         return MixPlan(fired=False, step=step)
     if frames.shape[0] != batch:
         raise ValueError("labels/frames do not match the batch size")
     plan = MixPlan(fired=True, name=name, step=step)
+    if plan.kind != "splice":
+        return _baseline_plan(plan, method, labels, frames, step, batch, channels, sample_rate,
+                              sig_len)
     # numpy's global stream first (lambda, then the warp knots right behind it): neither depends
     # on the labels, and python's random.Random (partners, offsets, masks) is a separate stream,
     # so the order BETWEEN the two streams is free — a callable `labels` that has to wait for the
@@ -384,6 +503,43 @@ def make_plan(method: str, labels, frames: np.ndarray, wav: Sequence[str], step:
             raise NotImplementedError("only (saloptenv…) and (saloptsum…) exist in the reference")
     if not is2d:
         plan.mix_all = "(mixAll)" in method
+    return plan
+
+
+def _baseline_plan(plan: MixPlan, method: str, labels, frames: np.ndarray, step: int, batch: int,
+                   channels: int, sample_rate, sig_len: Optional[int]) -> MixPlan:
+    """make_plan's part for the comparison baselines; the gate has fired."""
+    name = plan.name
+    if name == "mixup":
+        # get_lambda(alpha=1): np.random.seed(step); beta(1, 1) (augmentations.py:841, 851)
+        plan.lam64, _ = draw_lambda_knots(step, 1.0, 0.0, 0)
+        plan.lam32 = np.float32(plan.lam64)
+        if callable(labels):
+            labels = labels()
+        labels = np.asarray(labels).reshape(-1)
+        if labels.shape[0] != batch:
+            raise ValueError("labels/frames do not match the batch size")
+        if "(same)" in method:                                    # augmentations.py:840
+            plan.mix = shuffle_within_groups(labels.astype(np.int64, copy=False), step)
+        else:                                                     # '(mix)', augmentations.py:850
+            plan.mix = shuffle_within_groups(np.zeros(batch, dtype=np.int64), step)
+            plan.mix_all = True
+    elif name in ("magnitudewarp", "timewarp"):
+        sigma, knot = parse_warp(method, name)
+        if not 2 <= knot + 2 <= 64:
+            raise ValueError(f"{name}: {knot + 2} spline knots, the kernels take 2..64")
+        # np.random.normal(1, sigma, (B, knot+2, C)) from numpy's global stream AS IT IS: no
+        # reseeding (augmentations.py:677, 688)
+        _, knots = draw_lambda_knots(step, 0.0, sigma, batch * (knot + 2) * channels)
+        plan.n_knots = knot + 2
+        plan.knots = knots_array(knots, (batch, knot + 2, channels)) if knots is not None \
+            else np.zeros((0, knot + 2, channels))
+    elif name == "timemask":
+        plan.spans = mask_spans(method, frames, step, 2**31 - 1 if sig_len is None else sig_len)
+    elif name == "respiratoryscale":
+        if sample_rate is None or sig_len is None:
+            raise ValueError("respiratoryscale needs make_plan(..., sample_rate=, sig_len=)")
+        plan.scale_row = respiration_row(method, step, int(sig_len), sample_rate)
     return plan
 
 

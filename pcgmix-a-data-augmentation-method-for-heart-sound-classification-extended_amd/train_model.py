@@ -547,7 +547,8 @@ class GraphedTrainStep:
         self._pay_t = self._payload[12 + n_lab:12 + n_lab + n_t].reshape(batch_size, args.num_classes)
         self._rows = np.arange(batch_size)
         self.labels_mode = bool(                               # same test as _fwd_bwd's
-            isinstance(self.ce, CELoss) and "(mixAll)" not in args.method and args.num_classes <= 255
+            isinstance(self.ce, CELoss) and not augmentations.hostprep.soft_targets(args.method)
+            and args.num_classes <= 255
             and fused_loss_model(model, self.ce, self.x, self.t, None) is not None)
         self._pay_bytes = (12 + n_lab) * 4 if self.labels_mode else self._payload.nbytes
         self.sync = sync
@@ -781,7 +782,8 @@ class GraphedTrainStep:
                                                out=self.x)
         else:
             if hostprep.select_method(args.method, False):
-                plan = hostprep.make_plan(args.method, labels_np, frames_np, wav, step, B, C)
+                plan = hostprep.make_plan(args.method, labels_np, frames_np, wav, step, B, C,
+                                          sample_rate=getattr(args, "sample_rate", None), sig_len=T)
             fired = plan.fired
             if fired:
                 sal = None
