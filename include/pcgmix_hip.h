@@ -31,7 +31,7 @@ extern "C" {
  * language binding does not need the HIP headers). */
 typedef struct ihipStream_t* pcgmix_stream_t;
 
-#define PCGMIX_ABI_VERSION 18
+#define PCGMIX_ABI_VERSION 19
 
 /* ABI version of the loaded library (== PCGMIX_ABI_VERSION it was built with). */
 int pcgmix_abi_version(void);
@@ -823,6 +823,37 @@ int pcgmix_np_interp_f64(const double* x, long long nx, const double* xp, const 
                          long long n, double* out);
 int pcgmix_time_warp_row_f64(const double* spline_op, const double* knots, int n_knots,
                              const float* x, int T, float* y, double* xp_out);
+
+/* ------------------------------------------------------------------------------------------
+ * The paper's spectrogram comparison baselines.  csrc/pcgmix_baselines2d.hip.
+ *
+ * One launch each for the O(B*C*F*W) part of the reference's 2D baseline branches
+ * (augmentations2d.py:461-617); the RNG, the parsing and the per-sample tables stay in
+ * hostprep.py.  Batches are float32 (B, C, F, W), contiguous.  B == 0 returns 0 and launches
+ * nothing.  (mixup and latentmixup's blend are pcgmix_blend_rows_f32 on the flat sample planes.)
+ *
+ * pcgmix_zero_rects_f32 — timemask (augmentations2d.py:461-485) and freqmask (:487-508), IN PLACE:
+ *     x[b, c, rect[b][0] : rect[b][1], rect[b][2] : rect[b][3]] = 0   for every channel c;
+ *   rect device int32 (B, 4), clipped to the plane; max_area an upper bound of the rectangles'
+ *   clipped areas (it sizes the grid; F*W is always safe).  Only the zeroed elements are written.
+ * pcgmix_piecewise_rows_f32 — cutmix (:574-597, cutmix_multidim_tensors :34-51) and
+ *   durratiocutmix (:599-617, cutmix_keepdur_multidim_tensors :223-249):
+ *     y (B, C, F, Wo) from x (B, C, F, W).  segs device int32 (B, PCGMIX_PIECE_SEGS, 4), per
+ *     segment {lo, hi, src, shift}: contiguous, ordered, lo of the first = 0, along the columns
+ *     (axis 0) or along F (axis 1, Wo == W).  A position p in [lo, hi) reads
+ *       PCGMIX_PIECE_OWN      x[b]       at p + shift
+ *       PCGMIX_PIECE_PARTNER  x[mix[b]]  at p + shift
+ *       PCGMIX_PIECE_ZERO     0
+ *     along that axis (the other coordinates unchanged); positions beyond the last hi, and source
+ *     positions outside the input, give 0.  mix device int32 (B), values in [0, B).  x != y.   */
+#define PCGMIX_PIECE_SEGS 5
+#define PCGMIX_PIECE_OWN 0
+#define PCGMIX_PIECE_PARTNER 1
+#define PCGMIX_PIECE_ZERO 2
+int pcgmix_zero_rects_f32(float* x, const int32_t* rect, int B, int C, int F, int W, int max_area,
+                          pcgmix_stream_t stream);
+int pcgmix_piecewise_rows_f32(const float* x, float* y, const int32_t* segs, const int32_t* mix,
+                              int axis, int B, int C, int F, int W, int Wo, pcgmix_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpcgmix_hip.so")
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _c_int = ctypes.c_int
 _c_float = ctypes.c_float
@@ -141,6 +141,9 @@ SIGNATURES = {
     "pcgmix_time_warp_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _ptr, _c_int, _c_int, _c_int, _ptr]),
     "pcgmix_np_interp_f64": (_c_int, [_ptr, ctypes.c_longlong, _ptr, _ptr, ctypes.c_longlong, _ptr]),
     "pcgmix_time_warp_row_f64": (_c_int, [_ptr, _ptr, _c_int, _ptr, _c_int, _ptr, _ptr]),
+    "pcgmix_zero_rects_f32": (_c_int, [_ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr]),
+    "pcgmix_piecewise_rows_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int,
+                                           _c_int, _ptr]),
     "pcgmix_bnrp_workspace_floats": (ctypes.c_longlong, [_c_int, _c_int, _c_int, _c_int]),
     "pcgmix_bnrp_fwd_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_float, _c_float, _ptr, _ptr, _ptr, _ptr,
                                      _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr]),

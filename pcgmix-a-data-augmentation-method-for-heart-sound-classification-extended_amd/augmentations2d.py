@@ -13,20 +13,189 @@ applied to every frequency row, so the same kernel runs with C = F rows and T = 
 shorter state inside the longer one by saliency (augmentations2d.py:125-204, 416-423): maps from the
 frozen ResNet9-2D 'base' checkpoint through ``saliency.get_saliency_maps(dim=2)``, then the 1D
 displacement search and offset splice.
+
+The paper's spectrogram comparison baselines (augmentations2d.py:461-617) run through the same
+call, with the reference's return values (csrc/pcgmix_baselines2d.hip):
+
+    timemask(t)[+p]            columns [int(u1*f[-1]), int(u2*f[-1])) of every row and channel
+                               zeroed IN PLACE; returns ``data`` itself, ``[]``, None
+    freqmask(f)[+p]            rows [h1, h2) of every channel zeroed IN PLACE; same return
+    mixup(same) / mixup(mix)   data*lam + data[mix]*(1-lam) in fp32 on a new tensor; '(mix)'
+                               blends the targets too; returns (new, targets, mix, None)
+    cutmix, (rand)cutmix       own columns up to f1[cut], the partner's behind them, zeros after
+                               ``min(.., F)``; the new tensor is (B, C, F, F) as the reference's
+                               ``torch.zeros((size, C, F, F))``; returns (new, targets, mix, cut)
+    durratiocutmix             systole and diastole columns from the partner (needs W == F)
+    (rand)durratiocutmix       the reference's row-slicing quirk: whole frequency rows swapped
+    latentmixup[+p]            ``model(data, depth, 'first')`` blended with the same-label partners'
+                               features through a differentiable HIP blend; sets ``args.depth``
+
+Bare ``cutout`` (the one 2D baseline not served) and a bare ``mixup`` that nothing behind it
+catches raise NotImplementedError from ``hostprep.select_method``.
 """
 from __future__ import annotations
 
-from . import hostprep
-from .augmentations import (_as_numpy_frames, _check_data, apply_plan, gate_passes,
-                            labels_from_ohe, splice_plain)
+import ctypes
+
+import numpy as np
+import torch
+
+from . import _lib, hostprep
+from .augmentations import (_as_numpy_frames, _check_data, _raw_stream, apply_plan, blend_targets,
+                            gate_passes, labels_from_ohe, splice_plain, upload_array)
+
+
+def _stream(device) -> ctypes.c_void_p:
+    return ctypes.c_void_p(_raw_stream(device))
+
+
+def zero_rects_(data: torch.Tensor, rect: np.ndarray) -> torch.Tensor:
+    """``data[b, :, r0:r1, c0:c1] = 0`` in place for the (B, 4) int32 host rectangles."""
+    B, C, F, W = data.shape
+    if B == 0:
+        return data
+    area = int(((rect[:, 1] - rect[:, 0]).clip(0) * (rect[:, 3] - rect[:, 2]).clip(0)).max())
+    if area == 0:
+        return data
+    with torch.cuda.device(data.device):
+        dev = upload_array(np.ascontiguousarray(rect, dtype=np.int32), data.device)
+        _lib.check(_lib.load().pcgmix_zero_rects_f32(data.data_ptr(), dev.data_ptr(), B, C, F, W, area,
+                                                     _stream(data.device)), "pcgmix_zero_rects_f32")
+    return data
+
+
+def piecewise_rows(data: torch.Tensor, segs: np.ndarray, mix: np.ndarray, axis: int,
+                   out_cols: int) -> torch.Tensor:
+    """New (B, C, F, out_cols) tensor from the (B, 5, 4) segment table (cutmix, durratiocutmix)."""
+    B, C, F, W = data.shape
+    out = torch.empty((B, C, F, out_cols), dtype=data.dtype, device=data.device)
+    if B == 0:
+        return out
+    with torch.cuda.device(data.device):
+        # one upload: the table, then the partners
+        host = np.concatenate([np.ascontiguousarray(segs, dtype=np.int32).reshape(-1),
+                               np.asarray(mix, dtype=np.int32)])
+        dev = upload_array(host, data.device)
+        _lib.check(_lib.load().pcgmix_piecewise_rows_f32(
+            data.data_ptr(), out.data_ptr(), dev.data_ptr(), dev.data_ptr() + segs.size * 4, axis,
+            B, C, F, W, out_cols, _stream(data.device)), "pcgmix_piecewise_rows_f32")
+    return out
+
+
+def _blend_planes(src: torch.Tensor, dst: torch.Tensor, mix_dev: torch.Tensor, lam: float) -> None:
+    """dst[b] = src[b]*lam + src[mix[b]]*(1-lam) over each sample's storage (batch outermost)."""
+    B = src.shape[0]
+    plane = src.numel() // B
+    _lib.check(_lib.load().pcgmix_blend_rows_f32(src.data_ptr(), dst.data_ptr(), mix_dev.data_ptr(),
+                                                 ctypes.c_float(lam), B, 1, plane, _stream(src.device)),
+               "pcgmix_blend_rows_f32")
+
+
+def _batch_dense(t: torch.Tensor) -> bool:
+    """Dense storage with the batch as the outermost stride: contiguous, or channels-last 4D."""
+    if t.is_contiguous():
+        return True
+    return t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
+
+
+class LatentBlend(torch.autograd.Function):
+    """``h*lam + h[mix]*(1-lam)`` (augmentations2d.py:535) on the HIP blend, differentiable.
+
+    Forward: ``pcgmix_blend_rows_f32`` over each sample's flat storage, so a channels-last feature
+    map keeps its layout (output strides = input strides).  Backward: the same kernel with the
+    inverse permutation, ``grad_h[b] = lam*g[b] + (1-lam)*g[inv[b]]`` — the partners are a
+    permutation, so this is value for value what torch's autograd of the reference expression
+    gives (it scatters into +0.0, so only the sign of a zero may differ)."""
+
+    @staticmethod
+    def forward(ctx, h, mix_dev, inv_dev, lam):
+        if not _batch_dense(h):
+            h = h.contiguous()
+        out = torch.empty_like(h)
+        if h.shape[0] and h.numel():
+            with torch.cuda.device(h.device):
+                _blend_planes(h, out, mix_dev, lam)
+        ctx.save_for_backward(inv_dev)
+        ctx.lam = lam
+        ctx.strides = out.stride()
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (inv_dev,) = ctx.saved_tensors
+        if g.stride() != ctx.strides:
+            # an incoming gradient with other strides is brought to the forward output's layout
+            g = torch.empty_strided(g.shape, ctx.strides, dtype=g.dtype, device=g.device).copy_(g)
+        if not _batch_dense(g):
+            g = g.contiguous()
+        gh = torch.empty_like(g)
+        if g.shape[0] and g.numel():
+            with torch.cuda.device(g.device):
+                _blend_planes(g, gh, inv_dev, ctx.lam)
+        return gh, None, None, None
+
+
+def latent_blend(h: torch.Tensor, mix: np.ndarray, lam32) -> torch.Tensor:
+    """latentmixup's blend of the features ``h`` (float32 on a HIP device, batch outermost)."""
+    if not isinstance(h, torch.Tensor) or not h.is_cuda or h.dtype != torch.float32 or h.dim() < 1:
+        raise ValueError("latentmixup: the model's first half must return float32 features on a HIP device")
+    mix = np.asarray(mix, dtype=np.int64)
+    inv = np.empty_like(mix)
+    inv[mix] = np.arange(mix.shape[0])
+    with torch.cuda.device(h.device):
+        both = upload_array(np.concatenate([mix, inv]).astype(np.int32), h.device)
+    B = mix.shape[0]
+    return LatentBlend.apply(h, both[:B], both[B:], float(lam32))
+
+
+def _augment_baseline2d(args, data, target_ohe, frames, step: int, model, host_labels):
+    """One call of a spectrogram baseline (augmentations2d.py:461-617)."""
+    _check_data(data, 4)
+    B, C, F, W = data.shape
+    name = hostprep.select_method(args.method, is2d=True)
+    if name == "latentmixup" and getattr(args, "model", None) != "resnet9":
+        # the reference sets max_model_depth for 'resnet9' only (augmentations2d.py:520-521)
+        raise NotImplementedError(f"latentmixup: the reference defines the mixing depth for "
+                                  f"args.model == 'resnet9' only, got {getattr(args, 'model', None)!r}")
+    frames_np = _as_numpy_frames(frames)
+    labels = (lambda: labels_from_ohe(target_ohe)) if host_labels is None else np.asarray(host_labels)
+    plan = hostprep.make_plan(args.method, labels, frames_np, None, step, B, C, is2d=True, n_cols=W,
+                              n_freq=F)
+    if not plan.fired:
+        return data, target_ohe, [], None
+    kind = plan.kind
+    if kind in ("timemask2d", "freqmask2d"):
+        return zero_rects_(data, plan.zero_rect), target_ohe, [], None
+    if kind == "mixup2d":
+        out = torch.empty_like(data)
+        if B:
+            with torch.cuda.device(data.device):
+                mix = upload_array(plan.mix.astype(np.int32), data.device)
+                _blend_planes(data, out, mix, float(plan.lam32))
+        if plan.mix_all:
+            target_ohe = blend_targets(target_ohe, plan)
+        return out, target_ohe, plan.mix, None
+    if kind in ("cutmix2d", "durratiocutmix2d"):
+        out = piecewise_rows(data, plan.segs, plan.mix, plan.seg_axis, plan.out_cols)
+        return out, target_ohe, plan.mix, plan.cut
+    if kind == "latentmixup2d":
+        if model is None:
+            raise ValueError("latentmixup needs the model (augment(..., model, ...))")
+        args.depth = plan.depth
+        h = model(data, depth=plan.depth, pass_part="first")
+        return latent_blend(h, plan.mix, plan.lam32), target_ohe, plan.mix, None
+    raise NotImplementedError(kind)                                        # pragma: no cover
 
 
 def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RESULTS_ARGS,
             host_labels=None):
     method = args.method
     step = int(step_counter.count)
-    if hostprep.select_method(method, is2d=True) is None:
+    name = hostprep.select_method(method, is2d=True)
+    if name is None:
         return data, target_ohe, [], None
+    if name in hostprep.BASELINE_METHODS_2D:
+        return _augment_baseline2d(args, data, target_ohe, frames, step, model, host_labels)
     _check_data(data, 4)
     B, Cc, F, W = data.shape
     recipe = hostprep.plain_recipe(method, True)

@@ -11,6 +11,12 @@ host and called in the reference's order:
     Random(step).randint          '(rand)' placement offsets       augmentations.py:305-337
     np.random.normal              magnitude-warp knots             augmentations.py:677
 
+The spectrogram baselines (augmentations2d.py:461-617) draw from the same streams: the gate,
+same-label partners (or ``Random(step).sample`` for ``mixup(mix)``), ``get_lambda`` for mixup and
+latentmixup only, ``Random(step+131071)`` / ``Random(step+13119)`` for the mask sizes and
+positions, ``Random(step*131071).randint(1, 3)`` for ``(rand)cutmix``'s cut and
+``Random(step).randint(1, 3)`` for latentmixup's depth.
+
 The result is a small ``MixPlan`` of index/scalar data that the device kernels consume; no
 waveform data is touched here.
 """
@@ -32,6 +38,8 @@ BASELINE_METHODS_1D = ("respiratoryscale", "timemask", "mixup", "timewarp", "mag
 PCGMIX_METHODS_1D = SPLICE_METHODS_1D + BASELINE_METHODS_1D
 # 2D dispatch order: augmentations2d.py:286 (cutout), :325 (timemask), :361 (freqmask), :397
 PCGMIX_METHODS_2D = ("durmixcutout", "durmixtimemask", "durmixfreqmask", "durratiomixup")
+# the paper's spectrogram comparison baselines (augmentations2d.py:461, 487, 510, 538, 574, 599)
+BASELINE_METHODS_2D = ("timemask", "freqmask", "latentmixup", "mixup", "cutmix", "durratiocutmix")
 
 # Every name the reference dispatcher knows (augmentations.py:700-729, augmentations2d.py:269-281).
 # A method string that names one of these but none of ours is refused loudly instead of being
@@ -64,6 +72,21 @@ _CHAIN_1D = (
     (_has("timewarp"), "timewarp"),
     (_has("magnitudewarp"), "magnitudewarp"),
 )
+# The reference's 2D if-chain, in its order (augmentations2d.py:286, 325, 361, 397, 429, 461, 487, 510,
+# 538, 574, 599).  'cutout' is the one branch not served here.
+_CHAIN_2D = (
+    (_has("durmixcutout"), "durmixcutout"),
+    (_has("durmixtimemask"), "durmixtimemask"),
+    (_has("durmixfreqmask"), "durmixfreqmask"),
+    (_has("durratiomixup"), "durratiomixup"),
+    (lambda m: "cutout" in m and "durmixcutout" not in m, "cutout"),
+    (lambda m: "timemask" in m and "durmixtimemask" not in m, "timemask"),
+    (lambda m: "freqmask" in m and "durmixfreqmask" not in m, "freqmask"),
+    (_has("latentmixup"), "latentmixup"),
+    (lambda m: "mixup" in m and "durratiomixup" not in m and "latentmixup" not in m, "mixup"),
+    (lambda m: "cutmix" in m and "durratiocutmix" not in m, "cutmix"),
+    (_has("durratiocutmix"), "durratiocutmix"),
+)
 _UNSUPPORTED_SELECTORS = ("(sameCVD)", "(closestbins=", "(closestknn=")
 
 
@@ -84,11 +107,34 @@ class MixPlan:
     zero_rect: Optional[np.ndarray] = None     # int32 (B,4) [row0,row1,col0,col1): 2D mask variants
     spans: Optional[np.ndarray] = None         # int32 (B,2) [t0,t1): timemask, zeroed in place
     scale_row: Optional[np.ndarray] = None     # float64 (T,): respiratoryscale's sinusoid
+    is2d: bool = False                         # a spectrogram plan (augmentations2d.augment)
+    cut: Optional[int] = None                  # cutmix: the state boundary it cuts at (1..3)
+    depth: int = 0                             # latentmixup: the model depth it mixes at (1..3)
+    segs: Optional[np.ndarray] = None          # int32 (B,5,4) {lo,hi,src,shift}: cutmix / durratiocutmix
+    seg_axis: int = 0                          # 0: segments along the columns, 1: along F ('(rand)')
+    out_cols: int = 0                          # width of the new tensor (cutmix: F, augmentations2d.py:589)
 
     @property
     def kind(self) -> str:
-        """"splice" (durratiomixup / durmixmagwarp) or the baseline's name."""
+        """"splice" (durratiomixup / durmixmagwarp and the 2D mask variants), the 1D baseline's
+        name, or the 2D baseline's name with a "2d" suffix ("timemask2d", "cutmix2d", ...): a 2D
+        timemask is a rectangle per channel, never the 1D span path."""
+        if self.is2d:
+            return self.name + "2d" if self.name in BASELINE_METHODS_2D else "splice"
         return self.name if self.name in BASELINE_METHODS_1D else "splice"
+
+
+def _branch_2d(method: str) -> str:
+    """The reference's 2D if-chain (augmentations2d.py:286-617), as ``_branch_1d``: a bare ``mixup``
+    (no '(same)', no '(mix)', :547-572) falls through to the later branches; "" when the branch
+    reached is not implemented here ('cutout') or none is (the reference returns None)."""
+    for cond, name in _CHAIN_2D:
+        if not cond(method):
+            continue
+        if name == "mixup" and "(same)" not in method and "(mix)" not in method:
+            continue
+        return name if name in PCGMIX_METHODS_2D + BASELINE_METHODS_2D else ""
+    return ""
 
 
 def _branch_1d(method: str) -> Optional[str]:
@@ -110,14 +156,11 @@ def select_method(method: str, is2d: bool) -> Optional[str]:
     """Which of our branches the reference's if-chain would reach, or None for passthrough.
 
     Raises NotImplementedError for reference augmentations outside this package's scope."""
-    ours = PCGMIX_METHODS_2D if is2d else PCGMIX_METHODS_1D
+    ours = PCGMIX_METHODS_2D + BASELINE_METHODS_2D if is2d else PCGMIX_METHODS_1D
     known = _REFERENCE_METHODS_2D if is2d else _REFERENCE_METHODS_1D
     if not any(m in method for m in known):
         return None                                            # augmentations.py:731-732
-    if is2d:
-        hit = next((m for m in ours if m in method), None)
-    else:
-        hit = _branch_1d(method) or None
+    hit = (_branch_2d(method) if is2d else _branch_1d(method)) or None
     if hit is None:
         raise NotImplementedError(
             f"method {method!r} selects a reference augmentation outside the PCGmix hot path; "
@@ -312,30 +355,39 @@ def partner_indices(method: str, labels: np.ndarray, wav: Sequence[str], step: i
     return mix
 
 
-def rand_offsets(frames: np.ndarray, mix: np.ndarray, step: int) -> np.ndarray:
+def rand_offsets(frames: np.ndarray, mix: np.ndarray, step: int, states=(0, 1, 2, 3)) -> np.ndarray:
     """'(rand)': offset of the shorter state inside the longer one,
     ``Random(step).randint(0, |gap|)`` with a fresh generator per (sample, state), so the value
-    depends on (step, |gap|) only (augmentations.py:305-337)."""
+    depends on (step, |gap|) only (augmentations.py:305-337): one library draw per distinct gap.
+    int32 (B, 4); only the columns of ``states`` are drawn, the others are 0 ('(rand)durratiocutmix'
+    needs systole and diastole only, augmentations2d.py:236, 243)."""
     lens = np.diff(frames, axis=1)
-    gap = np.abs(lens[mix] - lens)
+    cols = list(states)
+    gap = np.abs(lens[mix] - lens)[:, cols]
     lib = _lib.load()
     uniq, inv = np.unique(gap, return_inverse=True)
     vals = np.array([lib.pcgmix_py_randint0(int(step), int(g)) for g in uniq], dtype=np.int32)
-    return vals[inv].reshape(gap.shape)
+    out = np.zeros(lens.shape, dtype=np.int32)
+    out[:, cols] = vals[inv].reshape(gap.shape)
+    return out
 
 
 def mask_rectangles(method: str, name: str, frames: np.ndarray, step: int, n_rows: int,
                     n_cols: int) -> np.ndarray:
     """Zeroed rectangle per sample for durmixcutout / durmixtimemask / durmixfreqmask
-    (augmentations2d.py:309-323, 348-358, 384-394): region sizes from
-    ``Random(step+131071).uniform``, positions from ``Random(step+13119).uniform``; the time span
-    is a fraction of each sample's own cycle length (``int(frac * f[-1])``), the frequency span is
-    one row range for the whole batch.  Rows count along the flattened (channel, frequency) axis
-    of the kernel call; the reference's images have one channel."""
+    (augmentations2d.py:309-323, 348-358, 384-394) and the plain timemask / freqmask (:476-484,
+    :500-507): region sizes from ``Random(step+131071).uniform``, positions from
+    ``Random(step+13119).uniform``; the time span is a fraction of each sample's own cycle length
+    (``int(frac * f[-1])``), the frequency span is one row range for the whole batch,
+    ``h1 = int(n_rows * u)``, ``h2 = min(n_rows, h1 + int(gap * n_rows))``.  ``n_rows`` is the row
+    axis the caller's kernel applies the rectangle to: the durmix variants pass the flattened
+    (channel, frequency) axis of the splice (the reference's images have one channel), the plain
+    names F (``spec_dim1 = data.shape[2]``), applied within every channel as ``d[:, h1:h2]`` does.
+    Columns are not clipped here."""
     def clamp01(v):
         return min(max(v, 0), 1)
     t_max = f_max = 0.2
-    key = name[len("durmix"):] + "("
+    key = (name[len("durmix"):] if name.startswith("durmix") else name) + "("
     parts = method.split(key)
     if len(parts) > 1:
         if name == "durmixcutout":
@@ -347,14 +399,14 @@ def mask_rectangles(method: str, name: str, frames: np.ndarray, step: int, n_row
     rect = np.zeros((B, 4), dtype=np.int32)
     rect[:, 1] = n_rows
     rect[:, 3] = n_cols
-    if name in ("durmixcutout", "durmixtimemask"):
+    if name in ("durmixcutout", "durmixtimemask", "timemask"):
         gap = random.Random(step + 131071).uniform(0, t_max)
         frac1 = random.Random(step + 13119).uniform(0, 1 - gap)
         frac2 = frac1 + gap
         beat = frames[:, 4].astype(np.float64)
         rect[:, 2] = (frac1 * beat).astype(np.int64)          # int() truncation
         rect[:, 3] = (frac2 * beat).astype(np.int64)
-    if name in ("durmixcutout", "durmixfreqmask"):
+    if name in ("durmixcutout", "durmixfreqmask", "freqmask"):
         fgap = random.Random(step + 131071).uniform(0, f_max)
         h1 = int(n_rows * random.Random(step + 13119).uniform(0, 1 - fgap))
         rect[:, 0] = h1
@@ -454,19 +506,25 @@ def validate_frames(frames: np.ndarray, sig_len: int) -> None:
 
 def make_plan(method: str, labels, frames: np.ndarray, wav: Sequence[str], step: int,
               batch: int, channels: int, is2d: bool = False, n_cols: int = 0,
-              sample_rate=None, sig_len: Optional[int] = None) -> MixPlan:
+              sample_rate=None, sig_len: Optional[int] = None,
+              n_freq: Optional[int] = None) -> MixPlan:
     """Everything random/integer for one step, in the reference's RNG order.
 
     ``labels`` may be an array or a zero-argument callable returning one: they are needed only
     when the gate fires (on a GPU they cost a device->host sync, augmentations.py:501), so a
     callable lets rejected steps skip the sync.  ``sample_rate`` (``args.sample_rate``) and
-    ``sig_len`` (T) are needed by respiratoryscale; timemask clips its spans to ``sig_len``."""
+    ``sig_len`` (T) are needed by respiratoryscale; timemask clips its spans to ``sig_len``.
+    The 2D baselines need the image's F (``n_freq``) and W (``n_cols``); ``channels`` is then C."""
     name = select_method(method, is2d)
     if name is None or not gate_fires(method, step):
         return MixPlan(fired=False, step=step)
     if frames.shape[0] != batch:
         raise ValueError("labels/frames do not match the batch size")
-    plan = MixPlan(fired=True, name=name, step=step)
+    plan = MixPlan(fired=True, name=name, step=step, is2d=is2d)
+    if is2d and plan.kind != "splice":
+        if n_freq is None or n_cols <= 0:
+            raise ValueError("2D baselines need make_plan(..., n_freq=F, n_cols=W)")
+        return _baseline_plan_2d(plan, method, labels, frames, step, batch, int(n_freq), int(n_cols))
     if plan.kind != "splice":
         return _baseline_plan(plan, method, labels, frames, step, batch, channels, sample_rate,
                               sig_len)
@@ -541,6 +599,129 @@ def _baseline_plan(plan: MixPlan, method: str, labels, frames: np.ndarray, step:
             raise ValueError("respiratoryscale needs make_plan(..., sample_rate=, sig_len=)")
         plan.scale_row = respiration_row(method, step, int(sig_len), sample_rate)
     return plan
+
+
+def _host_labels(labels, batch: int) -> np.ndarray:
+    if callable(labels):
+        labels = labels()
+    labels = np.asarray(labels).reshape(-1)
+    if labels.shape[0] != batch:
+        raise ValueError("labels/frames do not match the batch size")
+    return labels
+
+
+def _baseline_plan_2d(plan: MixPlan, method: str, labels, frames: np.ndarray, step: int, batch: int,
+                      F: int, W: int) -> MixPlan:
+    """make_plan's part for the spectrogram baselines (augmentations2d.py:461-617); the gate has
+    fired.  numpy's global stream is drawn by mixup and latentmixup only (get_lambda)."""
+    name = plan.name
+    if name in ("timemask", "freqmask"):                          # :476-484, :500-507
+        rect = mask_rectangles(method, name, frames, step, F, W)
+        rect[:, 2:] = np.clip(rect[:, 2:], 0, W)                  # the reference's slice clips
+        plan.zero_rect = rect
+        return plan
+    lib = _lib.load()
+    if name == "mixup" and "(same)" not in method:                # '(mix)': Random(step).sample, :560
+        plan.mix = shuffle_within_groups(np.zeros(batch, dtype=np.int64), step)
+        plan.mix_all = True
+    else:                                                         # get_same_label_mix_indices
+        plan.mix = shuffle_within_groups(_host_labels(labels, batch).astype(np.int64, copy=False), step)
+    if name in ("mixup", "latentmixup"):
+        if name == "latentmixup":                                 # Random(step).randint(1, 3), :522
+            plan.depth = 1 + int(lib.pcgmix_py_randint0(int(step), 2))
+        plan.lam64, _ = draw_lambda_knots(step, 1.0, 0.0, 0)      # get_lambda(alpha=1), :527, :551
+        plan.lam32 = np.float32(plan.lam64)
+        return plan
+    # cutmix / durratiocutmix read state boundaries: refused beyond the image, as the splice does
+    validate_frames(np.asarray(frames), W)
+    f1 = np.asarray(frames, dtype=np.int64)
+    if name == "cutmix":
+        plan.cut = 1 + int(lib.pcgmix_py_randint0(int(step) * 131071, 2)) if "(rand)" in method else 2
+        plan.segs = cutmix_segments(f1, plan.mix, plan.cut, F)
+        plan.out_cols = F
+        return plan
+    if W != F:
+        # data_new is (B, C, F, F) (augmentations2d.py:609) and receives a (C, F, W) d1.clone():
+        # torch refuses the assignment unless W == F
+        raise ValueError(f"durratiocutmix: the reference writes (C, F, W) = (.., {F}, {W}) samples into "
+                         f"(C, F, F) slots, which torch refuses unless W == F")
+    plan.out_cols = W
+    if "(rand)" in method:
+        plan.segs = rand_keepdur_segments(f1, plan.mix, rand_offsets(f1, plan.mix, step, (1, 3)), F)
+        plan.seg_axis = 1
+    else:
+        plan.segs = keepdur_segments(f1, plan.mix, W)
+    return plan
+
+
+_OWN, _PARTNER, _ZERO = 0, 1, 2        # PCGMIX_PIECE_* (include/pcgmix_hip.h)
+
+
+def _segment_table(bounds, kinds, shifts) -> np.ndarray:
+    """int32 (B, 5, 4) {lo, hi, src, shift} from the 6 boundaries (B each) of 5 contiguous segments."""
+    B = bounds[0].shape[0]
+    segs = np.zeros((B, 5, 4), dtype=np.int32)
+    for k in range(5):
+        segs[:, k, 0] = bounds[k]
+        segs[:, k, 1] = bounds[k + 1]
+        segs[:, k, 2] = kinds[k]
+        segs[:, k, 3] = shifts[k]
+    return segs
+
+
+def cutmix_segments(frames: np.ndarray, mix: np.ndarray, cut: int, F: int) -> np.ndarray:
+    """cutmix_multidim_tensors (augmentations2d.py:34-51) as a column table of the (F, F) output:
+    ``[0, f1[cut])`` own, ``[f1[cut], last)`` the partner from ``f2[cut]`` on, zero behind ``last =
+    min(f1[cut] + f2[4] - f2[cut], F)`` — the cap is spec_dim2 = data.shape[2] = F, not W.  With
+    ``f1[cut] > F`` (possible when F < W) the reference's own-part assignment has mismatched shapes:
+    ValueError, as torch raises there."""
+    f2 = frames[mix]
+    a = frames[:, cut]
+    if (a > F).any():
+        raise ValueError(f"cutmix: a cut at column {int(a.max())} > F = {F}: the reference copies "
+                         f"{int(a.max())} columns into an F-column slot and torch raises")
+    last = np.minimum(a + f2[:, 4] - f2[:, cut], F)
+    full = np.full_like(a, F)
+    zero = np.zeros_like(a)
+    return _segment_table((zero, a, last, full, full, full), (_OWN, _PARTNER, _ZERO, _ZERO, _ZERO),
+                          (zero, f2[:, cut] - a, zero, zero, zero))
+
+
+def keepdur_segments(frames: np.ndarray, mix: np.ndarray, W: int) -> np.ndarray:
+    """cutmix_keepdur_multidim_tensors without '(rand)' (augmentations2d.py:225-231): systole and
+    diastole columns, over the shorter of the two lengths, from the partner; a column table."""
+    f2 = frames[mix]
+    n_sys = np.minimum(frames[:, 2] - frames[:, 1], f2[:, 2] - f2[:, 1])
+    n_dia = np.minimum(frames[:, 4] - frames[:, 3], f2[:, 4] - f2[:, 3])
+    s0, d0 = frames[:, 1], frames[:, 3]
+    zero = np.zeros_like(s0)
+    return _segment_table((zero, s0, s0 + n_sys, d0, d0 + n_dia, np.full_like(s0, W)),
+                          (_OWN, _PARTNER, _OWN, _PARTNER, _OWN),
+                          (zero, f2[:, 1] - s0, zero, f2[:, 3] - d0, zero))
+
+
+def rand_keepdur_segments(frames: np.ndarray, mix: np.ndarray, off: np.ndarray, F: int) -> np.ndarray:
+    """'(rand)durratiocutmix' (augmentations2d.py:232-248) as a table along F: the reference slices
+    ``d_new[:, a:b]`` on a (C, F, W) sample, so it swaps whole FREQUENCY rows ``[a, b)`` (every column)
+    with the partner's rows at a shift.  ``off`` = ``rand_offsets``: ``Random(step).randint(0, |gap|)``
+    with ``gap = len2 - len1``; gap >= 0 shifts the partner's rows, gap < 0 the sample's own.  With
+    W == F and boundaries within W, both sides of every slice lie inside the image, so torch never
+    clips one side differently from the other."""
+    f2 = frames[mix]
+    out = []
+    for k in (1, 3):                                   # systole, diastole
+        l1 = frames[:, k + 1] - frames[:, k]
+        l2 = f2[:, k + 1] - f2[:, k]
+        ge = l2 - l1 >= 0
+        s = off[:, k].astype(np.int64)
+        t0 = np.where(ge, frames[:, k], frames[:, k] + s)
+        src0 = np.where(ge, f2[:, k] + s, f2[:, k])
+        out.append((t0, t0 + np.minimum(l1, l2), src0 - t0))
+    (a0, a1, sa), (b0, b1, sb) = out
+    zero = np.zeros_like(a0)
+    return _segment_table((zero, a0, a1, b0, b1, np.full_like(a0, F)),
+                          (_OWN, _PARTNER, _OWN, _PARTNER, _OWN),
+                          (zero, sa, zero, sb, zero))
 
 
 def _gpu_numa_node(torch, index):

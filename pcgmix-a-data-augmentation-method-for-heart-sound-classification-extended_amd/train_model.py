@@ -1148,6 +1148,13 @@ def train_model(args, dataset, device, use_graph: bool = True, log=print, pipeli
     spectro = args.dataset == "PhysioNet(spec128)"
     if args.dataset != "PhysioNet" and not spectro:
         raise NotImplementedError("train_model drives the PhysioNet time-series and spectrogram paths")
+    if spectro and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        from . import hostprep
+        if hostprep.select_method(args.method, is2d=True) == "latentmixup":
+            # two half passes of the DDP-wrapped model in one iteration (augmentations2d.py:523 and
+            # the training step's 'second' pass): refused rather than reduced twice or not at all
+            raise NotImplementedError("latentmixup under torch.distributed is not supported: it runs the "
+                                      "model in two halves per step, which the DDP step does not handle")
     seed_fix = 4                                                   # :217
     args.seed_fix = seed_fix
     torch.manual_seed(seed_fix)
