@@ -31,7 +31,7 @@ extern "C" {
  * language binding does not need the HIP headers). */
 typedef struct ihipStream_t* pcgmix_stream_t;
 
-#define PCGMIX_ABI_VERSION 19
+#define PCGMIX_ABI_VERSION 20
 
 /* ABI version of the loaded library (== PCGMIX_ABI_VERSION it was built with). */
 int pcgmix_abi_version(void);
@@ -75,6 +75,12 @@ int pcgmix_spline_operator_f64(int T, int n_knots, double* op /* host */);
  */
 int pcgmix_partner_permutation_i64(const int32_t* group_id, int B, int n_groups, uint64_t seed,
                                    int64_t* mix);
+
+/* A partner permutation and its inverse as one int32 block, what a kernel that follows the
+ * partners in both directions reads (pcgmix_potes_head_loss_latent_fwd_f32):
+ *   out[0..B) = mix, out[B..2B) = inv with inv[mix[b]] = b.                              [host]
+ * Returns -3 when an index lies outside [0, B), -4 when mix is not a permutation.              */
+int pcgmix_pack_partners_i32(const int64_t* mix, int B, int32_t* out);
 
 /* random.Random(seed).uniform(0, 1) — the probability-gate draw (augmentations.py:869-870). */
 double pcgmix_py_uniform01(uint64_t seed);
@@ -550,6 +556,28 @@ int pcgmix_potes_head_loss_bwd_f32(const float* dz, const float* gscale, const f
  * step when forward and backward always run together (a training step captured in a hipGraph).
  * With defer_finalize != 0 the forward writes neither `loss` nor `small`; the backward then takes
  * deferred_ws = ws, writes the loss to deferred_loss and ignores small_in.                      */
+
+/* The fused forward with manifold mixup at the hidden layer — 1D `latentmixup` with a Potes model
+ * (augmentations.py:1472-1506: `data = model(data, depth=1, 'first')`, `data*lam +
+ * data[mix_indices]*(1-lam)`, then train_model.py:537 `model(data, depth=1, 'second')` = Linear(20->C),
+ * models.py:456-465).  With h[b] = relu(z[b]) * mask2[b] * scale2 (every row under its own dropout
+ * bytes, as the first half applies Dropout(.5) before the blend):
+ *   hm[b] = lam h[b] + (1-lam) h[mix[b]];   logits[b] = W2 hm[b] + b2;   loss, dl as above;
+ *   dW2 = sum_b dl[b] (x) hm[b];  db2 = sum_b dl[b];
+ *   dz[b] = fac[b] * W2^T (lam dl[b] + (1-lam) dl[inv[b]]);  db1 = sum_b dz[b].
+ * mix (B) = the partner permutation, inv (B) = its inverse (inv[mix[b]] = b), both int32 on the
+ * device with values in [0, B); 0 <= lam <= 1.  z and dz are stored per row, z un-blended: the
+ * backward is pcgmix_potes_head_loss_bwd_f32, unchanged (deferred_ws = NULL: this entry point always
+ * finalizes).  Two launches behind the split-K product, as the plain forward; lam = 1 reproduces
+ * the plain forward's outputs bit for bit.  Other arguments as pcgmix_potes_head_loss_fwd_f32.  */
+int pcgmix_potes_head_loss_latent_fwd_f32(const float* x, const uint8_t* mask1, float scale1,
+                                          int thr1, int bits1, const float* w1, const float* b1,
+                                          const uint8_t* mask2, float scale2, int thr2,
+                                          const float* w2, const float* b2, const float* target,
+                                          float* partial, float* z, float* logits, float* dz,
+                                          float* loss, float* small, float* ws, float* dw1_zero,
+                                          int target_kind, int B, int K, int C, const int32_t* mix,
+                                          const int32_t* inv, float lam, pcgmix_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Soft-target cross entropy (train_model.py:45-54, CELoss).                          [device]

@@ -12,7 +12,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpcgmix_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _c_int = ctypes.c_int
 _c_float = ctypes.c_float
@@ -25,6 +25,7 @@ SIGNATURES = {
     "pcgmix_spline_operator_size": (_c_int, [_c_int]),
     "pcgmix_spline_operator_f64": (_c_int, [_c_int, _c_int, _ptr]),
     "pcgmix_partner_permutation_i64": (_c_int, [_ptr, _c_int, _c_int, ctypes.c_uint64, _ptr]),
+    "pcgmix_pack_partners_i32": (_c_int, [_ptr, _c_int, _ptr]),
     "pcgmix_py_uniform01": (ctypes.c_double, [ctypes.c_uint64]),
     "pcgmix_py_randint0": (ctypes.c_int64, [ctypes.c_uint64, ctypes.c_int64]),
     "pcgmix_np_seed": (_c_int, [_ptr, ctypes.c_uint32]),
@@ -96,6 +97,10 @@ SIGNATURES = {
     "pcgmix_potes_head_loss_fwd_f32": (_c_int, [_ptr, _ptr, _c_float, _c_int, _c_int, _ptr, _ptr, _ptr,
                                                 _c_float, _c_int, _ptr, _ptr, _ptr] + [_ptr] * 8 +
                                        [_c_int, _c_int, _c_int, _c_int, _c_int, _ptr]),
+    "pcgmix_potes_head_loss_latent_fwd_f32": (_c_int, [_ptr, _ptr, _c_float, _c_int, _c_int, _ptr, _ptr,
+                                                       _ptr, _c_float, _c_int, _ptr, _ptr, _ptr] +
+                                              [_ptr] * 8 + [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr,
+                                                            _c_float, _ptr]),
     "pcgmix_potes_head_loss_bwd_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_float, _c_int, _c_int, _ptr, _ptr,
                                                 _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _ptr]),
     "pcgmix_soft_ce_fwd_f32": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _ptr]),

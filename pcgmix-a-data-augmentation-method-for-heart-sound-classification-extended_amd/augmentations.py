@@ -12,7 +12,12 @@ Implemented methods (the PCGmix hot path): ``durratiomixup`` (augmentations.py:9
 ``(saloptsum…)`` and the ``+p`` probability gate.  The paper's 1D comparison baselines
 ``mixup(same)``, ``mixup(mix)``, ``magnitudewarp``, ``timewarp``, ``timemask`` and
 ``respiratoryscale`` (augmentations.py:777-862, 1002-1048) run through ``make_plan`` /
-``apply_plan`` with one kernel each (csrc/pcgmix_baselines.hip).  The host part (RNG, partner indices) is in
+``apply_plan`` with one kernel each (csrc/pcgmix_baselines.hip).  ``latentmixup[+p]`` (manifold
+mixup, augmentations.py:1472-1506; ``args.model`` 'Potes' or 'resnet9') runs ``model(data, depth,
+'first')`` and blends the features with the same-label partners' through the differentiable HIP
+blend (``LatentBlend``); it sets ``args.depth`` and returns the features.  ``gaussiannoise`` is not
+served: it draws from unseeded global streams through ``audiomentations``, so the reference defines
+no values to match.  The host part (RNG, partner indices) is in
 ``hostprep``; the O(B*C*T) part is ONE launch of ``pcgmix_mix_warp_f32`` (HIP, gfx950) on the
 current torch stream, with no host synchronisation after the labels have been read.
 
@@ -32,6 +37,7 @@ from .hostprep import MixPlan
 
 _OP_CACHE: dict = {}      # (device index, T, n_knots) -> device tensor with the spline operator
 _RECIPES: dict = {}       # method string -> plain recipe | None (general plan path) | False (passthrough)
+                          # | _LATENT (1D latentmixup: the model's first half, blended)
 
 
 def _raw_stream(device: torch.device) -> int:
@@ -577,6 +583,107 @@ def labels_from_ohe(target_ohe: torch.Tensor, after: Optional["torch.cuda.Event"
     return host.numpy().argmax(axis=1)
 
 
+def _blend_planes(src: torch.Tensor, dst: torch.Tensor, mix_dev: torch.Tensor, lam: float) -> None:
+    """dst[b] = src[b]*lam + src[mix[b]]*(1-lam) over each sample's storage (batch outermost)."""
+    B = src.shape[0]
+    plane = src.numel() // B
+    _lib.check(_lib.load().pcgmix_blend_rows_f32(src.data_ptr(), dst.data_ptr(), mix_dev.data_ptr(),
+                                                 ctypes.c_float(lam), B, 1, plane,
+                                                 ctypes.c_void_p(_raw_stream(src.device))),
+               "pcgmix_blend_rows_f32")
+
+
+def _batch_dense(t: torch.Tensor) -> bool:
+    """Dense storage with the batch as the outermost stride: contiguous, or channels-last 4D."""
+    if t.is_contiguous():
+        return True
+    return t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
+
+
+class LatentBlend(torch.autograd.Function):
+    """``h*lam + h[mix]*(1-lam)`` (augmentations.py:1505, augmentations2d.py:535) on the HIP blend,
+    differentiable.
+
+    Forward: ``pcgmix_blend_rows_f32`` over each sample's flat storage, so a channels-last feature
+    map keeps its layout (output strides = input strides).  Backward: the same kernel with the
+    inverse permutation, ``grad_h[b] = lam*g[b] + (1-lam)*g[inv[b]]`` — the partners are a
+    permutation, so this is value for value what torch's autograd of the reference expression
+    gives (it scatters into +0.0, so only the sign of a zero may differ)."""
+
+    @staticmethod
+    def forward(ctx, h, mix_dev, inv_dev, lam):
+        if not _batch_dense(h):
+            h = h.contiguous()
+        out = torch.empty_like(h)
+        if h.shape[0] and h.numel():
+            with torch.cuda.device(h.device):
+                _blend_planes(h, out, mix_dev, lam)
+        ctx.save_for_backward(inv_dev)
+        ctx.lam = lam
+        ctx.strides = out.stride()
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (inv_dev,) = ctx.saved_tensors
+        if g.stride() != ctx.strides:
+            # an incoming gradient with other strides is brought to the forward output's layout
+            g = torch.empty_strided(g.shape, ctx.strides, dtype=g.dtype, device=g.device).copy_(g)
+        if not _batch_dense(g):
+            g = g.contiguous()
+        gh = torch.empty_like(g)
+        if g.shape[0] and g.numel():
+            with torch.cuda.device(g.device):
+                _blend_planes(g, gh, inv_dev, ctx.lam)
+        return gh, None, None, None
+
+
+def latent_blend(h: torch.Tensor, mix: np.ndarray, lam32) -> torch.Tensor:
+    """latentmixup's blend of the features ``h`` (float32 on a HIP device, batch outermost)."""
+    if not isinstance(h, torch.Tensor) or not h.is_cuda or h.dtype != torch.float32 or h.dim() < 1:
+        raise ValueError("latentmixup: the model's first half must return float32 features on a HIP device")
+    with torch.cuda.device(h.device):
+        mix_dev, inv_dev = latent_partners(mix, h.device)
+    return LatentBlend.apply(h, mix_dev, inv_dev, float(lam32))
+
+
+_LATENT = "latentmixup"   # _RECIPES marker of a method string that reaches the 1D latentmixup branch
+
+
+def latent_partners(mix: np.ndarray, device: torch.device):
+    """(mix, inverse permutation) as two int32 device vectors out of ONE upload.  Must be called
+    with ``device`` current."""
+    mix = np.ascontiguousarray(mix, dtype=np.int64)
+    B = mix.shape[0]
+    both = np.empty(2 * B, dtype=np.int32)
+    err = _lib.load().pcgmix_pack_partners_i32(mix.ctypes.data, B, both.ctypes.data)
+    if err:
+        if err in (-3, -4):
+            raise ValueError("latentmixup: the partners are not a permutation of the batch")
+        _lib.check(err, "pcgmix_pack_partners_i32")
+    both = upload_array(both, device)
+    return both[:B], both[B:]
+
+
+def _augment_latent(args, data, target_ohe, step: int, model, host_labels):
+    """The reference's 1D ``latentmixup`` branch (augmentations.py:1472-1506): gate, same-label
+    partners, ``args.depth = Random(step).randint(1, max_depth)``, ``model(data, depth, 'first')``,
+    lambda from numpy's global stream, then the differentiable HIP blend of the features.  Returns
+    (features, target_ohe unchanged, partners, None) and leaves ``args.depth`` set, as the reference
+    does (the training step resets it, train_model.py:538).  A rejected gate returns ``data``
+    itself and touches neither ``args.depth`` nor numpy's stream."""
+    _check_data(data, 3)
+    if model is None:
+        raise ValueError("latentmixup needs the model (augment(..., model, ...))")
+    labels = (lambda: labels_from_ohe(target_ohe)) if host_labels is None else np.asarray(host_labels)
+    plan = hostprep.latent_plan(args.method, getattr(args, "model", None), labels, step, data.shape[0])
+    if not plan.fired:
+        return data, target_ohe, [], None
+    args.depth = plan.depth
+    h = model(data, depth=plan.depth, pass_part="first")
+    return latent_blend(h, plan.mix, plan.lam32), target_ohe, plan.mix, None
+
+
 def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RESULTS_ARGS,
             host_labels=None):
     """See module docstring.  Returns ``(data, target_ohe, mix_indices, cut)``; when the method
@@ -590,6 +697,10 @@ def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RE
     method = args.method
     step = int(step_counter.count)
     recipe = _RECIPES.get(method, _RECIPES)
+    if recipe is _RECIPES and hostprep.latent_recipe(method) is not None:
+        recipe = _RECIPES[method] = _LATENT
+    if recipe is _LATENT:                         # latentmixup: the model's first half, blended
+        return _augment_latent(args, data, target_ohe, step, model, host_labels)
     if recipe is _RECIPES:                        # first sight of this method string
         recipe = hostprep.plain_recipe(method, False) \
             if hostprep.select_method(method, is2d=False) is not None else False

@@ -41,8 +41,9 @@ import numpy as np
 import torch
 
 from . import _lib, hostprep
-from .augmentations import (_as_numpy_frames, _check_data, _raw_stream, apply_plan, blend_targets,
-                            gate_passes, labels_from_ohe, splice_plain, upload_array)
+from .augmentations import (LatentBlend, _as_numpy_frames, _batch_dense, _blend_planes, _check_data,  # noqa: F401
+                            _raw_stream, apply_plan, blend_targets, gate_passes, labels_from_ohe,
+                            latent_blend, splice_plain, upload_array)
 
 
 def _stream(device) -> ctypes.c_void_p:
@@ -80,72 +81,6 @@ def piecewise_rows(data: torch.Tensor, segs: np.ndarray, mix: np.ndarray, axis: 
             data.data_ptr(), out.data_ptr(), dev.data_ptr(), dev.data_ptr() + segs.size * 4, axis,
             B, C, F, W, out_cols, _stream(data.device)), "pcgmix_piecewise_rows_f32")
     return out
-
-
-def _blend_planes(src: torch.Tensor, dst: torch.Tensor, mix_dev: torch.Tensor, lam: float) -> None:
-    """dst[b] = src[b]*lam + src[mix[b]]*(1-lam) over each sample's storage (batch outermost)."""
-    B = src.shape[0]
-    plane = src.numel() // B
-    _lib.check(_lib.load().pcgmix_blend_rows_f32(src.data_ptr(), dst.data_ptr(), mix_dev.data_ptr(),
-                                                 ctypes.c_float(lam), B, 1, plane, _stream(src.device)),
-               "pcgmix_blend_rows_f32")
-
-
-def _batch_dense(t: torch.Tensor) -> bool:
-    """Dense storage with the batch as the outermost stride: contiguous, or channels-last 4D."""
-    if t.is_contiguous():
-        return True
-    return t.dim() == 4 and t.is_contiguous(memory_format=torch.channels_last)
-
-
-class LatentBlend(torch.autograd.Function):
-    """``h*lam + h[mix]*(1-lam)`` (augmentations2d.py:535) on the HIP blend, differentiable.
-
-    Forward: ``pcgmix_blend_rows_f32`` over each sample's flat storage, so a channels-last feature
-    map keeps its layout (output strides = input strides).  Backward: the same kernel with the
-    inverse permutation, ``grad_h[b] = lam*g[b] + (1-lam)*g[inv[b]]`` — the partners are a
-    permutation, so this is value for value what torch's autograd of the reference expression
-    gives (it scatters into +0.0, so only the sign of a zero may differ)."""
-
-    @staticmethod
-    def forward(ctx, h, mix_dev, inv_dev, lam):
-        if not _batch_dense(h):
-            h = h.contiguous()
-        out = torch.empty_like(h)
-        if h.shape[0] and h.numel():
-            with torch.cuda.device(h.device):
-                _blend_planes(h, out, mix_dev, lam)
-        ctx.save_for_backward(inv_dev)
-        ctx.lam = lam
-        ctx.strides = out.stride()
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        (inv_dev,) = ctx.saved_tensors
-        if g.stride() != ctx.strides:
-            # an incoming gradient with other strides is brought to the forward output's layout
-            g = torch.empty_strided(g.shape, ctx.strides, dtype=g.dtype, device=g.device).copy_(g)
-        if not _batch_dense(g):
-            g = g.contiguous()
-        gh = torch.empty_like(g)
-        if g.shape[0] and g.numel():
-            with torch.cuda.device(g.device):
-                _blend_planes(g, gh, inv_dev, ctx.lam)
-        return gh, None, None, None
-
-
-def latent_blend(h: torch.Tensor, mix: np.ndarray, lam32) -> torch.Tensor:
-    """latentmixup's blend of the features ``h`` (float32 on a HIP device, batch outermost)."""
-    if not isinstance(h, torch.Tensor) or not h.is_cuda or h.dtype != torch.float32 or h.dim() < 1:
-        raise ValueError("latentmixup: the model's first half must return float32 features on a HIP device")
-    mix = np.asarray(mix, dtype=np.int64)
-    inv = np.empty_like(mix)
-    inv[mix] = np.arange(mix.shape[0])
-    with torch.cuda.device(h.device):
-        both = upload_array(np.concatenate([mix, inv]).astype(np.int32), h.device)
-    B = mix.shape[0]
-    return LatentBlend.apply(h, both[:B], both[B:], float(lam32))
 
 
 def _augment_baseline2d(args, data, target_ohe, frames, step: int, model, host_labels):

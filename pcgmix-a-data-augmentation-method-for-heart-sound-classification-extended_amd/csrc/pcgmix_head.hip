@@ -18,6 +18,10 @@
 //   potes_head_bwd_kernel   dz -> dW1 = dz^T x and dx = mask1 * scale1 * (dz W1) in ONE pass over
 //                           the feature matrix x (read once, written once: 9 bytes/element)
 //
+// and, in front of the same backward, the fused tail + loss pair
+//   potes_tail_loss_kernel / potes_tail_loss_latent_kernel (1D latentmixup: the hidden features are
+//   blended with the partners' inside the kernel) + potes_tail_loss_finalize_kernel
+//
 // Dropout: the caller hands over bytes (same shape as what they mask) and a threshold; an element
 // is kept iff its byte >= thr.  thr = 1 reads a 0/1 mask; thr = 256*p reads uniformly random
 // bytes from torch's generator (one `random_()` call for both masks: seeding behaves as with
@@ -529,6 +533,182 @@ __global__ __launch_bounds__(kTailRows* kHeadO * 4) void potes_tail_loss_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------ tail + loss, latent
+// potes_tail_loss_kernel for manifold mixup at the hidden layer (latentmixup with a Potes model,
+// augmentations.py:1472-1506 around models.py:456-465): the 20 hidden features of every row are
+// blended with those of its same-label partner BEHIND the ReLU and the Dropout(.5) — each row under
+// its own dropout bytes — and in front of Linear(20->C):
+//   h[b]  = relu(z[b]) * m2[b] * scale2            hm[b] = lam h[b] + (1-lam) h[mix[b]]
+//   logits[b] = W2 hm[b] + b2, loss and dl[b] as in the plain kernel
+//   dz[b] = fac[b] * W2^T (lam dl[b] + (1-lam) dl[inv[b]])        (inv = the inverse permutation)
+//   dW2 += dl[b] (x) hm[b],  db2 += dl[b],  db1 += dz[b]
+// Rows reach across blocks in both directions (mix[b] forward, inv[b] backward).  Instead of a
+// second launch or a wait between blocks, a block forms z for its four rows AND for their mix and
+// inv rows from the split-K partials — three 20-vectors per row, summed in exactly the order of the
+// row's own block, so the recomputed values are bit-identical to the stored ones — and then has
+// everything locally: h[mix[b]] for the forward, and for dl[inv[b]] the logits of row inv[b], whose
+// own partner is mix[inv[b]] = b.  That triples the reads of `partial` (KS*B*20 floats) and adds
+// nothing to the passes over the features.  z, logits and dz are written for the block's own rows
+// only, z un-blended, so potes_tail_loss_finalize_kernel and potes_head_bwd_kernel follow unchanged.
+// lam = 1 gives the plain kernel's values bit for bit (1*a + 0*b, same fmaf chains).
+__global__ __launch_bounds__(kTailRows* kHeadO * 4) void potes_tail_loss_latent_kernel(
+    const float* __restrict__ partial, int KS, const float* __restrict__ b1,
+    const uint8_t* __restrict__ mask2, float scale2, int thr2, const float* __restrict__ w2,
+    const float* __restrict__ b2, const float* __restrict__ target, float* __restrict__ z,
+    float* __restrict__ logits, float* __restrict__ dz, float* __restrict__ ws,
+    float* __restrict__ zero, long long n_zero, int B, int C, int nrb, int target_kind,
+    const int32_t* __restrict__ mix, const int32_t* __restrict__ inv, float lam) {
+  if ((int)blockIdx.x >= nrb) {    // the other blocks clear the buffer head_bwd accumulates dW1 into
+    const int nz = (int)gridDim.x - nrb;
+    const long long per = (n_zero + nz - 1) / nz;
+    const long long lo = (long long)((int)blockIdx.x - nrb) * per;
+    const long long hi = lo + per < n_zero ? lo + per : n_zero;
+    for (long long i = lo + threadIdx.x; i < hi; i += blockDim.x) zero[i] = 0.f;
+    return;
+  }
+  // set 0: the block's own rows, 1: their partners mix[b], 2: the rows inv[b] they are partner of
+  __shared__ float h[3][kTailRows][kHeadO], fac[kTailRows][kHeadO], dzl[kTailRows][kHeadO];
+  __shared__ float hm[2][kTailRows][kHeadO];               // blended: own rows, inv rows
+  __shared__ float lg[2][kTailRows][kHeadMaxC], dl[2][kTailRows][kHeadMaxC], rl[kTailRows];
+  __shared__ int rows[3][kTailRows];
+  const int t = threadIdx.x, q = t & 3, e = t >> 2;            // e = r * kHeadO + o
+  const int r = e / kHeadO, o = e - r * kHeadO;
+  const int row = blockIdx.x * kTailRows + r;
+  const float oml = 1.f - lam;
+  int src[3];
+  src[0] = row < B ? row : 0;
+  src[1] = min(max(mix[src[0]], 0), B - 1);                // clamped: a bad index must not read outside
+  src[2] = min(max(inv[src[0]], 0), B - 1);
+  if (o == 0 && q == 0) {
+    rows[0][r] = src[0]; rows[1][r] = src[1]; rows[2][r] = src[2];
+  }
+  const size_t plane = (size_t)B * kHeadO;
+  size_t i3[3];
+  float v[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < 3; ++s) i3[s] = (size_t)src[s] * kHeadO + o;
+  int ks = q;
+  for (; ks + 12 < KS; ks += 16) {                  // twelve independent loads in flight
+    float t0[3], t1[3], t2[3], t3[3];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) {
+      t0[s] = partial[(size_t)ks * plane + i3[s]];
+      t1[s] = partial[(size_t)(ks + 4) * plane + i3[s]];
+      t2[s] = partial[(size_t)(ks + 8) * plane + i3[s]];
+      t3[s] = partial[(size_t)(ks + 12) * plane + i3[s]];
+    }
+#pragma unroll
+    for (int s = 0; s < 3; ++s) { v[s] += t0[s]; v[s] += t1[s]; v[s] += t2[s]; v[s] += t3[s]; }
+  }
+  for (; ks < KS; ks += 4) {
+#pragma unroll
+    for (int s = 0; s < 3; ++s) v[s] += partial[(size_t)ks * plane + i3[s]];
+  }
+#pragma unroll
+  for (int s = 0; s < 3; ++s) {
+    v[s] += __shfl_xor(v[s], 1, 64);
+    v[s] += __shfl_xor(v[s], 2, 64);
+  }
+  if (q < 3) {                     // lane q of the four finishes set q (all four hold the sums)
+    const float bias = b1 ? b1[o] : 0.f;
+    const float vv = (q == 0 ? v[0] : q == 1 ? v[1] : v[2]) + bias;
+    const size_t ii = q == 0 ? i3[0] : q == 1 ? i3[1] : i3[2];
+    float hv = 0.f, f = 0.f;
+    if (row < B) {
+      if (q == 0) z[ii] = vv;      // stored un-blended, the block's own rows only
+      f = vv > 0.f ? 1.f : 0.f;
+      if (mask2) f = (int)mask2[ii] >= thr2 ? f * scale2 : 0.f;
+      hv = vv * f;
+    }
+    h[q][r][o] = hv;
+    if (q == 0) fac[r][o] = f;
+  }
+  __syncthreads();
+  if (q == 0) hm[0][r][o] = lam * h[0][r][o] + oml * h[1][r][o];
+  else if (q == 1) hm[1][r][o] = lam * h[2][r][o] + oml * h[0][r][o];   // mix[inv[b]] = b
+  __syncthreads();
+  {                                // logits: wave 0 the own rows, wave 1 the inv rows
+    const int set = t >> 6, tt = t & 63;
+    if (set < 2 && tt < kTailRows * C) {
+      const int rr = tt / C, c = tt - rr * C;
+      const int row2 = blockIdx.x * kTailRows + rr;
+      float a = 0.f;
+      if (row2 < B) {
+        a = b2 ? b2[c] : 0.f;
+#pragma unroll
+        for (int k = 0; k < kHeadO; ++k) a = fmaf(hm[set][rr][k], w2[c * kHeadO + k], a);
+        if (set == 0) logits[(size_t)row2 * C + c] = a;
+      }
+      lg[set][rr][c] = a;
+    }
+  }
+  __syncthreads();
+  {                                // soft-target CE and dlogits of the own rows and of the inv rows
+    const int set = t >> 6, tt = t & 63;
+    if (set < 2 && tt < kTailRows) {
+      const int row2 = blockIdx.x * kTailRows + tt;
+      float loss_r = 0.f;
+      if (row2 < B) {
+        const int trow = set == 0 ? row2 : rows[2][tt];      // whose target
+        float tg[kHeadMaxC];
+        if (target_kind) {
+          const int lab = reinterpret_cast<const uint8_t*>(target)[trow];
+          for (int c = 0; c < C; ++c) tg[c] = c == lab ? 1.f : 0.f;
+        } else {
+          for (int c = 0; c < C; ++c) tg[c] = target[(size_t)trow * C + c];
+        }
+        const float* l = lg[set][tt];
+        float m = l[0];
+        for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
+        float se = 0.f, ts = 0.f;
+        for (int c = 0; c < C; ++c) {
+          se += expf(l[c] - m);
+          ts += tg[c];
+        }
+        const float lse = logf(se), inv_b = 1.f / (float)B;
+        for (int c = 0; c < C; ++c) {
+          loss_r -= (l[c] - m - lse) * tg[c];
+          dl[set][tt][c] = inv_b * (expf(l[c] - m - lse) * ts - tg[c]);
+        }
+      } else {
+        for (int c = 0; c < C; ++c) dl[set][tt][c] = 0.f;
+      }
+      if (set == 0) rl[tt] = loss_r;
+    }
+  }
+  __syncthreads();
+  if (q == 0) {                    // dz = (z > 0) * m2 * ((lam dl[b] + (1-lam) dl[inv[b]]) W2)
+    float sacc = 0.f;
+    for (int c = 0; c < C; ++c)
+      sacc = fmaf(lam * dl[0][r][c] + oml * dl[1][r][c], w2[c * kHeadO + o], sacc);
+    const float d = sacc * fac[r][o];
+    dzl[r][o] = d;
+    if (row < B) dz[i3[0]] = d;
+  }
+  __syncthreads();
+  float* out = ws + (size_t)blockIdx.x * kTlStride;
+  if (t < kHeadMaxC * kHeadO) {    // dW2[c][o] contribution of these rows: dl (x) the BLENDED features
+    const int c = t / kHeadO, oo = t - c * kHeadO;
+    float a = 0.f;
+    if (c < C)
+      for (int rr = 0; rr < kTailRows; ++rr) a = fmaf(dl[0][rr][c], hm[0][rr][oo], a);
+    out[t] = a;
+  } else if (t < kHeadMaxC * kHeadO + kHeadMaxC) {
+    const int c = t - kHeadMaxC * kHeadO;
+    float a = 0.f;
+    if (c < C)
+      for (int rr = 0; rr < kTailRows; ++rr) a += dl[0][rr][c];
+    out[t] = a;
+  } else if (t < kHeadMaxC * kHeadO + kHeadMaxC + kHeadO) {
+    const int oo = t - kHeadMaxC * kHeadO - kHeadMaxC;
+    float a = 0.f;
+    for (int rr = 0; rr < kTailRows; ++rr) a += dzl[rr][oo];
+    out[t] = a;
+  } else if (t == kHeadMaxC * kHeadO + kHeadMaxC + kHeadO) {
+    out[t] = (rl[0] + rl[1]) + (rl[2] + rl[3]);
+  }
+}
+
 // Column t of the per-block contributions, summed in a FIXED order: four threads per column
 // take a quarter of the row blocks each (their loads all in flight together), then thread 0 of
 // the column adds the four partial sums in order.  (One thread walking all 64 row blocks took
@@ -671,6 +851,34 @@ extern "C" int pcgmix_potes_head_loss_fwd_f32(const float* x, const uint8_t* mas
   if (!defer_finalize)
     hipLaunchKernelGGL(potes_tail_loss_finalize_kernel, dim3(1), dim3(kTlStride * kTlSeg), 0, s, ws,
                        nrb, loss, small, B, C);
+  return (int)hipGetLastError();
+}
+
+extern "C" int pcgmix_potes_head_loss_latent_fwd_f32(
+    const float* x, const uint8_t* mask1, float scale1, int thr1, int bits1, const float* w1,
+    const float* b1, const uint8_t* mask2, float scale2, int thr2, const float* w2, const float* b2,
+    const float* target, float* partial, float* z, float* logits, float* dz, float* loss,
+    float* small, float* ws, float* dw1_zero, int target_kind, int B, int K, int C,
+    const int32_t* mix, const int32_t* inv, float lam, pcgmix_stream_t stream) {
+  using namespace pcgmix;
+  if (!w2 || !target || !z || !logits || !dz || !loss || !small || !ws || !mix || !inv || B <= 0 ||
+      C <= 0 || C > kHeadMaxC || (reinterpret_cast<uintptr_t>(dz) & 15) ||
+      (target_kind != 0 && target_kind != 1) || !(lam >= 0.f && lam <= 1.f))
+    return hipErrorInvalidValue;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const hipError_t e =
+      launch_skinny_partial(x, w1, partial, B, K, kHeadO, s, mask1, scale1, thr1, bits1);
+  if (e != hipSuccess) return (int)e;
+  const int KS = pcgmix_skinny_linear_splits(B, K);
+  const int nrb = (B + kTailRows - 1) / kTailRows;
+  const long long n_zero = dw1_zero ? (long long)kHeadO * K : 0;
+  const unsigned zero_blocks = (unsigned)((n_zero + 4095) / 4096);
+  hipLaunchKernelGGL(potes_tail_loss_latent_kernel, dim3((unsigned)nrb + zero_blocks),
+                     dim3(kTailRows * kHeadO * 4), 0, s, partial, KS, b1, mask2, scale2, thr2, w2, b2,
+                     target, z, logits, dz, ws, dw1_zero, n_zero, B, C, nrb, target_kind, mix, inv,
+                     lam);
+  hipLaunchKernelGGL(potes_tail_loss_finalize_kernel, dim3(1), dim3(kTlStride * kTlSeg), 0, s, ws,
+                     nrb, loss, small, B, C);
   return (int)hipGetLastError();
 }
 

@@ -282,6 +282,19 @@ extern "C" int pcgmix_partner_permutation_i64(const int32_t* group_id, int B, in
   return hipSuccess;
 }
 
+extern "C" int pcgmix_pack_partners_i32(const int64_t* mix, int B, int32_t* out) {
+  if (!mix || !out || B < 0) return hipErrorInvalidValue;
+  for (int b = 0; b < B; ++b) out[B + b] = -1;
+  for (int b = 0; b < B; ++b) {
+    const int64_t m = mix[b];
+    if (m < 0 || m >= B) return -3;
+    if (out[B + m] >= 0) return -4;              // two rows share a partner
+    out[b] = (int32_t)m;
+    out[B + m] = b;
+  }
+  return hipSuccess;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Validate the boundaries and pack the per-step index block the kernels read:
 //   int32 frames[B][5] | int32 mix[B] | int32 rand_off[B][4] (optional) | int32 rect[B][4] (optional)

@@ -296,6 +296,61 @@ def salopt_recipe(method: str):
     return mode, parse_alpha(method, name), sigma, knot + 2
 
 
+# Names whose branch comes BEFORE 'latentmixup' in the reference's 1D if-chain (augmentations.py:
+# 734-1396) and is entered on a bare substring test; the bare-'mixup' branch (:829) excludes
+# 'latentmixup' by its own condition, and what comes later ('cutmix', 'cutout', ...) never gets a
+# turn.
+_BEFORE_LATENT_1D = (
+    "durmixrespscale", "respiratoryscale", "timemask", "durmixmagwarp", "durratiomixup",
+    "wav-durratiocutmix", "timewarp", "magnitudewarp", "gaussiannoise", "durratiocutmix",
+    "lengthcutmix", "datasetcutmix", "wavcutmix", "lc-nointrusion", "labelcutmix", "swapsysdia",
+    "cont-cutmix", "saliency-cutmix")
+# max_model_depth of the reference's 1D branch (augmentations.py:1484-1493) for the models served here
+LATENT_MAX_DEPTH_1D = {"Potes": 1, "resnet9": 3}
+
+
+@functools.lru_cache(maxsize=256)
+def latent_recipe(method: str):
+    """``(p,)`` when the reference's 1D if-chain reaches its ``latentmixup`` branch for ``method``
+    (augmentations.py:1472-1506), None otherwise.  ``select_method`` keeps refusing the name: it
+    answers "which augmentation of the WAVEFORM runs", and every caller of it goes on to launch
+    one; latentmixup leaves the waveform alone and needs the model, so ``augment()`` and the
+    training step ask here first."""
+    if "latentmixup" not in method or any(n in method for n in _BEFORE_LATENT_1D):
+        return None
+    return (parse_probability(method),)
+
+
+def latent_depth(model_name, step: int) -> int:
+    """``Random(step).randint(1, max_model_depth)`` (augmentations.py:1494).  Models for which the
+    reference leaves ``max_model_depth`` unbound (it fails there) are refused."""
+    top = LATENT_MAX_DEPTH_1D.get(model_name)
+    if top is None:
+        raise NotImplementedError(f"latentmixup: the mixing depth is defined for args.model in "
+                                  f"{tuple(LATENT_MAX_DEPTH_1D)} only, got {model_name!r}")
+    return 1 + int(_lib.load().pcgmix_py_randint0(int(step), top - 1))
+
+
+def latent_plan(method: str, model_name, labels, step: int, batch: int) -> MixPlan:
+    """Host draws of one 1D latentmixup step in the reference's order (augmentations.py:1477-1497):
+    gate, same-label partners, depth, then ``get_lambda(alpha=1)`` — numpy's global stream is
+    reseeded only when the gate fires.  ``labels``: array or zero-argument callable (asked after
+    the gate).  ``plan.mix`` are the partners, ``plan.depth`` the model depth, ``plan.lam64/32``."""
+    recipe = latent_recipe(method)
+    if recipe is None:
+        raise ValueError(f"{method!r} does not reach the reference's 1D latentmixup branch")
+    if LATENT_MAX_DEPTH_1D.get(model_name) is None:
+        latent_depth(model_name, step)                         # raises
+    if not (recipe[0] >= 1.0 or gate_fires(method, step)):
+        return MixPlan(fired=False, step=step)
+    plan = MixPlan(fired=True, name="latentmixup", step=step)
+    plan.mix = shuffle_within_groups(_host_labels(labels, batch).astype(np.int64, copy=False), step)
+    plan.depth = latent_depth(model_name, step)
+    plan.lam64, _ = draw_lambda_knots(step, 1.0, 0.0, 0)
+    plan.lam32 = np.float32(plan.lam64)
+    return plan
+
+
 def soft_targets(method: str) -> bool:
     """True when a fired step blends the one-hot targets into floats: '(mixAll)' (augmentations.py:
     915-917, 978-980) and 'mixup(mix)' (:857).  A training step then needs the float targets."""

@@ -7,6 +7,9 @@
 Both keep the reference's ``forward(x, depth=None, pass_part=None)`` signature; the training
 loop calls ``model(data, depth=0, pass_part='second')`` (train_model.py:537), which is the plain
 full forward pass.  Convolutions run through MIOpen (MFMA paths for the ResNet9 GEMMs).
+``depth`` > 0 splits the pass for 1D latentmixup (augmentations.py:1494-1495): 'first' returns the
+hidden features, 'second' continues from them; for CNN_potes on the fused head the blend of those
+features can also happen inside the head's tail kernel (``loss_and_logits(..., latent=...)``).
 """
 from __future__ import annotations
 
@@ -289,7 +292,14 @@ class PotesHeadLossFunction(torch.autograd.Function):
     the backward kernel (no extra launch)."""
 
     @staticmethod
-    def forward(ctx, feat, w1, b1, w2, b2, target, p1, p2, training, rnd=None, defer=False):
+    def forward(ctx, feat, w1, b1, w2, b2, target, p1, p2, training, rnd=None, defer=False,
+                latent=None):
+        # latent = (mix_dev, inv_dev, lam): manifold mixup at the hidden layer (1D latentmixup at
+        # depth 1) inside the tail kernel — the 20 hidden features of every row, behind ReLU and
+        # Dropout(p2), are blended with those of row mix[b] in front of Linear(20->C)
+        # (``pcgmix_potes_head_loss_latent_fwd_f32``; int32 device vectors of the partner
+        # permutation and its inverse, see ``augmentations.latent_partners``).  Same launches as
+        # the plain step, same backward.
         # defer: leave the forward's finalize launch (loss and small gradients from the per-row-block
         # contributions) to the backward's feature pass — the loss is then only valid after
         # backward.  For callers whose forward and backward always run together and who cannot
@@ -332,14 +342,30 @@ class PotesHeadLossFunction(torch.autograd.Function):
         dw1 = torch.empty_like(w1c) if need_dw1 else None
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         opt = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
-        defer = bool(defer and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]))
-        _lib.check(lib.pcgmix_potes_head_loss_fwd_f32(
-            x.data_ptr(), opt(mask1), ctypes.c_float(s1), thr1, bits1, w1c.data_ptr(),
-            b1.detach().data_ptr() if b1 is not None else None, opt(mask2), ctypes.c_float(s2), thr2,
-            w2c.data_ptr(), b2.detach().data_ptr() if b2 is not None else None, tgt.data_ptr(),
-            partial.data_ptr(), z.data_ptr(), logits.data_ptr(), dz.data_ptr(), loss.data_ptr(),
-            small.data_ptr(), ws.data_ptr(), opt(dw1), int(defer), int(hard), B, K, C, stream),
-            "pcgmix_potes_head_loss_fwd_f32")
+        defer = bool(defer and latent is None
+                     and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]))
+        if latent is not None:
+            mix_dev, inv_dev, lam = latent
+            for v in (mix_dev, inv_dev):
+                if v.dtype != torch.int32 or v.shape != (B,) or v.device != dev or not v.is_contiguous():
+                    raise ValueError("latent: mix and inv must be contiguous int32 (B,) tensors on "
+                                     "the features' device")
+            _lib.check(lib.pcgmix_potes_head_loss_latent_fwd_f32(
+                x.data_ptr(), opt(mask1), ctypes.c_float(s1), thr1, bits1, w1c.data_ptr(),
+                b1.detach().data_ptr() if b1 is not None else None, opt(mask2), ctypes.c_float(s2),
+                thr2, w2c.data_ptr(), b2.detach().data_ptr() if b2 is not None else None,
+                tgt.data_ptr(), partial.data_ptr(), z.data_ptr(), logits.data_ptr(), dz.data_ptr(),
+                loss.data_ptr(), small.data_ptr(), ws.data_ptr(), opt(dw1), int(hard), B, K, C,
+                mix_dev.data_ptr(), inv_dev.data_ptr(), ctypes.c_float(float(lam)), stream),
+                "pcgmix_potes_head_loss_latent_fwd_f32")
+        else:
+            _lib.check(lib.pcgmix_potes_head_loss_fwd_f32(
+                x.data_ptr(), opt(mask1), ctypes.c_float(s1), thr1, bits1, w1c.data_ptr(),
+                b1.detach().data_ptr() if b1 is not None else None, opt(mask2), ctypes.c_float(s2), thr2,
+                w2c.data_ptr(), b2.detach().data_ptr() if b2 is not None else None, tgt.data_ptr(),
+                partial.data_ptr(), z.data_ptr(), logits.data_ptr(), dz.data_ptr(), loss.data_ptr(),
+                small.data_ptr(), ws.data_ptr(), opt(dw1), int(defer), int(hard), B, K, C, stream),
+                "pcgmix_potes_head_loss_fwd_f32")
         ctx.save_for_backward(x, w1c, dz, small, mask1, dw1)
         # the backward writes the loss through this alias (no version check: under capture nobody
         # can have touched it in between)
@@ -356,7 +382,7 @@ class PotesHeadLossFunction(torch.autograd.Function):
         x, w1, dz, small, mask1, dw1 = ctx.saved_tensors
         ws, loss = ctx.deferred
         if gloss is None:                       # nothing upstream of the loss
-            return (None,) * 11
+            return (None,) * 12
         # dW1 is accumulated (two row halves, atomicAdd) into the buffer the FORWARD zeroed and is
         # returned as the gradient: a second backward over the same graph would add onto the first
         # result — which may already be p.grad — without an error.  Refuse it.
@@ -381,7 +407,7 @@ class PotesHeadLossFunction(torch.autograd.Function):
         dw2 = small_out[:C * 20].view(C, 20)
         db2 = small_out[C * 20:C * 20 + C] if ctx.has_b2 else None
         db1 = small_out[C * 20 + C:] if ctx.has_b1 else None
-        return dx, dw1, db1, dw2, db2, None, None, None, None, None, None
+        return dx, dw1, db1, dw2, db2, None, None, None, None, None, None, None
 
 
 def _potes_block(c_in: int, c_out: int, dropout: float = 0.0) -> nn.Sequential:
@@ -478,11 +504,14 @@ class CNN_potes(nn.Module):
                                        float(drop.p) if drop is not None else 0.0,
                                        float(self.dropout.p), self.training, rnd)
 
-    def loss_and_logits(self, x: torch.Tensor, target: torch.Tensor):
+    def loss_and_logits(self, x: torch.Tensor, target: torch.Tensor, latent=None):
         """(soft-target cross entropy, logits) of the whole network in one chain of HIP kernels
         — the conv stack, then head and loss as ONE autograd node (``PotesHeadLossFunction``).
         Needs ``_fused_head(x)``; ``target`` is the (B, classes) one-hot / soft target matrix, or
-        — hard targets — a uint8 (B,) tensor of class labels."""
+        — hard targets — a uint8 (B,) tensor of class labels.  ``latent = (mix_dev, inv_dev, lam)``:
+        the step is a 1D ``latentmixup`` one at depth 1 — the hidden features are blended with the
+        partners' inside the head's tail kernel (``PotesHeadLossFunction``); what
+        ``model(x, 1, 'first')`` -> blend -> ``model(h, 1, 'second')`` -> CELoss computes."""
         B, C, T = x.shape
         c1, c2 = self.cnn1[0][0], self.cnn1[1][0]
         rows = x[:, :4, :].reshape(B * 4, T)
@@ -495,7 +524,7 @@ class CNN_potes(nn.Module):
         return PotesHeadLossFunction.apply(z.reshape(B, -1), self.dimreduc.weight, self.dimreduc.bias,
                                            self.linear.weight, self.linear.bias, target,
                                            float(drop.p) if drop is not None else 0.0,
-                                           float(self.dropout.p), self.training, rnd, defer)
+                                           float(self.dropout.p), self.training, rnd, defer, latent)
 
     def features(self, x: torch.Tensor) -> torch.Tensor:
         B, C, T = x.shape

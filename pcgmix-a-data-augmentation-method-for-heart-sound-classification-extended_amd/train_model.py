@@ -450,6 +450,50 @@ def fused_loss_model(model, criterion, data, target_ohe, epoch):
     return model
 
 
+LATENT_DDP_MESSAGE = ("latentmixup under torch.distributed is not supported: it runs the "
+                      "model in two halves per step, which the DDP step does not handle")
+LATENT_GRAPH_MESSAGE = ("latentmixup is not wired into the captured step: its per-step partners and "
+                        "lambda have no slot in the graph's static block; use train_step")
+
+
+def latent_method(args) -> bool:
+    """True when ``args.method`` reaches the reference's 1D ``latentmixup`` branch on a time-series
+    dataset (``hostprep.latent_recipe``)."""
+    return args.dataset not in SPECTROGRAM_DATASETS \
+        and augmentations.hostprep.latent_recipe(args.method) is not None
+
+
+def latent_fused_model(args, model, criterion, data, target_ohe, epoch):
+    """The CNN_potes that runs a 1D ``latentmixup`` step inside its fused head (the blend happens in
+    the tail kernel, ``CNN_potes.loss_and_logits(..., latent=...)``), or None when the step takes
+    the drop-in path ``augment()`` + ``model(h, depth, 'second')``: any other model or a wrapped
+    one, the SELC phase, targets that need a gradient, CPU tensors, ``args.model`` other than
+    'Potes' (the only name whose depth is always 1) — or on request: ``args.latent_fused = False``
+    or ``PCGMIX_NO_LATENT_FUSED`` in the environment (tests and A/B timing)."""
+    if not latent_method(args) or getattr(args, "model", None) != "Potes":
+        return None
+    if not getattr(args, "latent_fused", True) or os.environ.get("PCGMIX_NO_LATENT_FUSED") is not None:
+        return None
+    return fused_loss_model(model, criterion, data, target_ohe, epoch)
+
+
+def latent_host_step(args, data, target, target_ohe, step: int):
+    """Host part of a fused 1D ``latentmixup`` step, exactly what ``augment()`` does in front of the
+    model's first half (augmentations.py:1472-1497): gate, same-label partners, ``args.depth``,
+    lambda from numpy's global stream; then the partners and their inverse go up in one copy.
+    Returns ``(mix_dev, inv_dev, lam)``, or None when the gate rejects the step (``args.depth`` and
+    numpy's stream untouched)."""
+    labels = target.numpy() if not target.is_cuda \
+        else (lambda: augmentations.labels_from_ohe(target_ohe))
+    plan = augmentations.hostprep.latent_plan(args.method, args.model, labels, step, data.shape[0])
+    if not plan.fired:
+        return None
+    args.depth = plan.depth
+    with torch.cuda.device(data.device):
+        mix_dev, inv_dev = augmentations.latent_partners(plan.mix, data.device)
+    return mix_dev, inv_dev, float(plan.lam32)
+
+
 def train_step(args, model, batch, device, optimizer, scheduler, criterion, epoch, step_counter,
                stats: Optional[dict] = None, sync: Optional["FlatGradSync"] = None):
     """One iteration of the reference's batch loop (train_model.py:498-582) without host syncs.
@@ -459,13 +503,21 @@ def train_step(args, model, batch, device, optimizer, scheduler, criterion, epoc
     data = data.to(device, non_blocking=True)
     target_ohe = F.one_hot(target, args.num_classes).to(device, non_blocking=True)
     aug = augmentations2d if args.dataset in SPECTROGRAM_DATASETS else augmentations
-    data, target_ohe, _, _ = aug.augment(args, data, target_ohe, frames, wav,
-                                         augmentation_counter(args, step_counter), model, device, None,
-                                         host_labels=target.numpy() if not target.is_cuda else None)
-    fused = fused_loss_model(model, criterion, data, target_ohe, epoch) \
-        if getattr(args, "depth", 0) == 0 else None
+    latent = None
+    fused = latent_fused_model(args, model, criterion, data, target_ohe, epoch)
+    if fused is not None:
+        # 1D latentmixup on the fused Potes path: the same launch chain as a plain step, the blend
+        # of the hidden features happens inside the head's tail kernel
+        latent = latent_host_step(args, data, target, target_ohe,
+                                  int(augmentation_counter(args, step_counter).count))
+    else:
+        data, target_ohe, _, _ = aug.augment(args, data, target_ohe, frames, wav,
+                                             augmentation_counter(args, step_counter), model, device, None,
+                                             host_labels=target.numpy() if not target.is_cuda else None)
+        fused = fused_loss_model(model, criterion, data, target_ohe, epoch) \
+            if getattr(args, "depth", 0) == 0 else None
     if fused is not None:                   # head + loss as one autograd node (two launches, not four)
-        loss, out = fused.loss_and_logits(data, target_ohe)
+        loss, out = fused.loss_and_logits(data, target_ohe, latent=latent)
     else:
         out = model(data, depth=getattr(args, "depth", 0), pass_part="second")
         loss = criterion(out, target_ohe, indices, epoch, "train")
@@ -519,6 +571,8 @@ class GraphedTrainStep:
                  sig_len, sync: Optional[FlatGradSync] = None):
         if args.dataset in SPECTROGRAM_DATASETS:
             raise NotImplementedError("graphed step is wired for the 1D path")
+        if latent_method(args):
+            raise NotImplementedError(LATENT_GRAPH_MESSAGE)
         self.args, self.model, self.opt, self.sched = args, model, optimizer, scheduler
         self.ce = criterion.CEloss if hasattr(criterion, "CEloss") else criterion
         self.es = getattr(criterion, "es", None)
@@ -955,12 +1009,15 @@ def _epoch_graphed_step(args, model, optimizer, scheduler, criterion, device, ep
     what ``GraphedTrainStep`` needs; the graph is built at the first batch and kept for as long as
     model, optimiser, scheduler, criterion, method and batch shape stay the same objects/values
     (the reference creates them once per run, train_model.py:293-410).  ``args.hipgraph = False``
-    switches it off.  Eager: CPU, spectrogram datasets, wrapped (DataParallel/DDP) models, a
+    switches it off.  Eager: CPU, spectrogram datasets, 1D latentmixup (per-step partners and lambda
+    have no slot in the capture), wrapped (DataParallel/DDP) models, a
     criterion other than ``SELCLoss``, epochs past its turning point, an active process group
     (use ``train_model()`` / ``FlatGradSync`` there)."""
     if not getattr(args, "hipgraph", True) or device.type != "cuda":
         return None
     if args.dataset in SPECTROGRAM_DATASETS or not isinstance(criterion, SELCLoss):
+        return None
+    if latent_method(args):                 # per-step partners and lambda: not captured (train_step)
         return None
     if not isinstance(model, (models.CNN_potes, models.ResNet9_myrtle)):
         return None
@@ -1153,8 +1210,10 @@ def train_model(args, dataset, device, use_graph: bool = True, log=print, pipeli
         if hostprep.select_method(args.method, is2d=True) == "latentmixup":
             # two half passes of the DDP-wrapped model in one iteration (augmentations2d.py:523 and
             # the training step's 'second' pass): refused rather than reduced twice or not at all
-            raise NotImplementedError("latentmixup under torch.distributed is not supported: it runs the "
-                                      "model in two halves per step, which the DDP step does not handle")
+            raise NotImplementedError(LATENT_DDP_MESSAGE)
+    if not spectro and latent_method(args) and dist.is_available() and dist.is_initialized() \
+            and dist.get_world_size() > 1:
+        raise NotImplementedError(LATENT_DDP_MESSAGE)
     seed_fix = 4                                                   # :217
     args.seed_fix = seed_fix
     torch.manual_seed(seed_fix)
@@ -1178,7 +1237,8 @@ def train_model(args, dataset, device, use_graph: bool = True, log=print, pipeli
     args.num_steps = args.num_epochs * (len(train_loader.dataset) // args.batch_size)   # :390
     criterion = SELCLoss(train_labels, args.num_classes, es=selc_turning_point(args), device=device)
     # (the spectrogram step is 80 ms of MIOpen convolutions: nothing for a graph to win, it stays eager)
-    graphable = use_graph and device.type == "cuda" and args.num_epochs <= criterion.es and not spectro
+    graphable = use_graph and device.type == "cuda" and args.num_epochs <= criterion.es and not spectro \
+        and not latent_method(args)         # latentmixup: eager step (not wired into the capture)
     if not graphable:
         model = wrap_distributed(model, device)
     optimizer, scheduler = make_optimizer(args, model)
