@@ -31,7 +31,7 @@ extern "C" {
  * language binding does not need the HIP headers). */
 typedef struct ihipStream_t* pcgmix_stream_t;
 
-#define PCGMIX_ABI_VERSION 20
+#define PCGMIX_ABI_VERSION 21
 
 /* ABI version of the loaded library (== PCGMIX_ABI_VERSION it was built with). */
 int pcgmix_abi_version(void);
@@ -882,6 +882,40 @@ int pcgmix_zero_rects_f32(float* x, const int32_t* rect, int B, int C, int F, in
                           pcgmix_stream_t stream);
 int pcgmix_piecewise_rows_f32(const float* x, float* y, const int32_t* segs, const int32_t* mix,
                               int axis, int B, int C, int F, int W, int Wo, pcgmix_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The heart-cycle cut-and-paste family and durmixrespscale.  csrc/pcgmix_cutpaste.hip.
+ *
+ * One launch each, on (B, C, T) float32 contiguous batches; the RNG, the partner selection and the
+ * per-sample tables stay in hostprep.py.  B == 0 returns 0 and launches nothing.  The input and
+ * the output may not overlap (every sample reads its partner's rows).
+ *
+ * pcgmix_cutpaste_rows_f32 — replaces the per-sample loops around cutmix_keepdur_multidim_tensors
+ *   (augmentations.py:340-366; the branches :983-1000 wav-durratiocutmix, :1101-1119
+ *   durratiocutmix) and cutmix_multidim_tensors (:30-58; :1121-1151 lengthcutmix, :1153-1182
+ *   datasetcutmix, :1184-1213 wavcutmix, :1285-1316 labelcutmix, with their 'cutout' suffix):
+ *     segs device int32 (B, PCGMIX_PIECE_SEGS, 4), {lo, hi, src, shift} along T in the convention
+ *     of pcgmix_piecewise_rows_f32 (contiguous, ordered; positions beyond the last hi and source
+ *     positions outside [0, T) give 0); mix device int32 (B), values in [0, B).
+ *     junctions: NULL, or device int32 (B, 4) {c1, c2, ov, unused} — the '(smooth)' cross-fade
+ *     (:41-51): for ov in 1..PCGMIX_CUTPASTE_MAX_OVERLAP and t in [c1-ov, c1+ov), j = t-(c1-ov),
+ *       y[b,c,t] = float(double(x[b,c,t]) * (1 - s[j]) + double(x[mix[b],c,c2-ov+j]) * s[j])
+ *     (float64 multiply, multiply, add, each rounded on its own, then one rounding to float32)
+ *     unless t lies in a ZERO segment; ov outside that range: no window.  sigmoid_tab: device
+ *     float64 (PCGMIX_CUTPASTE_MAX_OVERLAP, 2*PCGMIX_CUTPASTE_MAX_OVERLAP), row ov-1 = the
+ *     reference's sigmoid(ov) (:668-672) in its first 2*ov entries; required with junctions.
+ * pcgmix_mix_scale_f32 — durmixrespscale (:734-775): the splice of pcgmix_mix_warp_f32 without
+ *   warp (frames, mix_idx, off as there; fp32 mul, mul, add) and then, for EVERY element,
+ *     y[b,c,t] = float(double(splice[b,c,t]) * row[t])
+ *   with row device float64 (T) — one launch instead of the splice followed by
+ *   pcgmix_scale_rows_f32.                                                                   */
+#define PCGMIX_CUTPASTE_MAX_OVERLAP 10
+int pcgmix_cutpaste_rows_f32(const float* x, float* y, const int32_t* segs, const int32_t* mix,
+                             const int32_t* junctions, const double* sigmoid_tab, int B, int C,
+                             int T, pcgmix_stream_t stream);
+int pcgmix_mix_scale_f32(const float* x, float* y, const int32_t* frames, const int32_t* mix_idx,
+                         const int32_t* off, float lam, const double* row, int B, int C, int T,
+                         pcgmix_stream_t stream);
 
 #ifdef __cplusplus
 }

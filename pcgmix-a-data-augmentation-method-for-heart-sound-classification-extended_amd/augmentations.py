@@ -15,7 +15,13 @@ Implemented methods (the PCGmix hot path): ``durratiomixup`` (augmentations.py:9
 ``apply_plan`` with one kernel each (csrc/pcgmix_baselines.hip).  ``latentmixup[+p]`` (manifold
 mixup, augmentations.py:1472-1506; ``args.model`` 'Potes' or 'resnet9') runs ``model(data, depth,
 'first')`` and blends the features with the same-label partners' through the differentiable HIP
-blend (``LatentBlend``); it sets ``args.depth`` and returns the features.  ``gaussiannoise`` is not
+blend (``LatentBlend``); it sets ``args.depth`` and returns the features.  The heart-cycle
+cut-and-paste methods — ``durratiocutmix``, ``wav-durratiocutmix`` (augmentations.py:983-1000,
+1101-1119), ``labelcutmix``, ``lengthcutmix``, ``datasetcutmix``, ``wavcutmix`` (:1121-1213,
+1285-1316) with ``(rand)``, ``(smooth)`` and the ``cutout`` suffix — ``durmixrespscale`` (:734-775)
+and bare ``cutout`` / ``cutout(ch)`` (:1569-1616) are planned by ``hostprep.cutpaste_plan`` and run
+as one launch each (csrc/pcgmix_cutpaste.hip; cutout through ``pcgmix_zero_spans_f32``, in place).
+``gaussiannoise`` is not
 served: it draws from unseeded global streams through ``audiomentations``, so the reference defines
 no values to match.  The host part (RNG, partner indices) is in
 ``hostprep``; the O(B*C*T) part is ONE launch of ``pcgmix_mix_warp_f32`` (HIP, gfx950) on the
@@ -38,6 +44,7 @@ from .hostprep import MixPlan
 _OP_CACHE: dict = {}      # (device index, T, n_knots) -> device tensor with the spline operator
 _RECIPES: dict = {}       # method string -> plain recipe | None (general plan path) | False (passthrough)
                           # | _LATENT (1D latentmixup: the model's first half, blended)
+                          # | _CUTPASTE (hostprep.cutpaste_recipe: planned by cutpaste_plan)
 
 
 def _raw_stream(device: torch.device) -> int:
@@ -216,7 +223,10 @@ def apply_plan(plan: MixPlan, data: torch.Tensor, frames: np.ndarray,
                saliency_maps: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Run the device part of a fired plan; returns the new (B,C,T) tensor (``out`` if given:
-    a static buffer a captured hipGraph reads from)."""
+    a static buffer a captured hipGraph reads from).  Plans of ``hostprep.cutpaste_plan`` (1D) are
+    accepted as well; their in-place kind (``cutout``) then zeroes a copy of ``data`` in ``out``."""
+    if plan.family:
+        return _apply_cutpaste(plan, data, frames, out)
     if plan.kind != "splice":
         return _apply_baseline(plan, data, out)
     B, C, T = data.shape
@@ -321,6 +331,107 @@ def _apply_baseline(plan: MixPlan, data: torch.Tensor, out: Optional[torch.Tenso
         else:                                                   # pragma: no cover
             raise NotImplementedError(kind)
     return out
+
+
+_SIGMOID: dict = {}       # device index -> float64 (10, 20) device tensor: the '(smooth)' coefficient tables
+
+
+def _sigmoid_table(device: torch.device) -> torch.Tensor:
+    """The ten possible ``sigmoid(ov)`` tables of '(smooth)' (hostprep.sigmoid_table), uploaded once
+    per device."""
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    tab = _SIGMOID.get(key)
+    if tab is None:
+        tab = _SIGMOID[key] = torch.from_numpy(hostprep.sigmoid_table().copy()).to(device)
+    return tab
+
+
+def _apply_cutpaste(plan: MixPlan, data: torch.Tensor, frames: np.ndarray,
+                    out: Optional[torch.Tensor]) -> torch.Tensor:
+    """Device part of a ``hostprep.cutpaste_plan`` (csrc/pcgmix_cutpaste.hip): ONE launch on the
+    current stream.  ``cutpaste``: the segment table, the partners and the '(smooth)' junctions go
+    up in one copy, then ``pcgmix_cutpaste_rows_f32`` writes a new tensor.  ``mixscale``
+    (durmixrespscale): the splice's index block and the sinusoid row, then ``pcgmix_mix_scale_f32``.
+    ``cutout`` zeroes its spans IN PLACE in ``data`` (augmentations.py:1615) through
+    ``pcgmix_zero_spans_f32`` — or, with ``out``, in a copy of ``data`` there."""
+    kind = plan.kind
+    if kind == "cutout2d" or data.dim() != 3:
+        raise ValueError("a 2D cutout plan is applied by augmentations2d.augment")
+    B, C, T = data.shape
+    device = data.device
+    if out is not None and not _fresh_out_ok(out, data):
+        raise ValueError("out must be a distinct contiguous tensor shaped like data")
+    lib = _lib.load()
+    if kind == "cutout":
+        dst = data if out is None else out.copy_(data)
+        rows = plan.span_rows
+        if rows not in (1, C) or plan.spans.shape != (B * rows, 2):
+            raise ValueError("cutout: the spans do not match the batch")
+        if B:
+            with torch.cuda.device(device):
+                spans = upload_array(plan.spans, device)
+                _lib.check(lib.pcgmix_zero_spans_f32(dst.data_ptr(), spans.data_ptr(), B * rows, C // rows, T,
+                                                     ctypes.c_void_p(_raw_stream(device))),
+                           "pcgmix_zero_spans_f32")
+        return dst
+    if out is None:
+        out = torch.empty_like(data)
+    if B == 0:
+        return out
+    mix = np.asarray(plan.mix, dtype=np.int64)
+    if mix.shape != (B,) or int(mix.min()) < 0 or int(mix.max()) >= B:
+        raise ValueError(_PACK_ERRORS[3])
+    with torch.cuda.device(device):
+        stream = ctypes.c_void_p(_raw_stream(device))
+        if kind == "cutpaste":
+            if plan.segs.shape != (B, 5, 4):
+                raise ValueError("cutpaste: the segment table does not match the batch")
+            parts = [np.ascontiguousarray(plan.segs, dtype=np.int32).reshape(-1), mix.astype(np.int32)]
+            if plan.junctions is not None:
+                parts.append(np.ascontiguousarray(plan.junctions, dtype=np.int32).reshape(-1))
+            dev = upload_array(np.concatenate(parts), device)
+            base = dev.data_ptr()
+            junc_ptr = sig_ptr = None
+            if plan.junctions is not None:
+                junc_ptr = base + (B * 20 + B) * 4
+                sig_ptr = _sigmoid_table(device).data_ptr()
+            _lib.check(lib.pcgmix_cutpaste_rows_f32(data.data_ptr(), out.data_ptr(), base, base + B * 20 * 4,
+                                                    junc_ptr, sig_ptr, B, C, T, stream),
+                       "pcgmix_cutpaste_rows_f32")
+        elif kind == "mixscale":
+            if plan.scale_row.shape != (T,):
+                raise ValueError("durmixrespscale: the sinusoid row does not match the signal length")
+            dev, offs = upload_plan(plan, frames, device, T)
+            base = dev.data_ptr()
+            row = upload_array(plan.scale_row, device)
+            _lib.check(lib.pcgmix_mix_scale_f32(
+                data.data_ptr(), out.data_ptr(), base + offs["frames"], base + offs["mix"],
+                base + offs["off"] if offs["off"] is not None else None, _c_float(float(plan.lam32)),
+                row.data_ptr(), B, C, T, stream), "pcgmix_mix_scale_f32")
+        else:                                                   # pragma: no cover
+            raise NotImplementedError(kind)
+    return out
+
+
+def _augment_cutpaste(args, data: torch.Tensor, target_ohe, frames, wav, step: int, host_labels):
+    """One call of a cut-and-paste method, durmixrespscale or bare cutout (augmentations.py:734-775,
+    983-1000, 1101-1213, 1285-1316, 1569-1616) with the reference's return tuple: the keep-duration
+    methods return ``(new, targets, mix, None)``, the four cutmix branches ``(new, targets, mix,
+    cut)``, durmixrespscale ``(new, targets, [], None)`` and cutout ``(data itself, targets, [],
+    None)``."""
+    _check_data(data, 3)
+    B, C, T = data.shape
+    frames_np = _as_numpy_frames(frames)
+    labels = (lambda: labels_from_ohe(target_ohe)) if host_labels is None else np.asarray(host_labels)
+    plan = hostprep.cutpaste_plan(args.method, labels, frames_np, wav, step, B, C, T,
+                                  batch_size=getattr(args, "batch_size", None),
+                                  sample_rate=getattr(args, "sample_rate", None))
+    if not plan.fired:
+        return data, target_ohe, [], None
+    out = apply_plan(plan, data, frames_np)
+    if plan.kind == "cutpaste":
+        return out, target_ohe, plan.mix, plan.cut
+    return out, target_ohe, [], None
 
 
 def _augment_baseline(args, data: torch.Tensor, target_ohe, frames, wav, step: int, host_labels):
@@ -648,6 +759,7 @@ def latent_blend(h: torch.Tensor, mix: np.ndarray, lam32) -> torch.Tensor:
 
 
 _LATENT = "latentmixup"   # _RECIPES marker of a method string that reaches the 1D latentmixup branch
+_CUTPASTE = "cutpaste"    # ... that reaches a branch of hostprep.cutpaste_recipe
 
 
 def latent_partners(mix: np.ndarray, device: torch.device):
@@ -701,6 +813,10 @@ def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RE
         recipe = _RECIPES[method] = _LATENT
     if recipe is _LATENT:                         # latentmixup: the model's first half, blended
         return _augment_latent(args, data, target_ohe, step, model, host_labels)
+    if recipe is _RECIPES and hostprep.cutpaste_recipe(method, False) is not None:
+        recipe = _RECIPES[method] = _CUTPASTE
+    if recipe is _CUTPASTE:                       # cut-and-paste family, durmixrespscale, cutout
+        return _augment_cutpaste(args, data, target_ohe, frames, wav, step, host_labels)
     if recipe is _RECIPES:                        # first sight of this method string
         recipe = hostprep.plain_recipe(method, False) \
             if hostprep.select_method(method, is2d=False) is not None else False

@@ -30,8 +30,12 @@ call, with the reference's return values (csrc/pcgmix_baselines2d.hip):
     latentmixup[+p]            ``model(data, depth, 'first')`` blended with the same-label partners'
                                features through a differentiable HIP blend; sets ``args.depth``
 
-Bare ``cutout`` (the one 2D baseline not served) and a bare ``mixup`` that nothing behind it
-catches raise NotImplementedError from ``hostprep.select_method``.
+    cutout[(t,f)][+p]          durmixcutout's rectangle without the splice (augmentations2d.py:429-459):
+                               rows [h1, h2) x columns [int(u1*f[-1]), int(u2*f[-1])) of every
+                               channel zeroed IN PLACE; returns ``data`` itself, ``[]``, None
+
+A bare ``mixup`` that nothing behind it catches raises NotImplementedError from
+``hostprep.select_method``.
 """
 from __future__ import annotations
 
@@ -122,10 +126,25 @@ def _augment_baseline2d(args, data, target_ohe, frames, step: int, model, host_l
     raise NotImplementedError(kind)                                        # pragma: no cover
 
 
+def _augment_cutout2d(args, data, target_ohe, frames, step: int):
+    """Bare ``cutout[(t,f)]`` (augmentations2d.py:429-459): durmixcutout's rectangle without the
+    splice — no partners, no lambda, numpy's global stream untouched — zeroed IN PLACE in every
+    channel; returns ``data`` itself."""
+    _check_data(data, 4)
+    B, C, F, W = data.shape
+    plan = hostprep.cutpaste_plan(args.method, None, _as_numpy_frames(frames), None, step, B, C, W,
+                                  is2d=True, n_freq=F, n_cols=W)
+    if not plan.fired:
+        return data, target_ohe, [], None
+    return zero_rects_(data, plan.zero_rect), target_ohe, [], None
+
+
 def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RESULTS_ARGS,
             host_labels=None):
     method = args.method
     step = int(step_counter.count)
+    if hostprep.cutpaste_recipe(method, True) is not None:
+        return _augment_cutout2d(args, data, target_ohe, frames, step)
     name = hostprep.select_method(method, is2d=True)
     if name is None:
         return data, target_ohe, [], None

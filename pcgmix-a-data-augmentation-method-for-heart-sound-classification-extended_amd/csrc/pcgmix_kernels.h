@@ -155,6 +155,86 @@ __device__ __forceinline__ uint32_t onehot_argmax4(const int64_t* __restrict__ o
   return packed;
 }
 
+// ---- device code shared by the splice kernels (pcgmix_mix.hip, pcgmix_cutpaste.hip) -----------------
+// 16-byte vector whose address is only known to be 4-byte aligned (partner rows are read at
+// an arbitrary sample offset); gfx950 global loads handle the misalignment in hardware.
+typedef float float4_u __attribute__((ext_vector_type(4), aligned(4)));
+typedef float float4_a __attribute__((ext_vector_type(4), aligned(16)));
+
+struct StateMap {
+  int a[4];      // own-side start of the blended range of state k
+  int n[4];      // its length (0 = nothing to blend)
+  int delta[4];  // partner index = own index + delta
+};
+
+// Boundaries of sample b and its partner -> blended ranges.  All inputs are block-uniform.
+__device__ __forceinline__ StateMap make_state_map(const int32_t* __restrict__ frames,
+                                                   const int32_t* __restrict__ off, int b, int m,
+                                                   int T, const float2* __restrict__ part = nullptr) {
+  StateMap sm;
+  int f1[5], f2[5];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    f1[k] = frames[b * 5 + k];
+    f2[k] = frames[m * 5 + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    int len1 = f1[k + 1] - f1[k];
+    int len2 = f2[k + 1] - f2[k];
+    int gap = len2 - len1;
+    int agap = gap < 0 ? -gap : gap;
+    int o = off ? off[b * 4 + k] : 0;
+    if (part) {  // salopt_finalize_kernel's rule: greatest value, smallest displacement on ties
+      float bv = -INFINITY;
+      int bd = 0x7fffffff;
+#pragma unroll
+      for (int z = 0; z < kDispSplit; ++z) {
+        const float2 p = part[((size_t)b * 4 + k) * kDispSplit + z];
+        const int dd = __float_as_int(p.y);
+        if (p.x > bv || (p.x == bv && dd < bd)) {
+          bv = p.x;
+          bd = dd;
+        }
+      }
+      o = bd == 0x7fffffff ? 0 : bd;
+    }
+    o = o < 0 ? 0 : (o > agap ? agap : o);
+    int a = f1[k] + (gap < 0 ? o : 0);
+    int s = f2[k] + (gap > 0 ? o : 0);
+    int n = len1 < len2 ? len1 : len2;
+    // never blend outside the row on either side (malformed frames are rejected on the host;
+    // this keeps the kernel memory-safe regardless)
+    if (a < 0 || s < 0) n = 0;
+    if (n > T - a) n = T - a;
+    if (n > T - s) n = T - s;
+    if (n < 0) n = 0;
+    sm.a[k] = a;
+    sm.n[k] = n;
+    sm.delta[k] = s - a;
+  }
+  return sm;
+}
+
+// Returns the partner-minus-own index shift for sample position t, or INT_MIN if t is not
+// inside a blended range.
+__device__ __forceinline__ int blend_shift(const StateMap& sm, int t, bool& hit) {
+  int d = 0;
+  hit = false;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    bool in = (unsigned)(t - sm.a[k]) < (unsigned)sm.n[k];
+    d = in ? sm.delta[k] : d;
+    hit = hit || in;
+  }
+  return d;
+}
+
+__device__ __forceinline__ float blend(float own, float other, float lam, float oml) {
+  // x*lam + partner*(1-lam) as three separately rounded fp32 ops (augmentations.py:294)
+  return __fadd_rn(__fmul_rn(own, lam), __fmul_rn(other, oml));
+}
+
 // pcgmix_saliency.hip: the displacement search of pcgmix_salopt_disp_f32; disp == nullptr leaves
 // the per-block results in `workspace` for launch_mix_warp's disp_part.
 // pay_*: pay_n16 16-byte words that one otherwise idle block copies from pay_src (device-readable

@@ -17,6 +17,13 @@ latentmixup only, ``Random(step+131071)`` / ``Random(step+13119)`` for the mask 
 positions, ``Random(step*131071).randint(1, 3)`` for ``(rand)cutmix``'s cut and
 ``Random(step).randint(1, 3)`` for latentmixup's depth.
 
+The heart-cycle cut-and-paste family, ``durmixrespscale`` and bare ``cutout`` (augmentations.py:
+734-775, 983-1000, 1101-1213, 1285-1316, 1569-1616; augmentations2d.py:429-459) are planned by
+``cutpaste_recipe`` / ``cutpaste_plan``: the gate, partners by label / recording / data set /
+(label, length bin), ``Random(step).randint(1, 3)`` or ``Random(step*131071).randint(1, 3)`` for
+the cut, ``Random(step + i*131071)`` for the 'cutout' suffix; only ``durmixrespscale`` touches
+numpy's global stream (``get_lambda``).
+
 The result is a small ``MixPlan`` of index/scalar data that the device kernels consume; no
 waveform data is touched here.
 """
@@ -59,8 +66,9 @@ def _has(name):
     return lambda m: name in m
 
 
-# The reference's 1D if-chain up to the last branch served here, in its order (augmentations.py:734,
-# 777, 807, 829, 864, 931, 983, 1002, 1026); everything behind it is refused.
+# The reference's 1D if-chain up to the last branch select_method serves, in its order
+# (augmentations.py:734, 777, 807, 829, 864, 931, 983, 1002, 1026); select_method refuses everything
+# behind it (the whole chain: _FULL_CHAIN_1D, for cutpaste_recipe).
 _CHAIN_1D = (
     (_has("durmixrespscale"), "durmixrespscale"),
     (_has("respiratoryscale"), "respiratoryscale"),
@@ -73,7 +81,7 @@ _CHAIN_1D = (
     (_has("magnitudewarp"), "magnitudewarp"),
 )
 # The reference's 2D if-chain, in its order (augmentations2d.py:286, 325, 361, 397, 429, 461, 487, 510,
-# 538, 574, 599).  'cutout' is the one branch not served here.
+# 538, 574, 599).  'cutout' is served through cutpaste_recipe / cutpaste_plan, not through select_method.
 _CHAIN_2D = (
     (_has("durmixcutout"), "durmixcutout"),
     (_has("durmixtimemask"), "durmixtimemask"),
@@ -113,12 +121,20 @@ class MixPlan:
     segs: Optional[np.ndarray] = None          # int32 (B,5,4) {lo,hi,src,shift}: cutmix / durratiocutmix
     seg_axis: int = 0                          # 0: segments along the columns, 1: along F ('(rand)')
     out_cols: int = 0                          # width of the new tensor (cutmix: F, augmentations2d.py:589)
+    family: str = ""                           # cutpaste_plan: "cutpaste" | "mixscale" | "cutout" | "cutout2d"
+    junctions: Optional[np.ndarray] = None     # int32 (B,4) {c1, c2, ov, 0}: the '(smooth)' cross-fade
+    span_rows: int = 0                         # cutout: rows per sample that carry a span of their own
+                                               # (1, or C for '(ch)': spans is then (B*C, 2))
 
     @property
     def kind(self) -> str:
         """"splice" (durratiomixup / durmixmagwarp and the 2D mask variants), the 1D baseline's
-        name, or the 2D baseline's name with a "2d" suffix ("timemask2d", "cutmix2d", ...): a 2D
-        timemask is a rectangle per channel, never the 1D span path."""
+        name, the 2D baseline's name with a "2d" suffix ("timemask2d", "cutmix2d", ...): a 2D
+        timemask is a rectangle per channel, never the 1D span path — or, for a ``cutpaste_plan``,
+        its family: "cutpaste" (segment table + junction), "mixscale" (durmixrespscale: splice x
+        row), "cutout" (1D spans, in place), "cutout2d" (rectangles, in place)."""
+        if self.family:
+            return self.family
         if self.is2d:
             return self.name + "2d" if self.name in BASELINE_METHODS_2D else "splice"
         return self.name if self.name in BASELINE_METHODS_1D else "splice"
@@ -127,7 +143,8 @@ class MixPlan:
 def _branch_2d(method: str) -> str:
     """The reference's 2D if-chain (augmentations2d.py:286-617), as ``_branch_1d``: a bare ``mixup``
     (no '(same)', no '(mix)', :547-572) falls through to the later branches; "" when the branch
-    reached is not implemented here ('cutout') or none is (the reference returns None)."""
+    reached is not one select_method serves ('cutout': see cutpaste_recipe) or none is (the reference
+    returns None)."""
     for cond, name in _CHAIN_2D:
         if not cond(method):
             continue
@@ -163,8 +180,10 @@ def select_method(method: str, is2d: bool) -> Optional[str]:
     hit = (_branch_2d(method) if is2d else _branch_1d(method)) or None
     if hit is None:
         raise NotImplementedError(
-            f"method {method!r} selects a reference augmentation outside the PCGmix hot path; "
-            f"this package implements {ours} only")
+            f"method {method!r} selects no augmentation that select_method() serves {ours}; the "
+            f"cut-and-paste family, durmixrespscale, cutout and latentmixup are answered by "
+            f"cutpaste_recipe() / latent_recipe(), which augment() asks first; the reference's "
+            f"2-tuple branches, manifold-*, (UMC-subset), (sameCVD) and gaussiannoise are not served")
     for sel in _UNSUPPORTED_SELECTORS:
         if sel in method and not is2d and hit in SPLICE_METHODS_1D:
             raise NotImplementedError(f"partner selector {sel!r} is out of scope (SURVEY.md §2)")
@@ -251,11 +270,7 @@ def respiration_row(method: str, step: int, sig_len: int, sample_rate) -> np.nda
     it: the gate's own ``u = Random(step).random()`` gives rate = min + (max-min)*u and phase =
     2*pi*u (``Random(step).uniform`` twice on fresh generators)."""
     lo, hi = parse_respscale(method)
-    u = _lib.load().pcgmix_py_uniform01(int(step))
-    rate = lo + (hi - lo) * u
-    phase = 0 + (2 * np.pi - 0) * u
-    t = np.linspace(0, sig_len / sample_rate, sig_len)
-    return np.sin(2 * np.pi * rate * t + phase)
+    return _respiration_row(lo, hi, step, sig_len, sample_rate)
 
 
 @functools.lru_cache(maxsize=256)
@@ -777,6 +792,263 @@ def rand_keepdur_segments(frames: np.ndarray, mix: np.ndarray, off: np.ndarray, 
     return _segment_table((zero, a0, a1, b0, b1, np.full_like(a0, F)),
                           (_OWN, _PARTNER, _OWN, _PARTNER, _OWN),
                           (zero, sa, zero, sb, zero))
+
+
+# ---- the cut-and-paste family, durmixrespscale and bare cutout --------------------------------------
+# Names planned by ``cutpaste_plan`` (1D: augmentations.py:734, 983, 1101, 1121, 1153, 1184, 1285,
+# 1569; 2D: augmentations2d.py:429).
+CUTPASTE_METHODS_1D = ("durmixrespscale", "wav-durratiocutmix", "durratiocutmix", "lengthcutmix",
+                       "datasetcutmix", "wavcutmix", "labelcutmix", "cutout")
+CUTPASTE_METHODS_2D = ("cutout",)
+_KEEPDUR_1D = ("wav-durratiocutmix", "durratiocutmix")
+_CUTMIX_1D = ("lengthcutmix", "datasetcutmix", "wavcutmix", "labelcutmix")
+CUTPASTE_MAX_OVERLAP = 10          # PCGMIX_CUTPASTE_MAX_OVERLAP: cutmix_multidim_tensors' overlap=10
+
+# The reference's WHOLE 1D if-chain, in its order (augmentations.py:734 ... 1616); ``None`` marks a
+# branch that is somebody else's (served through select_method / latent_recipe, or refused).
+_FULL_CHAIN_1D = (
+    (_has("durmixrespscale"), "durmixrespscale"),                                        # :734
+    (_has("respiratoryscale"), None), (_has("timemask"), None),                          # :777, :807
+    (lambda m: "mixup" in m and "latentmixup" not in m and "durratiomixup" not in m, "mixup"),  # :829
+    (_has("durmixmagwarp"), None), (_has("durratiomixup"), None),                        # :864, :931
+    (_has("wav-durratiocutmix"), "wav-durratiocutmix"),                                  # :983
+    (_has("timewarp"), None), (_has("magnitudewarp"), None), (_has("gaussiannoise"), None),
+    (lambda m: "(UMC-subset)durratiocutmix" in m and "(plus)" not in m and "(plusplus)" not in m, None),
+    (lambda m: "durratiocutmix" in m and "(plus)" not in m and "(plusplus)" not in m
+     and "(UMC" not in m and "wav-durratiocutmix" not in m, "durratiocutmix"),           # :1101
+    (_has("lengthcutmix"), "lengthcutmix"), (_has("datasetcutmix"), "datasetcutmix"),    # :1121, :1153
+    (lambda m: "wavcutmix" in m and "durratiowavcutmix" not in m, "wavcutmix"),          # :1184
+    (_has("lc-nointrusion"), None),                                                      # :1215
+    (_has("labelcutmix"), "labelcutmix"),                                                # :1285
+    (_has("swapsysdia"), None), (_has("cont-cutmix"), None), (_has("saliency-cutmix"), None),
+    (_has("latentmixup"), None),                                                         # :1472
+    (lambda m: "cutmix" in m and "saliency" not in m and "label" not in m, None),        # :1508
+    (lambda m: "cutout" in m and "saliency" not in m, "cutout"),                         # :1569
+)
+
+
+@functools.lru_cache(maxsize=256)
+def cutpaste_recipe(method: str, is2d: bool = False) -> Optional[str]:
+    """The branch name when the reference's if-chain reaches, for ``method``, one of the branches
+    ``cutpaste_plan`` serves — the heart-cycle cut-and-paste methods, ``durmixrespscale`` and bare
+    ``cutout`` in 1D (``CUTPASTE_METHODS_1D``), bare ``cutout`` in 2D — and None otherwise (an
+    earlier branch takes the string, or a later one, or none).  ``select_method`` keeps refusing
+    these names; ``augment()`` asks here first, as it does with ``latent_recipe``."""
+    if is2d:
+        if not any(n in method for n in _REFERENCE_METHODS_2D):
+            return None
+        for cond, name in _CHAIN_2D:
+            if cond(method):
+                return "cutout" if name == "cutout" else None
+        return None
+    if not any(n in method for n in _REFERENCE_METHODS_1D):
+        return None                                            # augmentations.py:731-732
+    for cond, name in _FULL_CHAIN_1D:
+        if not cond(method):
+            continue
+        if name == "mixup":                                    # falls through without a selector
+            if "(same)" in method or "(mix)" in method:
+                return None
+            continue
+        if name == "cutout" and "manifold" in method:          # needs max_depth: bound for FCN only
+            return None
+        return name
+    return None
+
+
+@functools.lru_cache(maxsize=256)
+def parse_durmixrespscale(method: str):
+    """'durmixrespscale(min,max)' -> (min, max) in Hz (augmentations.py:760-764): as
+    ``parse_respscale``, split on the branch's own name."""
+    lo, hi = 12 / 60, 20 / 60
+    parts = method.split("durmixrespscale(")
+    if len(parts) > 1:
+        lo = float(parts[1].split(",")[0]) / 60
+        hi = int(method.split(",")[1].split(")")[0]) / 60
+    return lo, hi
+
+
+def _respiration_row(lo: float, hi: float, step: int, sig_len: int, sample_rate) -> np.ndarray:
+    u = _lib.load().pcgmix_py_uniform01(int(step))
+    rate = lo + (hi - lo) * u
+    phase = 0 + (2 * np.pi - 0) * u
+    t = np.linspace(0, sig_len / sample_rate, sig_len)
+    return np.sin(2 * np.pi * rate * t + phase)
+
+
+@functools.lru_cache(maxsize=16)
+def sigmoid_table() -> np.ndarray:
+    """float64 (10, 20): row ov-1 holds the reference's ``sigmoid(ov)`` (augmentations.py:668-672) in
+    its first 2*ov entries, computed with numpy as the reference computes it."""
+    tab = np.zeros((CUTPASTE_MAX_OVERLAP, 2 * CUTPASTE_MAX_OVERLAP), dtype=np.float64)
+    for ov in range(1, CUTPASTE_MAX_OVERLAP + 1):
+        row = np.array([1.0 / (1.0 + np.exp(-x)) for x in np.linspace(-8, 8, ov * 2)])
+        row[0] = 0
+        row[-1] = 1
+        tab[ov - 1, :2 * ov] = row
+    tab.setflags(write=False)
+    return tab
+
+
+def length_bin_keys(method: str, labels: np.ndarray, frames: np.ndarray, batch_size: int) -> np.ndarray:
+    """get_same_length_mix_indices' grouping key (augmentations.py:558-575): (label, length bin) with
+    ``num_bins = batch_size//100`` ('(5bins)', '(10bins)'), the bins through numpy itself."""
+    lengths = [int(v) for v in frames[:, -1]]
+    num_bins = int(batch_size) // 100
+    if "(5bins)" in method:
+        num_bins = 5
+    if "(10bins)" in method:
+        num_bins = 10
+    bins = np.linspace(np.min(lengths) - 1, np.max(lengths) + 1, num_bins + 1)
+    bins_inds = np.digitize(lengths, bins).astype(np.int64)
+    return labels.astype(np.int64) * (int(bins_inds.max()) + 1) + bins_inds
+
+
+def cutout_spans(frames: np.ndarray, step: int, sig_len: int, channels: int, per_channel: bool) -> np.ndarray:
+    """Bare 1D cutout (augmentations.py:1594-1615): int32 (B, 2), or (B*C, 2) for '(ch)'.  The
+    parameters in the method string are ignored, as the reference ignores them."""
+    beat = np.asarray(frames)[:, -1].astype(np.float64)
+    if per_channel:
+        fr = np.array([sorted(random.Random(step + i * 131071 + c * 524287).uniform(0, 1) for i in range(2))
+                       for c in range(channels)])                              # (C, 2)
+        spans = (fr[None, :, :] * beat[:, None, None]).astype(np.int64).reshape(-1, 2)
+    else:
+        gap = random.Random(step + 131071).uniform(0, 0.05)
+        frac1 = random.Random(step + 13119).uniform(0, 1 - gap)
+        frac2 = frac1 + gap
+        spans = np.stack([(frac1 * beat).astype(np.int64), (frac2 * beat).astype(np.int64)], axis=1)
+    return np.clip(spans, 0, sig_len).astype(np.int32)
+
+
+def cutmix_cutout_segments(frames: np.ndarray, mix: np.ndarray, cut: int, T: int, cut_frac) -> np.ndarray:
+    """``cutmix_segments`` with the 'cutout' suffix of the four 1D cutmix branches (e.g. :1143-1148):
+    ``[int(cf0*last), int(cf1*last))`` zeroed after the paste, ``last`` = the new cycle's end."""
+    f2 = frames[mix]
+    a = frames[:, cut]
+    last = np.minimum(a + f2[:, 4] - f2[:, cut], T)
+    z0 = (cut_frac[0] * last.astype(np.float64)).astype(np.int64)              # int() truncation
+    z1 = (cut_frac[1] * last.astype(np.float64)).astype(np.int64)
+    pts = np.sort(np.stack([np.zeros_like(a), a, z0, z1, last], axis=1), axis=1)
+    B = a.shape[0]
+    segs = np.zeros((B, 5, 4), dtype=np.int32)
+    for k in range(5):
+        lo = pts[:, k]
+        hi = pts[:, k + 1] if k < 4 else np.full_like(a, T)
+        zero = ((lo >= z0) & (lo < z1)) | (lo >= last)
+        partner = ~zero & (lo >= a)
+        segs[:, k, 0] = lo
+        segs[:, k, 1] = hi
+        segs[:, k, 2] = np.where(zero, _ZERO, np.where(partner, _PARTNER, _OWN))
+        segs[:, k, 3] = np.where(partner, f2[:, cut] - a, 0)
+    return segs
+
+
+def smooth_junctions(frames: np.ndarray, mix: np.ndarray, cut: int) -> np.ndarray:
+    """'(smooth)' (augmentations.py:41-51): int32 (B, 4) {f1[cut], f2[cut], ov, 0} with ``ov = min(10,
+    f1[cut], f2[4]-f2[cut], f1[4]-f1[cut], f2[cut])``.  ``ov == 0`` makes the reference index an empty
+    array inside ``sigmoid``: IndexError, raised here before anything is launched."""
+    f2 = frames[mix]
+    a, c2 = frames[:, cut], f2[:, cut]
+    ov = np.minimum.reduce([np.full_like(a, CUTPASTE_MAX_OVERLAP), a, f2[:, 4] - c2, frames[:, 4] - a, c2])
+    if (ov <= 0).any():
+        raise IndexError("(smooth): a part next to the junction is empty (overlap 0); the reference "
+                         "raises IndexError in sigmoid(0)")
+    return np.stack([a, c2, ov, np.zeros_like(a)], axis=1).astype(np.int32)
+
+
+def _validate_cycles(frames: np.ndarray, sig_len: int) -> None:
+    validate_frames(frames, sig_len)
+    if frames.size and (frames[:, 0] != 0).any():
+        raise ValueError("frames[:, 0] must be 0 (a heart cycle starts at its first sample)")
+
+
+def cutpaste_plan(method: str, labels, frames: np.ndarray, wav: Optional[Sequence[str]], step: int,
+                  batch: int, channels: int, sig_len: int, is2d: bool = False,
+                  batch_size: Optional[int] = None, sample_rate=None, n_freq: Optional[int] = None,
+                  n_cols: int = 0) -> MixPlan:
+    """Host part of one step of a ``cutpaste_recipe`` method, in the reference's RNG order: gate,
+    partners, cut, 'cutout' fractions; for durmixrespscale gate, partners, ``get_lambda`` (numpy's
+    global stream, only when the gate fires), '(rand)' offsets, the sinusoid.  ``labels``: array or
+    zero-argument callable (asked after the gate).  1D: ``sig_len`` = T; ``batch_size`` =
+    ``args.batch_size`` (lengthcutmix), ``sample_rate`` = ``args.sample_rate`` (durmixrespscale).
+    2D: ``n_freq`` = F, ``n_cols`` = W."""
+    name = cutpaste_recipe(method, is2d)
+    if name is None:
+        raise ValueError(f"{method!r} reaches none of the branches cutpaste_plan serves")
+    if not gate_fires(method, step):
+        return MixPlan(fired=False, step=step)
+    frames = np.asarray(frames)
+    if frames.ndim != 2 or frames.shape != (batch, 5):
+        raise ValueError("labels/frames do not match the batch size")
+    plan = MixPlan(fired=True, name=name, step=step, is2d=is2d)
+    if is2d:                                                   # augmentations2d.py:429-459
+        if n_freq is None or n_cols <= 0:
+            raise ValueError("2D cutout needs cutpaste_plan(..., n_freq=F, n_cols=W)")
+        rect = mask_rectangles(method, "durmixcutout", frames, step, int(n_freq), int(n_cols))
+        rect[:, 2:] = np.clip(rect[:, 2:], 0, int(n_cols))     # the reference's slice clips
+        plan.zero_rect, plan.family = rect, "cutout2d"
+        return plan
+    if name == "cutout":                                       # :1569-1616
+        per_ch = "(ch)" in method
+        plan.spans = cutout_spans(frames, step, sig_len, channels, per_ch)
+        plan.span_rows = channels if per_ch else 1
+        plan.family = "cutout"
+        return plan
+    _validate_cycles(frames, sig_len)
+    f1 = frames.astype(np.int64, copy=False)
+    lab = lambda: _host_labels(labels, batch).astype(np.int64, copy=False)   # noqa: E731
+    if name == "durmixrespscale":                              # :734-775
+        if "(sameCVD)" in method:
+            raise NotImplementedError("partner selector '(sameCVD)' needs the reference's private CVD table")
+        if sample_rate is None:
+            raise ValueError("durmixrespscale needs cutpaste_plan(..., sample_rate=)")
+        plan.mix = shuffle_within_groups(lab(), step)
+        plan.lam64, _ = draw_lambda_knots(step, 1.0, 0.0, 0)   # get_lambda(alpha=1)
+        plan.lam32 = np.float32(plan.lam64)
+        if "(rand)" in method:
+            plan.rand_off = rand_offsets(f1, plan.mix, step)
+        lo, hi = parse_durmixrespscale(method)
+        plan.scale_row = _respiration_row(lo, hi, step, int(sig_len), sample_rate)
+        plan.family = "mixscale"
+        return plan
+    plan.family = "cutpaste"
+    if wav is None and name in ("wav-durratiocutmix", "wavcutmix", "datasetcutmix"):
+        raise ValueError(f"{name} groups the batch by recording: it needs wav")
+    if name in ("wav-durratiocutmix", "wavcutmix"):            # get_same_wav_mix_indices, :528
+        if len(wav) != batch:
+            raise ValueError("wav does not match the batch size")
+        plan.mix = shuffle_within_groups(list(wav), step)
+    elif name == "datasetcutmix":                              # get_same_dataset_mix_indices, :542
+        if len(wav) != batch:
+            raise ValueError("wav does not match the batch size")
+        plan.mix = shuffle_within_groups([f"{w[0]}_{int(t)}" for w, t in zip(wav, lab())], step)
+    elif name == "lengthcutmix":                               # get_same_length_mix_indices, :558
+        if batch_size is None:
+            raise ValueError("lengthcutmix needs args.batch_size (cutpaste_plan(..., batch_size=))")
+        plan.mix = shuffle_within_groups(length_bin_keys(method, lab(), f1, batch_size), step) \
+            if batch else np.zeros(0, np.int64)
+    else:                                                      # get_same_label_mix_indices
+        plan.mix = shuffle_within_groups(lab(), step)
+    if name in _KEEPDUR_1D:                                    # cutmix_keepdur_multidim_tensors, :340
+        if "(rand)" in method:
+            plan.segs = rand_keepdur_segments(f1, plan.mix, rand_offsets(f1, plan.mix, step, (1, 3)),
+                                              sig_len)
+        else:
+            plan.segs = keepdur_segments(f1, plan.mix, sig_len)
+        return plan
+    lib = _lib.load()
+    plan.cut = 2                                               # cutmix_multidim_tensors, :30
+    if "(rand)" in method:                                     # :1139 / :1303
+        seed = int(step) * 131071 if name == "labelcutmix" else int(step)
+        plan.cut = 1 + int(lib.pcgmix_py_randint0(seed, 2))
+    if "cutout" in method:
+        cut_frac = sorted(random.Random(step + i * 131071).uniform(0, 1) for i in range(2))
+        plan.segs = cutmix_cutout_segments(f1, plan.mix, plan.cut, sig_len, cut_frac)
+    else:
+        plan.segs = cutmix_segments(f1, plan.mix, plan.cut, sig_len)
+    if "(smooth)" in method:
+        plan.junctions = smooth_junctions(f1, plan.mix, plan.cut)
+    return plan
 
 
 def _gpu_numa_node(torch, index):

@@ -463,6 +463,19 @@ def latent_method(args) -> bool:
         and augmentations.hostprep.latent_recipe(args.method) is not None
 
 
+def cutpaste_method(args) -> bool:
+    """True when ``args.method`` reaches a branch of ``hostprep.cutpaste_recipe`` — the cut-and-paste
+    family, durmixrespscale, bare cutout: eager ``train_step`` only."""
+    return augmentations.hostprep.cutpaste_recipe(
+        args.method, args.dataset in SPECTROGRAM_DATASETS) is not None
+
+
+def cutpaste_graph_message(args) -> str:
+    return (f"method {args.method!r} ({augmentations.hostprep.cutpaste_recipe(args.method, False)}) is not "
+            f"wired into the captured step: its per-step segment tables have no slot in the graph's "
+            f"static block; use train_step")
+
+
 def latent_fused_model(args, model, criterion, data, target_ohe, epoch):
     """The CNN_potes that runs a 1D ``latentmixup`` step inside its fused head (the blend happens in
     the tail kernel, ``CNN_potes.loss_and_logits(..., latent=...)``), or None when the step takes
@@ -573,6 +586,8 @@ class GraphedTrainStep:
             raise NotImplementedError("graphed step is wired for the 1D path")
         if latent_method(args):
             raise NotImplementedError(LATENT_GRAPH_MESSAGE)
+        if cutpaste_method(args):
+            raise NotImplementedError(cutpaste_graph_message(args))
         self.args, self.model, self.opt, self.sched = args, model, optimizer, scheduler
         self.ce = criterion.CEloss if hasattr(criterion, "CEloss") else criterion
         self.es = getattr(criterion, "es", None)
@@ -1019,6 +1034,8 @@ def _epoch_graphed_step(args, model, optimizer, scheduler, criterion, device, ep
         return None
     if latent_method(args):                 # per-step partners and lambda: not captured (train_step)
         return None
+    if cutpaste_method(args):               # per-step segment tables: not captured (train_step)
+        return None
     if not isinstance(model, (models.CNN_potes, models.ResNet9_myrtle)):
         return None
     if epoch > criterion.es or getattr(args, "num_epochs", epoch) > criterion.es:
@@ -1238,7 +1255,7 @@ def train_model(args, dataset, device, use_graph: bool = True, log=print, pipeli
     criterion = SELCLoss(train_labels, args.num_classes, es=selc_turning_point(args), device=device)
     # (the spectrogram step is 80 ms of MIOpen convolutions: nothing for a graph to win, it stays eager)
     graphable = use_graph and device.type == "cuda" and args.num_epochs <= criterion.es and not spectro \
-        and not latent_method(args)         # latentmixup: eager step (not wired into the capture)
+        and not latent_method(args) and not cutpaste_method(args)   # eager step (not wired into the capture)
     if not graphable:
         model = wrap_distributed(model, device)
     optimizer, scheduler = make_optimizer(args, model)
