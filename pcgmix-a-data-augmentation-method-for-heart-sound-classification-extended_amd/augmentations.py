@@ -1,4 +1,4 @@
-"""Drop-in replacement for the PCGmix branches of the reference's ``augmentations.augment``.
+"""Drop-in replacement for the reference's ``augmentations.augment``.
 
 Same name, same positional signature, same return tuple as augmentations.py:698 (called once
 per batch from train_model.py:507):
@@ -6,26 +6,32 @@ per batch from train_model.py:507):
     data, target_ohe, mix_indices, cut = augment(args, data, target_ohe, frames, wav,
                                                  step_counter, model, device, RESULTS_ARGS)
 
-Implemented methods (the PCGmix hot path): ``durratiomixup`` (augmentations.py:931-981) and
-``durmixmagwarp(sigma,knot)`` (augmentations.py:864-929) with the selectors ``(rand)``,
-``(alpha=a)``, ``(samePCG)``, ``(sameDataset)``, ``(mixAll)``, ``(saloptenv…)``,
-``(saloptsum…)`` and the ``+p`` probability gate.  The paper's 1D comparison baselines
-``mixup(same)``, ``mixup(mix)``, ``magnitudewarp``, ``timewarp``, ``timemask`` and
-``respiratoryscale`` (augmentations.py:777-862, 1002-1048) run through ``make_plan`` /
-``apply_plan`` with one kernel each (csrc/pcgmix_baselines.hip).  ``latentmixup[+p]`` (manifold
-mixup, augmentations.py:1472-1506; ``args.model`` 'Potes' or 'resnet9') runs ``model(data, depth,
-'first')`` and blends the features with the same-label partners' through the differentiable HIP
-blend (``LatentBlend``); it sets ``args.depth`` and returns the features.  The heart-cycle
-cut-and-paste methods — ``durratiocutmix``, ``wav-durratiocutmix`` (augmentations.py:983-1000,
-1101-1119), ``labelcutmix``, ``lengthcutmix``, ``datasetcutmix``, ``wavcutmix`` (:1121-1213,
-1285-1316) with ``(rand)``, ``(smooth)`` and the ``cutout`` suffix — ``durmixrespscale`` (:734-775)
-and bare ``cutout`` / ``cutout(ch)`` (:1569-1616) are planned by ``hostprep.cutpaste_plan`` and run
-as one launch each (csrc/pcgmix_cutpaste.hip; cutout through ``pcgmix_zero_spans_f32``, in place).
-``gaussiannoise`` is not
-served: it draws from unseeded global streams through ``audiomentations``, so the reference defines
-no values to match.  The host part (RNG, partner indices) is in
-``hostprep``; the O(B*C*T) part is ONE launch of ``pcgmix_mix_warp_f32`` (HIP, gfx950) on the
-current torch stream, with no host synchronisation after the labels have been read.
+``augment()`` is a dispatch: one cached ``hostprep.route(args.method, False)`` lookup, then one
+branch on the route's family.
+
+splice     ``durratiomixup`` (augmentations.py:931-981) and ``durmixmagwarp(sigma,knot)`` (:864-929)
+           with the selectors ``(rand)``, ``(alpha=a)``, ``(samePCG)``, ``(sameDataset)``,
+           ``(mixAll)``, ``(saloptenv…)``, ``(saloptsum…)`` and the ``+p`` probability gate.  The
+           host part (RNG, partner indices) is in ``hostprep``; the O(B*C*T) part is ONE launch of
+           ``pcgmix_mix_warp_f32`` (HIP, gfx950) on the current torch stream, with no host
+           synchronisation after the labels have been read.  A plain splice (``Route.plain``) is one
+           library call (``splice_plain``).
+baseline   the paper's 1D comparison baselines ``mixup(same)``, ``mixup(mix)``, ``magnitudewarp``,
+           ``timewarp``, ``timemask`` and ``respiratoryscale`` (:777-862, 1002-1048) through
+           ``make_plan`` / ``apply_plan`` with one kernel each (csrc/pcgmix_baselines.hip).
+cutpaste   the heart-cycle cut-and-paste methods — ``durratiocutmix``, ``wav-durratiocutmix``
+           (:983-1000, 1101-1119), ``labelcutmix``, ``lengthcutmix``, ``datasetcutmix``, ``wavcutmix``
+           (:1121-1213, 1285-1316) with ``(rand)``, ``(smooth)`` and the ``cutout`` suffix —
+           ``durmixrespscale`` (:734-775) and bare ``cutout`` / ``cutout(ch)`` (:1569-1616), planned
+           by ``hostprep.cutpaste_plan`` and run as one launch each (csrc/pcgmix_cutpaste.hip; cutout
+           through ``pcgmix_zero_spans_f32``, in place).
+latent     ``latentmixup[+p]`` (manifold mixup, :1472-1506; ``args.model`` 'Potes' or 'resnet9') runs
+           ``model(data, depth, 'first')`` and blends the features with the same-label partners'
+           through the differentiable HIP blend (``LatentBlend``); it sets ``args.depth`` and returns
+           the features.
+refused    every other branch of the reference raises NotImplementedError.  ``gaussiannoise`` is
+           among them: it draws from unseeded global streams through ``audiomentations``, so the
+           reference defines no values to match.
 
 The split form ``make_plan`` / ``apply_plan`` lets a training loop that already holds the
 labels on the host prepare step n+1 while the GPU still runs step n.
@@ -41,20 +47,43 @@ import torch
 from . import _lib, hostprep
 from .hostprep import MixPlan
 
+# Module state: caches keyed by device index (never freed) and constants of the C ABI.
 _OP_CACHE: dict = {}      # (device index, T, n_knots) -> device tensor with the spline operator
-_RECIPES: dict = {}       # method string -> plain recipe | None (general plan path) | False (passthrough)
-                          # | _LATENT (1D latentmixup: the model's first half, blended)
-                          # | _CUTPASTE (hostprep.cutpaste_recipe: planned by cutpaste_plan)
+_RINGS: dict = {}         # device index -> _StagingRing
+_CTX: dict = {}           # device index -> pcgmix_ctx* (per-device step context)
+_SIGMOID: dict = {}       # device index -> float64 (10, 20) device tensor: the '(smooth)' coefficient tables
+_LABEL_PINNED: dict = {}  # (device index, dtype) -> pinned buffer of labels_from_ohe
+_SIDE_STREAMS: dict = {}  # device index -> the stream labels_from_ohe(after=) copies on
+_I64_ARRAYS: dict = {}    # n -> ctypes.c_int64 * n
+_BLIT_LIMIT = 16384       # hipMemcpyAsync uses a blit kernel up to here, the SDMA engine above
+_NOT_ARMED = -3           # PCGMIX_NOT_ARMED (include/pcgmix_hip.h)
+_PACK_ERRORS = {1: "frames must be non-decreasing and non-negative",
+                2: "heart cycle ends beyond the signal length",
+                3: "partner index out of range"}
+_SPLICE_ERRORS = {-1: _PACK_ERRORS[1], -2: _PACK_ERRORS[2], -3: _PACK_ERRORS[3]}
+_c_float = ctypes.c_float
+# hipStream_t of torch's current stream on a device index: the private getter where this torch build
+# has it (no Stream object: 0.07 us), the public one otherwise; resolved once, here
+_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None) \
+    or (lambda index: torch.cuda.current_stream(index).cuda_stream)       # pragma: no cover
 
 
 def _raw_stream(device: torch.device) -> int:
-    """hipStream_t of torch's current stream on ``device`` (the cheap private getter when this
-    torch build has it, the public Stream object otherwise)."""
-    idx = device.index if device.index is not None else torch.cuda.current_device()
-    try:
-        return torch._C._cuda_getCurrentRawStream(idx)
-    except AttributeError:      # pragma: no cover
-        return torch.cuda.current_stream(device).cuda_stream
+    """``_get_raw_stream`` for a ``torch.device`` (which may carry no index)."""
+    return _get_raw_stream(device.index if device.index is not None else torch.cuda.current_device())
+
+
+def _check_out(out: torch.Tensor, data: torch.Tensor) -> None:
+    if out.shape != data.shape or out.dtype != data.dtype or not out.is_contiguous() \
+            or out.data_ptr() == data.data_ptr():
+        raise ValueError("out must be a distinct contiguous tensor shaped like data")
+
+
+def _check_splice(err: int, what: str) -> None:
+    """A non-zero status of a splice entry point: negative = malformed frames or partners."""
+    if err < 0:
+        raise ValueError(_SPLICE_ERRORS.get(err, f"{what} error {err}"))
+    _lib.check(err, what)
 
 
 def _as_numpy_frames(frames) -> np.ndarray:
@@ -123,10 +152,6 @@ class _StagingRing:
         ev.record(stream)
 
 
-_RINGS: dict = {}
-_BLIT_LIMIT = 16384       # hipMemcpyAsync uses a blit kernel up to here, the SDMA engine above
-
-
 def _h2d(dev: torch.Tensor, pinned: torch.Tensor, nbytes: int) -> None:
     """Async copy of the first ``nbytes`` of a pinned staging buffer into the uint8 device tensor
     ``dev`` on the current stream.  Above 16 KB the copy is one launch of the library's fetch
@@ -167,11 +192,6 @@ def upload_into(dst: torch.Tensor, arr: np.ndarray) -> None:
     pinned.numpy()[:nbytes] = arr.reshape(-1).view(np.uint8)
     dst.view(torch.uint8).view(-1).copy_(pinned[:nbytes], non_blocking=True)
     ring.sent(slot, torch.cuda.current_stream(dst.device))
-
-
-_PACK_ERRORS = {1: "frames must be non-decreasing and non-negative",
-                2: "heart cycle ends beyond the signal length",
-                3: "partner index out of range"}
 
 
 def upload_plan(plan: MixPlan, frames: np.ndarray, device: torch.device, sig_len: int = 2**31 - 1):
@@ -225,7 +245,7 @@ def apply_plan(plan: MixPlan, data: torch.Tensor, frames: np.ndarray,
     """Run the device part of a fired plan; returns the new (B,C,T) tensor (``out`` if given:
     a static buffer a captured hipGraph reads from).  Plans of ``hostprep.cutpaste_plan`` (1D) are
     accepted as well; their in-place kind (``cutout``) then zeroes a copy of ``data`` in ``out``."""
-    if plan.family:
+    if plan.kind in hostprep.CUTPASTE_KINDS:
         return _apply_cutpaste(plan, data, frames, out)
     if plan.kind != "splice":
         return _apply_baseline(plan, data, out)
@@ -248,9 +268,8 @@ def apply_plan(plan: MixPlan, data: torch.Tensor, frames: np.ndarray,
             knots_ptr, op_ptr = base + offs["knots"], op.data_ptr()
         if out is None:
             out = torch.empty_like(data)
-        elif out.shape != data.shape or out.dtype != data.dtype or not out.is_contiguous() \
-                or out.data_ptr() == data.data_ptr():
-            raise ValueError("out must be a distinct contiguous tensor shaped like data")
+        else:
+            _check_out(out, data)
         rect_ptr = base + offs["rect"] if offs["rect"] is not None else None
         if plan.salopt_mode is not None:
             # displacement search + splice in one call: the splice kernel reduces the search's
@@ -284,8 +303,8 @@ def _apply_baseline(plan: MixPlan, data: torch.Tensor, out: Optional[torch.Tenso
     there; every other method writes a new tensor (``out`` if given)."""
     B, C, T = data.shape
     device = data.device
-    if out is not None and not _fresh_out_ok(out, data):
-        raise ValueError("out must be a distinct contiguous tensor shaped like data")
+    if out is not None:
+        _check_out(out, data)
     lib = _lib.load()
     kind = plan.kind
     if kind == "timemask":
@@ -333,9 +352,6 @@ def _apply_baseline(plan: MixPlan, data: torch.Tensor, out: Optional[torch.Tenso
     return out
 
 
-_SIGMOID: dict = {}       # device index -> float64 (10, 20) device tensor: the '(smooth)' coefficient tables
-
-
 def _sigmoid_table(device: torch.device) -> torch.Tensor:
     """The ten possible ``sigmoid(ov)`` tables of '(smooth)' (hostprep.sigmoid_table), uploaded once
     per device."""
@@ -359,8 +375,8 @@ def _apply_cutpaste(plan: MixPlan, data: torch.Tensor, frames: np.ndarray,
         raise ValueError("a 2D cutout plan is applied by augmentations2d.augment")
     B, C, T = data.shape
     device = data.device
-    if out is not None and not _fresh_out_ok(out, data):
-        raise ValueError("out must be a distinct contiguous tensor shaped like data")
+    if out is not None:
+        _check_out(out, data)
     lib = _lib.load()
     if kind == "cutout":
         dst = data if out is None else out.copy_(data)
@@ -422,7 +438,7 @@ def _augment_cutpaste(args, data: torch.Tensor, target_ohe, frames, wav, step: i
     _check_data(data, 3)
     B, C, T = data.shape
     frames_np = _as_numpy_frames(frames)
-    labels = (lambda: labels_from_ohe(target_ohe)) if host_labels is None else np.asarray(host_labels)
+    labels = _label_source(target_ohe, host_labels)
     plan = hostprep.cutpaste_plan(args.method, labels, frames_np, wav, step, B, C, T,
                                   batch_size=getattr(args, "batch_size", None),
                                   sample_rate=getattr(args, "sample_rate", None))
@@ -440,7 +456,7 @@ def _augment_baseline(args, data: torch.Tensor, target_ohe, frames, wav, step: i
     itself, zeroed in place."""
     B, C, T = data.shape
     frames_np = _as_numpy_frames(frames)
-    labels = (lambda: labels_from_ohe(target_ohe)) if host_labels is None else np.asarray(host_labels)
+    labels = _label_source(target_ohe, host_labels)
     plan = hostprep.make_plan(args.method, labels, frames_np, wav, step, B, C,
                               sample_rate=getattr(args, "sample_rate", None), sig_len=T)
     if not plan.fired:
@@ -451,23 +467,6 @@ def _augment_baseline(args, data: torch.Tensor, target_ohe, frames, wav, step: i
     if plan.mix_all:
         target_ohe = blend_targets(target_ohe, plan)
     return out, target_ohe, plan.mix, None
-
-
-_SPLICE_ERRORS = {-1: _PACK_ERRORS[1], -2: _PACK_ERRORS[2], -3: _PACK_ERRORS[3]}
-
-_CTX: dict = {}           # device index -> pcgmix_ctx* (per-device step context, never freed)
-_c_float = ctypes.c_float
-_get_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-_NOT_ARMED = -3          # PCGMIX_NOT_ARMED (include/pcgmix_hip.h)
-_I64_ARRAYS = {}
-
-
-def _fresh_out_ok(out: torch.Tensor, data: torch.Tensor) -> bool:
-    return out.shape == data.shape and out.dtype == data.dtype and out.is_contiguous() \
-        and out.data_ptr() != data.data_ptr()
-
 
 
 def _index_out(n: int):
@@ -535,9 +534,10 @@ def splice_plain(recipe, data: torch.Tensor, labels, frames, step: int,
             raise ValueError("labels/frames do not match the batch size")
         lab_ptr = labels.ctypes.data
     fr_ptr, fr_keep = _frames_ptr(frames, B)
-    stream = _get_raw_stream(idx) if _get_raw_stream is not None \
-        else torch.cuda.current_stream(data.device).cuda_stream
-    if ohe_ptr is not None and n_knots == 0 and (out is None or _fresh_out_ok(out, data)):
+    stream = _get_raw_stream(idx)
+    if out is not None:
+        _check_out(out, data)
+    if ohe_ptr is not None and n_knots == 0:
         # Strict signature, no warp: the ARMED kernel is launched FIRST (it needs neither lambda nor the
         # partners: both reach it in its records), lambda is drawn from numpy's stream while the GPU
         # gets to the kernel and the labels come back, then the second call delivers the records.
@@ -553,9 +553,7 @@ def splice_plain(recipe, data: torch.Tensor, labels, frames, step: int,
             mix_buf, mix = _index_out(B)
             err = lib.pcgmix_augment_plain_finish(ctx, fr_ptr, step, _c_float(lam), mix_buf)
             if err:
-                if err < 0:
-                    raise ValueError(_SPLICE_ERRORS.get(err, f"pcgmix_augment_plain_finish error {err}"))
-                _lib.check(err, "pcgmix_augment_plain_finish")
+                _check_splice(err, "pcgmix_augment_plain_finish")
             return out, mix
         if err != _NOT_ARMED:
             _lib.check(err, "pcgmix_augment_plain_begin")
@@ -565,17 +563,12 @@ def splice_plain(recipe, data: torch.Tensor, labels, frames, step: int,
     knots_ptr = knots.ctypes.data if isinstance(knots, np.ndarray) else knots
     if out is None:
         out = torch.empty_like(data)
-    elif out.shape != data.shape or out.dtype != data.dtype or not out.is_contiguous() \
-            or out.data_ptr() == data.data_ptr():
-        raise ValueError("out must be a distinct contiguous tensor shaped like data")
     mix_buf, mix = _index_out(B)
     err = _lib.load().pcgmix_augment_plain_f32(
         _CTX.get(idx) or step_context(idx), data.data_ptr(), out.data_ptr(), ohe_ptr, n_cls, lab_ptr,
         fr_ptr, step, _c_float(lam), knots_ptr, n_knots, mix_buf, B, C, T, stream)
     if err:
-        if err < 0:
-            raise ValueError(_SPLICE_ERRORS.get(err, f"pcgmix_augment_plain_f32 error {err}"))
-        _lib.check(err, "pcgmix_augment_plain_f32")
+        _check_splice(err, "pcgmix_augment_plain_f32")
     return out, mix
 
 
@@ -595,8 +588,7 @@ def _salopt_step(srec, g, data: torch.Tensor, ohe: Optional[torch.Tensor], label
     idx = data.device.index
     lib = _lib.load()
     ctx = _CTX.get(idx) or step_context(idx)
-    stream = _get_raw_stream(idx) if _get_raw_stream is not None \
-        else torch.cuda.current_stream(data.device).cuda_stream
+    stream = _get_raw_stream(idx)
     fr_ptr, fr_keep = _frames_ptr(frames, B)
     lab_ptr = None
     if labels is not None:
@@ -604,9 +596,8 @@ def _salopt_step(srec, g, data: torch.Tensor, ohe: Optional[torch.Tensor], label
         if labels.shape[0] != B:
             raise ValueError("labels/frames do not match the batch size")
         lab_ptr = labels.ctypes.data
-    if out is not None and (out.shape != data.shape or out.dtype != data.dtype
-                            or not out.is_contiguous() or out.data_ptr() == data.data_ptr()):
-        raise ValueError("out must be a distinct contiguous tensor shaped like data")
+    if out is not None:
+        _check_out(out, data)
     if lab_ptr is not None:
         name = "pcgmix_ctx_salopt_begin_labels"
         err = lib.pcgmix_ctx_salopt_begin_labels(ctx, lab_ptr, g.seed.shape[1], g.seed.data_ptr(),
@@ -616,9 +607,7 @@ def _salopt_step(srec, g, data: torch.Tensor, ohe: Optional[torch.Tensor], label
         err = lib.pcgmix_ctx_salopt_begin(ctx, ohe.data_ptr(), ohe.shape[1], g.seed.data_ptr(), fr_ptr,
                                           g.fr.data_ptr(), B, T, stream)
     if err:
-        if err < 0:
-            raise ValueError(_SPLICE_ERRORS.get(err, f"{name} error {err}"))
-        _lib.check(err, name)
+        _check_splice(err, name)
     if torch.cuda.current_device() == idx:
         sal = g.replay(data)
     else:
@@ -655,12 +644,6 @@ def blend_targets(target_ohe: torch.Tensor, plan: MixPlan) -> torch.Tensor:
     return target_ohe * lt + target_ohe[mix] * (1 - lt)
 
 
-_LABEL_PINNED: dict = {}
-
-
-_SIDE_STREAMS: dict = {}
-
-
 def labels_from_ohe(target_ohe: torch.Tensor, after: Optional["torch.cuda.Event"] = None) -> np.ndarray:
     """Reverse the one-hot encoding on the host (augmentations.py:501): one D2H copy of the
     (B, classes) matrix, argmax (first maximum, like torch.max) in numpy — no reduce kernel.
@@ -692,6 +675,12 @@ def labels_from_ohe(target_ohe: torch.Tensor, after: Optional["torch.cuda.Event"
             host.copy_(t, non_blocking=True)
         side.synchronize()
     return host.numpy().argmax(axis=1)
+
+
+def _label_source(target_ohe: torch.Tensor, host_labels):
+    """The ``labels`` argument of the plan functions: the caller's host labels, or a callable that
+    reads them back from ``target_ohe`` — asked only when the gate fires."""
+    return (lambda: labels_from_ohe(target_ohe)) if host_labels is None else np.asarray(host_labels)
 
 
 def _blend_planes(src: torch.Tensor, dst: torch.Tensor, mix_dev: torch.Tensor, lam: float) -> None:
@@ -758,10 +747,6 @@ def latent_blend(h: torch.Tensor, mix: np.ndarray, lam32) -> torch.Tensor:
     return LatentBlend.apply(h, mix_dev, inv_dev, float(lam32))
 
 
-_LATENT = "latentmixup"   # _RECIPES marker of a method string that reaches the 1D latentmixup branch
-_CUTPASTE = "cutpaste"    # ... that reaches a branch of hostprep.cutpaste_recipe
-
-
 def latent_partners(mix: np.ndarray, device: torch.device):
     """(mix, inverse permutation) as two int32 device vectors out of ONE upload.  Must be called
     with ``device`` current."""
@@ -787,13 +772,88 @@ def _augment_latent(args, data, target_ohe, step: int, model, host_labels):
     _check_data(data, 3)
     if model is None:
         raise ValueError("latentmixup needs the model (augment(..., model, ...))")
-    labels = (lambda: labels_from_ohe(target_ohe)) if host_labels is None else np.asarray(host_labels)
+    labels = _label_source(target_ohe, host_labels)
     plan = hostprep.latent_plan(args.method, getattr(args, "model", None), labels, step, data.shape[0])
     if not plan.fired:
         return data, target_ohe, [], None
     args.depth = plan.depth
     h = model(data, depth=plan.depth, pass_part="first")
     return latent_blend(h, plan.mix, plan.lam32), target_ohe, plan.mix, None
+
+
+def _saliency_front(args, srec, data: torch.Tensor, target_ohe, frames, frames_np, step: int,
+                    host_labels, labels):
+    """The saliency pass of a fired saliency-guided step, enqueued BEFORE the host part of the plan
+    (label read-back, permutation, lambda, B*(k+2)*C normal draws: ~0.1 ms) so that the GPU works
+    meanwhile.  The saliency maps use no host RNG, so the reference's draw order is kept.  Returns
+    ``(result, None, None)`` when the whole step ran here (same-label partners: ``_salopt_step``),
+    else ``(None, saliency maps, labels)`` for ``make_plan`` / ``apply_plan``."""
+    from . import saliency as _sal
+    B = data.shape[0]
+    # The label arg-max kernel of the step context goes first: it writes the labels into
+    # host-mapped memory (the read-back must wait for whatever produced target_ohe, but not
+    # for the saliency pass) and, on the way, the saliency pass's gradient seed; then the
+    # captured pass; the host picks the labels up when it needs them — by then the kernel has
+    # long finished and the GPU is inside the graph.
+    ohe = target_ohe.detach()
+    g = _sal.step_graph(args, data, ohe.shape[1]) if ohe.dim() == 2 else None
+    ohe_ok = ohe.dim() == 2 and ohe.is_cuda and ohe.dtype == torch.int64 and ohe.is_contiguous() \
+        and ohe.shape[0] == B
+    if isinstance(srec, Exception):
+        raise srec
+    if g is not None and srec is not None and (ohe_ok or host_labels is not None):
+        out, mix = _salopt_step(srec, g, data, ohe if host_labels is None else None, host_labels,
+                                frames, step)
+        return (out, target_ohe, mix, None), None, None
+    if g is not None and ohe_ok:
+        lib = _lib.load()
+        idx = data.device.index
+        ctx = _CTX.get(idx) or step_context(idx)
+        stream = _get_raw_stream(idx)
+        _lib.check(lib.pcgmix_ctx_labels_begin(ctx, ohe.data_ptr(), ohe.shape[1], B,
+                                               g.seed.data_ptr(), stream), "pcgmix_ctx_labels_begin")
+        with torch.cuda.device(data.device):
+            sal = g.run(data, frames_np, keep=False)         # consumed by the caller, in this call
+        if host_labels is None:
+            def labels():           # asked for by make_plan after its numpy draws
+                out = np.empty(B, dtype=np.int64)
+                _lib.check(lib.pcgmix_ctx_labels_wait(ctx, out.ctypes.data, B, stream),
+                           "pcgmix_ctx_labels_wait")
+                return out
+        return None, sal, labels
+    if host_labels is None:
+        mark = torch.cuda.Event()
+        mark.record(torch.cuda.current_stream(data.device))
+    sal = _sal.get_saliency_maps(args, data.device, data, target_ohe, frames_np, dim=1, gauss_k_n=101)
+    if host_labels is None:
+        labels = labels_from_ohe(target_ohe, after=mark)
+    return None, sal, labels
+
+
+def _augment_splice(args, route, data: torch.Tensor, target_ohe, frames, wav, step: int, host_labels):
+    """One call of a splice that is not plain — '(rand)', '(samePCG)', '(sameDataset)', '(mixAll)',
+    saliency-guided, or an empty batch — through ``make_plan`` / ``apply_plan``."""
+    if isinstance(route.plain, Exception):
+        raise route.plain
+    method = args.method
+    B, C, T = data.shape
+    frames_np = _as_numpy_frames(frames)
+    labels = _label_source(target_ohe, host_labels)
+    sal = None
+    if "(salopt" in method and B > 0:
+        if not hostprep.gate_fires(method, step):
+            return data, target_ohe, [], None
+        result, sal, labels = _saliency_front(args, route.salopt, data, target_ohe, frames, frames_np,
+                                              step, host_labels, labels)
+        if result is not None:
+            return result
+    plan = hostprep.make_plan(method, labels, frames_np, wav, step, B, C, is2d=False)
+    if not plan.fired:
+        return data, target_ohe, [], None
+    out = apply_plan(plan, data, frames_np, sal)
+    if plan.mix_all:
+        target_ohe = blend_targets(target_ohe, plan)
+    return out, target_ohe, plan.mix, None
 
 
 def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RESULTS_ARGS,
@@ -806,85 +866,25 @@ def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RE
     array.  A training loop that still has the loader's CPU ``target`` can pass it to spare the
     device->host read-back of ``target_ohe`` (the reference's only unavoidable sync,
     augmentations.py:501); results are identical."""
-    method = args.method
     step = int(step_counter.count)
-    recipe = _RECIPES.get(method, _RECIPES)
-    if recipe is _RECIPES and hostprep.latent_recipe(method) is not None:
-        recipe = _RECIPES[method] = _LATENT
-    if recipe is _LATENT:                         # latentmixup: the model's first half, blended
-        return _augment_latent(args, data, target_ohe, step, model, host_labels)
-    if recipe is _RECIPES and hostprep.cutpaste_recipe(method, False) is not None:
-        recipe = _RECIPES[method] = _CUTPASTE
-    if recipe is _CUTPASTE:                       # cut-and-paste family, durmixrespscale, cutout
-        return _augment_cutpaste(args, data, target_ohe, frames, wav, step, host_labels)
-    if recipe is _RECIPES:                        # first sight of this method string
-        recipe = hostprep.plain_recipe(method, False) \
-            if hostprep.select_method(method, is2d=False) is not None else False
-        _RECIPES[method] = recipe
-    if recipe is False:                           # not one of ours: passthrough (:731-732)
-        return data, target_ohe, [], None
-    _check_data(data, 3)
-    B, C, T = data.shape
-    if recipe is None and hostprep.select_method(method, False) in hostprep.BASELINE_METHODS_1D:
-        return _augment_baseline(args, data, target_ohe, frames, wav, step, host_labels)
-    if recipe is not None and B > 0:              # the common case: one library call
-        if not gate_passes(recipe, method, step, data.device.index):
-            return data, target_ohe, [], None
-        out, mix = splice_plain(recipe, data, host_labels, frames, step, target_ohe=target_ohe)
-        return out, target_ohe, mix, None
-    frames_np = _as_numpy_frames(frames)
-    labels = (lambda: labels_from_ohe(target_ohe)) if host_labels is None else np.asarray(host_labels)
-    sal = None
-    if "(salopt" in method and B > 0:
-        # Saliency-guided step: enqueue the frozen model's forward + input gradient +
-        # post-processing FIRST, then do the host part of the plan (label read-back, permutation,
-        # lambda, B*(k+2)*C normal draws: ~0.1 ms) while the GPU works.  The saliency maps use no
-        # host RNG, so the reference's draw order is kept.
-        if not hostprep.gate_fires(method, step):
-            return data, target_ohe, [], None
-        from . import saliency as _sal
-        # The label arg-max kernel of the step context goes first: it writes the labels into
-        # host-mapped memory (the read-back must wait for whatever produced target_ohe, but not
-        # for the saliency pass) and, on the way, the saliency pass's gradient seed; then the
-        # captured pass; the host picks the labels up when it needs them — by then the kernel has
-        # long finished and the GPU is inside the graph.
-        ohe = target_ohe.detach()
-        g = _sal.step_graph(args, data, ohe.shape[1]) if ohe.dim() == 2 else None
-        ohe_ok = ohe.dim() == 2 and ohe.is_cuda and ohe.dtype == torch.int64 and ohe.is_contiguous() \
-            and ohe.shape[0] == B
-        srec = hostprep.salopt_recipe(method)
-        if g is not None and srec is not None and (ohe_ok or host_labels is not None):
-            out, mix = _salopt_step(srec, g, data, ohe if host_labels is None else None, host_labels,
-                                    frames, step)
+    route = hostprep.route(args.method, False)         # cached: the one lookup of the hot path
+    family = route.family
+    if family == "splice":
+        _check_data(data, 3)
+        plain = route.plain
+        if plain.__class__ is tuple and data.shape[0] > 0:       # the common case: one library call
+            if not gate_passes(plain, args.method, step, data.device.index):
+                return data, target_ohe, [], None
+            out, mix = splice_plain(plain, data, host_labels, frames, step, target_ohe=target_ohe)
             return out, target_ohe, mix, None
-        if g is not None and ohe_ok:
-            lib = _lib.load()
-            idx = data.device.index
-            ctx = _CTX.get(idx) or step_context(idx)
-            stream = _raw_stream(data.device)
-            _lib.check(lib.pcgmix_ctx_labels_begin(ctx, ohe.data_ptr(), ohe.shape[1], B,
-                                                   g.seed.data_ptr(), stream), "pcgmix_ctx_labels_begin")
-            with torch.cuda.device(data.device):
-                sal = g.run(data, frames_np, keep=False)         # consumed below, in this call
-            if host_labels is None:
-                def labels():           # asked for by make_plan after its numpy draws
-                    out = np.empty(B, dtype=np.int64)
-                    _lib.check(lib.pcgmix_ctx_labels_wait(ctx, out.ctypes.data, B, stream),
-                               "pcgmix_ctx_labels_wait")
-                    return out
-        elif host_labels is None:
-            mark = torch.cuda.Event()
-            mark.record(torch.cuda.current_stream(data.device))
-            sal = _sal.get_saliency_maps(args, data.device, data, target_ohe, frames_np, dim=1,
-                                         gauss_k_n=101)
-            labels = labels_from_ohe(target_ohe, after=mark)
-        else:
-            sal = _sal.get_saliency_maps(args, data.device, data, target_ohe, frames_np, dim=1,
-                                         gauss_k_n=101)
-    plan = hostprep.make_plan(method, labels, frames_np, wav, step, B, C, is2d=False)
-    if not plan.fired:
+        return _augment_splice(args, route, data, target_ohe, frames, wav, step, host_labels)
+    if family == "passthrough":                        # not one of ours (:731-732)
         return data, target_ohe, [], None
-    out = apply_plan(plan, data, frames_np, sal)
-    if plan.mix_all:
-        target_ohe = blend_targets(target_ohe, plan)
-    return out, target_ohe, plan.mix, None
+    if family == "baseline":
+        _check_data(data, 3)
+        return _augment_baseline(args, data, target_ohe, frames, wav, step, host_labels)
+    if family == "cutpaste":                           # cut-and-paste family, durmixrespscale, cutout
+        return _augment_cutpaste(args, data, target_ohe, frames, wav, step, host_labels)
+    if family == "latent":                             # latentmixup: the model's first half, blended
+        return _augment_latent(args, data, target_ohe, step, model, host_labels)
+    raise NotImplementedError(route.refusal)

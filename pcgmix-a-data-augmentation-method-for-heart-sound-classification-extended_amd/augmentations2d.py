@@ -1,7 +1,10 @@
-"""Drop-in replacement for the PCGmix branch of the reference's ``augmentations2d.augment``
-(augmentations2d.py:267, ``durratiomixup`` branch :397-427; called from train_model.py:505).
+"""Drop-in replacement for the reference's ``augmentations2d.augment`` (augmentations2d.py:267,
+called from train_model.py:505): one cached ``hostprep.route(args.method, True)`` lookup, then one
+branch on the route's family — the ``durratiomixup`` splice (:397-427) and its mask variants, the
+comparison baselines, bare ``cutout``; a branch of the reference that is not served raises
+NotImplementedError (a bare ``mixup`` that nothing behind it catches among them).
 
-Also the mask variants ``durmixcutout(t,f)``, ``durmixtimemask(t)``, ``durmixfreqmask(f)``
+The mask variants ``durmixcutout(t,f)``, ``durmixtimemask(t)``, ``durmixfreqmask(f)``
 (augmentations2d.py:286-395): the same splice followed by a zeroed rectangle, fused into the same
 kernel launch as one extra predicate.
 
@@ -33,9 +36,6 @@ call, with the reference's return values (csrc/pcgmix_baselines2d.hip):
     cutout[(t,f)][+p]          durmixcutout's rectangle without the splice (augmentations2d.py:429-459):
                                rows [h1, h2) x columns [int(u1*f[-1]), int(u2*f[-1])) of every
                                channel zeroed IN PLACE; returns ``data`` itself, ``[]``, None
-
-A bare ``mixup`` that nothing behind it catches raises NotImplementedError from
-``hostprep.select_method``.
 """
 from __future__ import annotations
 
@@ -46,12 +46,8 @@ import torch
 
 from . import _lib, hostprep
 from .augmentations import (LatentBlend, _as_numpy_frames, _batch_dense, _blend_planes, _check_data,  # noqa: F401
-                            _raw_stream, apply_plan, blend_targets, gate_passes, labels_from_ohe,
+                            _label_source, _raw_stream, apply_plan, blend_targets, gate_passes,
                             latent_blend, splice_plain, upload_array)
-
-
-def _stream(device) -> ctypes.c_void_p:
-    return ctypes.c_void_p(_raw_stream(device))
 
 
 def zero_rects_(data: torch.Tensor, rect: np.ndarray) -> torch.Tensor:
@@ -65,7 +61,7 @@ def zero_rects_(data: torch.Tensor, rect: np.ndarray) -> torch.Tensor:
     with torch.cuda.device(data.device):
         dev = upload_array(np.ascontiguousarray(rect, dtype=np.int32), data.device)
         _lib.check(_lib.load().pcgmix_zero_rects_f32(data.data_ptr(), dev.data_ptr(), B, C, F, W, area,
-                                                     _stream(data.device)), "pcgmix_zero_rects_f32")
+                                                     ctypes.c_void_p(_raw_stream(data.device))), "pcgmix_zero_rects_f32")
     return data
 
 
@@ -83,21 +79,20 @@ def piecewise_rows(data: torch.Tensor, segs: np.ndarray, mix: np.ndarray, axis: 
         dev = upload_array(host, data.device)
         _lib.check(_lib.load().pcgmix_piecewise_rows_f32(
             data.data_ptr(), out.data_ptr(), dev.data_ptr(), dev.data_ptr() + segs.size * 4, axis,
-            B, C, F, W, out_cols, _stream(data.device)), "pcgmix_piecewise_rows_f32")
+            B, C, F, W, out_cols, ctypes.c_void_p(_raw_stream(data.device))), "pcgmix_piecewise_rows_f32")
     return out
 
 
-def _augment_baseline2d(args, data, target_ohe, frames, step: int, model, host_labels):
-    """One call of a spectrogram baseline (augmentations2d.py:461-617)."""
+def _augment_baseline2d(args, name, data, target_ohe, frames, step: int, model, host_labels):
+    """One call of the spectrogram baseline ``name`` (augmentations2d.py:461-617)."""
     _check_data(data, 4)
     B, C, F, W = data.shape
-    name = hostprep.select_method(args.method, is2d=True)
     if name == "latentmixup" and getattr(args, "model", None) != "resnet9":
         # the reference sets max_model_depth for 'resnet9' only (augmentations2d.py:520-521)
         raise NotImplementedError(f"latentmixup: the reference defines the mixing depth for "
                                   f"args.model == 'resnet9' only, got {getattr(args, 'model', None)!r}")
     frames_np = _as_numpy_frames(frames)
-    labels = (lambda: labels_from_ohe(target_ohe)) if host_labels is None else np.asarray(host_labels)
+    labels = _label_source(target_ohe, host_labels)
     plan = hostprep.make_plan(args.method, labels, frames_np, None, step, B, C, is2d=True, n_cols=W,
                               n_freq=F)
     if not plan.fired:
@@ -139,29 +134,22 @@ def _augment_cutout2d(args, data, target_ohe, frames, step: int):
     return zero_rects_(data, plan.zero_rect), target_ohe, [], None
 
 
-def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RESULTS_ARGS,
-            host_labels=None):
-    method = args.method
-    step = int(step_counter.count)
-    if hostprep.cutpaste_recipe(method, True) is not None:
-        return _augment_cutout2d(args, data, target_ohe, frames, step)
-    name = hostprep.select_method(method, is2d=True)
-    if name is None:
-        return data, target_ohe, [], None
-    if name in hostprep.BASELINE_METHODS_2D:
-        return _augment_baseline2d(args, data, target_ohe, frames, step, model, host_labels)
+def _augment_splice2d(args, route, data, target_ohe, frames, wav, step: int, device, host_labels):
+    """One call of ``durratiomixup`` or a mask variant (augmentations2d.py:286-427)."""
     _check_data(data, 4)
     B, Cc, F, W = data.shape
-    recipe = hostprep.plain_recipe(method, True)
-    if recipe is not None and B > 0:              # durratiomixup: one library call
-        if not gate_passes(recipe, method, step, data.device.index):
+    plain = route.plain
+    if plain.__class__ is tuple and B > 0:             # durratiomixup: one library call
+        if not gate_passes(plain, args.method, step, data.device.index):
             return data, target_ohe, [], None
-        out, mix = splice_plain(recipe, data.view(B, Cc * F, W), host_labels, frames, step,
+        out, mix = splice_plain(plain, data.view(B, Cc * F, W), host_labels, frames, step,
                                 target_ohe=target_ohe)
         return out.view(B, Cc, F, W), target_ohe, mix, None
+    if isinstance(plain, Exception):
+        raise plain
     frames_np = _as_numpy_frames(frames)
-    labels = (lambda: labels_from_ohe(target_ohe)) if host_labels is None else host_labels
-    plan = hostprep.make_plan(method, labels, frames_np, wav, step, B, Cc * F, is2d=True, n_cols=W)
+    plan = hostprep.make_plan(args.method, _label_source(target_ohe, host_labels), frames_np, wav, step,
+                              B, Cc * F, is2d=True, n_cols=W)
     if not plan.fired:
         return data, target_ohe, [], None
     sal = None
@@ -173,3 +161,19 @@ def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RE
         sal = saliency.get_saliency_maps(args, device, data, target_ohe, frames_np, dim=2)
     out = apply_plan(plan, data.view(B, Cc * F, W), frames_np, sal).view(B, Cc, F, W)
     return out, target_ohe, plan.mix, None
+
+
+def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RESULTS_ARGS,
+            host_labels=None):
+    step = int(step_counter.count)
+    route = hostprep.route(args.method, True)
+    family = route.family
+    if family == "splice":
+        return _augment_splice2d(args, route, data, target_ohe, frames, wav, step, device, host_labels)
+    if family == "passthrough":
+        return data, target_ohe, [], None
+    if family == "baseline":
+        return _augment_baseline2d(args, route.branch, data, target_ohe, frames, step, model, host_labels)
+    if family == "cutpaste":
+        return _augment_cutout2d(args, data, target_ohe, frames, step)
+    raise NotImplementedError(route.refusal)

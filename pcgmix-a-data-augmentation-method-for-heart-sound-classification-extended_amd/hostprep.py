@@ -1,5 +1,12 @@
 """Host prologue of one PCGmix augmentation call: everything that is integer or random.
 
+Which augmentation a method string selects is decided in ONE place: ``route(method, is2d)`` walks the
+reference's if-chain (``_CHAIN_1D`` / ``_CHAIN_2D``, stated once, in the reference's order) and
+returns a cached ``Route``: the branch reached, the family that serves it ("passthrough", "splice",
+"baseline", "cutpaste", "latent", "refused") and the splice's recipes.  ``select_method``,
+``plain_recipe``, ``salopt_recipe``, ``latent_recipe``, ``cutpaste_recipe`` and ``soft_targets`` are
+views of it; both ``augment()``s and the training steps branch on ``Route.family``.
+
 The reference derives all randomness of a step from ``step_counter.count`` through CPython's
 ``random.Random`` and numpy's legacy global ``RandomState`` (augmentations.py:869, 936, 500-514,
 659-666, 677).  Those streams *define* parity, are O(B) work, and are therefore kept on the
@@ -19,7 +26,7 @@ positions, ``Random(step*131071).randint(1, 3)`` for ``(rand)cutmix``'s cut and
 
 The heart-cycle cut-and-paste family, ``durmixrespscale`` and bare ``cutout`` (augmentations.py:
 734-775, 983-1000, 1101-1213, 1285-1316, 1569-1616; augmentations2d.py:429-459) are planned by
-``cutpaste_recipe`` / ``cutpaste_plan``: the gate, partners by label / recording / data set /
+``cutpaste_plan``: the gate, partners by label / recording / data set /
 (label, length bin), ``Random(step).randint(1, 3)`` or ``Random(step*131071).randint(1, 3)`` for
 the cut, ``Random(step + i*131071)`` for the 'cutout' suffix; only ``durmixrespscale`` touches
 numpy's global stream (``get_lambda``).
@@ -43,58 +50,63 @@ from . import _lib
 SPLICE_METHODS_1D = ("durmixmagwarp", "durratiomixup")
 BASELINE_METHODS_1D = ("respiratoryscale", "timemask", "mixup", "timewarp", "magnitudewarp")
 PCGMIX_METHODS_1D = SPLICE_METHODS_1D + BASELINE_METHODS_1D
-# 2D dispatch order: augmentations2d.py:286 (cutout), :325 (timemask), :361 (freqmask), :397
+# the PCGmix splice and its mask variants on spectrograms (augmentations2d.py:286, 328, 364, 397)
 PCGMIX_METHODS_2D = ("durmixcutout", "durmixtimemask", "durmixfreqmask", "durratiomixup")
 # the paper's spectrogram comparison baselines (augmentations2d.py:461, 487, 510, 538, 574, 599)
 BASELINE_METHODS_2D = ("timemask", "freqmask", "latentmixup", "mixup", "cutmix", "durratiocutmix")
 
-# Every name the reference dispatcher knows (augmentations.py:700-729, augmentations2d.py:269-281).
-# A method string that names one of these but none of ours is refused loudly instead of being
-# passed through un-augmented.
-_REFERENCE_METHODS_1D = (
-    "durratiocutmix", "lengthcutmix", "datasetcutmix", "wav-durratiocutmix", "wavcutmix",
-    "lc-nointrusion", "labelcutmix", "swapsysdia", "s1s2mask", "cont-cutmix", "saliency-cutmix",
-    "latentmixup", "manifold-cutmix(ch)", "manifold-cutmix", "manifold-cutout(ch)",
-    "manifold-cutout", "cutmix(ch)", "cutmix", "cutout(ch)", "cutout", "gaussiannoise",
-    "magnitudewarp", "timewarp", "mixup", "timemask", "durratiomixup", "durmixmagwarp",
-    "respiratoryscale", "durmixrespscale")
-_REFERENCE_METHODS_2D = (
-    "durratiocutmix", "cutmix", "mixup", "latentmixup", "freqmask", "timemask", "cutout",
-    "durratiomixup", "durmixfreqmask", "durmixtimemask", "durmixcutout")
-
-def _has(name):
-    return lambda m: name in m
+# Names planned by ``cutpaste_plan`` (1D: augmentations.py:734, 983, 1101, 1121, 1153, 1184, 1285,
+# 1569; 2D: augmentations2d.py:429).
+CUTPASTE_METHODS_1D = ("durmixrespscale", "wav-durratiocutmix", "durratiocutmix", "lengthcutmix",
+                       "datasetcutmix", "wavcutmix", "labelcutmix", "cutout")
+CUTPASTE_METHODS_2D = ("cutout",)
+CUTPASTE_KINDS = ("cutpaste", "mixscale", "cutout", "cutout2d")      # MixPlan.kind of a cutpaste_plan
 
 
-# The reference's 1D if-chain up to the last branch select_method serves, in its order
-# (augmentations.py:734, 777, 807, 829, 864, 931, 983, 1002, 1026); select_method refuses everything
-# behind it (the whole chain: _FULL_CHAIN_1D, for cutpaste_recipe).
-_CHAIN_1D = (
-    (_has("durmixrespscale"), "durmixrespscale"),
-    (_has("respiratoryscale"), "respiratoryscale"),
-    (_has("timemask"), "timemask"),
-    (lambda m: "mixup" in m and "latentmixup" not in m and "durratiomixup" not in m, "mixup"),
-    (_has("durmixmagwarp"), "durmixmagwarp"),
-    (_has("durratiomixup"), "durratiomixup"),
-    (_has("wav-durratiocutmix"), "wav-durratiocutmix"),
-    (_has("timewarp"), "timewarp"),
-    (_has("magnitudewarp"), "magnitudewarp"),
+def _branch(name, line, cond=None):
+    """One branch of the reference's if-chain: its name, the source line it restates, and its
+    condition on the method string (a bare substring test unless given)."""
+    return name, line, cond or (lambda m: name in m)
+
+
+# The reference's if-chains, each stated ONCE, whole and in the reference's order; ``route`` is the
+# only function that walks them.  Every branch returns, except 'mixup' (see ``route``).  A method
+# string that holds none of a chain's names is passed through (augmentations.py:731-732,
+# augmentations2d.py:283-284: the names of ``methods_implemented`` all contain one of these).
+_CHAIN_1D = (                                                         # augmentations.py
+    _branch("durmixrespscale", 734), _branch("respiratoryscale", 777), _branch("timemask", 807),
+    _branch("mixup", 829, lambda m: "mixup" in m and "latentmixup" not in m and "durratiomixup" not in m),
+    _branch("durmixmagwarp", 864), _branch("durratiomixup", 931), _branch("wav-durratiocutmix", 983),
+    _branch("timewarp", 1002), _branch("magnitudewarp", 1026), _branch("gaussiannoise", 1050),
+    _branch("(UMC-subset)durratiocutmix", 1080, lambda m: "(UMC-subset)durratiocutmix" in m
+            and "(plus)" not in m and "(plusplus)" not in m),
+    _branch("durratiocutmix", 1101, lambda m: "durratiocutmix" in m and "(plus)" not in m
+            and "(plusplus)" not in m and "(UMC" not in m and "wav-durratiocutmix" not in m),
+    _branch("lengthcutmix", 1121), _branch("datasetcutmix", 1153),
+    _branch("wavcutmix", 1184, lambda m: "wavcutmix" in m and "durratiowavcutmix" not in m),
+    _branch("lc-nointrusion", 1215), _branch("labelcutmix", 1285), _branch("swapsysdia", 1318),
+    _branch("cont-cutmix", 1356), _branch("saliency-cutmix", 1396), _branch("latentmixup", 1472),
+    _branch("cutmix", 1508, lambda m: "cutmix" in m and "saliency" not in m and "label" not in m),
+    _branch("cutout", 1569, lambda m: "cutout" in m and "saliency" not in m),
+    _branch("s1s2mask", 1618, lambda m: m == "s1s2mask"),
 )
-# The reference's 2D if-chain, in its order (augmentations2d.py:286, 325, 361, 397, 429, 461, 487, 510,
-# 538, 574, 599).  'cutout' is served through cutpaste_recipe / cutpaste_plan, not through select_method.
-_CHAIN_2D = (
-    (_has("durmixcutout"), "durmixcutout"),
-    (_has("durmixtimemask"), "durmixtimemask"),
-    (_has("durmixfreqmask"), "durmixfreqmask"),
-    (_has("durratiomixup"), "durratiomixup"),
-    (lambda m: "cutout" in m and "durmixcutout" not in m, "cutout"),
-    (lambda m: "timemask" in m and "durmixtimemask" not in m, "timemask"),
-    (lambda m: "freqmask" in m and "durmixfreqmask" not in m, "freqmask"),
-    (_has("latentmixup"), "latentmixup"),
-    (lambda m: "mixup" in m and "durratiomixup" not in m and "latentmixup" not in m, "mixup"),
-    (lambda m: "cutmix" in m and "durratiocutmix" not in m, "cutmix"),
-    (_has("durratiocutmix"), "durratiocutmix"),
+_CHAIN_2D = (                                                         # augmentations2d.py
+    _branch("durmixcutout", 286), _branch("durmixtimemask", 328), _branch("durmixfreqmask", 364),
+    _branch("durratiomixup", 397),
+    _branch("cutout", 429, lambda m: "cutout" in m and "durmixcutout" not in m),
+    _branch("timemask", 461, lambda m: "timemask" in m and "durmixtimemask" not in m),
+    _branch("freqmask", 487, lambda m: "freqmask" in m and "durmixfreqmask" not in m),
+    _branch("latentmixup", 510),
+    _branch("mixup", 538, lambda m: "mixup" in m and "durratiomixup" not in m and "latentmixup" not in m),
+    _branch("cutmix", 574, lambda m: "cutmix" in m and "durratiocutmix" not in m),
+    _branch("durratiocutmix", 599),
 )
+# Who serves a branch: "splice" and "baseline" go through plain_recipe / salopt_recipe / make_plan,
+# "cutpaste" through cutpaste_plan, "latent" (1D) through latent_plan; any other branch is refused.
+_FAMILY_1D = {**dict.fromkeys(SPLICE_METHODS_1D, "splice"), **dict.fromkeys(BASELINE_METHODS_1D, "baseline"),
+              **dict.fromkeys(CUTPASTE_METHODS_1D, "cutpaste"), "latentmixup": "latent"}
+_FAMILY_2D = {**dict.fromkeys(PCGMIX_METHODS_2D, "splice"), **dict.fromkeys(BASELINE_METHODS_2D, "baseline"),
+              **dict.fromkeys(CUTPASTE_METHODS_2D, "cutpaste")}
 _UNSUPPORTED_SELECTORS = ("(sameCVD)", "(closestbins=", "(closestknn=")
 
 
@@ -121,73 +133,112 @@ class MixPlan:
     segs: Optional[np.ndarray] = None          # int32 (B,5,4) {lo,hi,src,shift}: cutmix / durratiocutmix
     seg_axis: int = 0                          # 0: segments along the columns, 1: along F ('(rand)')
     out_cols: int = 0                          # width of the new tensor (cutmix: F, augmentations2d.py:589)
-    family: str = ""                           # cutpaste_plan: "cutpaste" | "mixscale" | "cutout" | "cutout2d"
     junctions: Optional[np.ndarray] = None     # int32 (B,4) {c1, c2, ov, 0}: the '(smooth)' cross-fade
     span_rows: int = 0                         # cutout: rows per sample that carry a span of their own
                                                # (1, or C for '(ch)': spans is then (B*C, 2))
+    # Which device path applies the plan, set where the plan is made: "splice" (durratiomixup /
+    # durmixmagwarp and the 2D mask variants), the 1D baseline's name, the 2D baseline's name with a
+    # "2d" suffix ("timemask2d", "cutmix2d", ...: a 2D timemask is a rectangle per channel, never the
+    # 1D span path), or one of CUTPASTE_KINDS: "cutpaste" (segment table + junction), "mixscale"
+    # (durmixrespscale: splice x row), "cutout" (1D spans, in place), "cutout2d" (rectangles, in place).
+    kind: str = ""
 
-    @property
-    def kind(self) -> str:
-        """"splice" (durratiomixup / durmixmagwarp and the 2D mask variants), the 1D baseline's
-        name, the 2D baseline's name with a "2d" suffix ("timemask2d", "cutmix2d", ...): a 2D
-        timemask is a rectangle per channel, never the 1D span path — or, for a ``cutpaste_plan``,
-        its family: "cutpaste" (segment table + junction), "mixscale" (durmixrespscale: splice x
-        row), "cutout" (1D spans, in place), "cutout2d" (rectangles, in place)."""
-        if self.family:
-            return self.family
-        if self.is2d:
-            return self.name + "2d" if self.name in BASELINE_METHODS_2D else "splice"
-        return self.name if self.name in BASELINE_METHODS_1D else "splice"
+    def __post_init__(self):
+        if not self.kind:                      # a plan built by hand from a branch name
+            self.kind = _plan_kind(route(self.name, self.is2d), self.is2d)
 
 
-def _branch_2d(method: str) -> str:
-    """The reference's 2D if-chain (augmentations2d.py:286-617), as ``_branch_1d``: a bare ``mixup``
-    (no '(same)', no '(mix)', :547-572) falls through to the later branches; "" when the branch
-    reached is not one select_method serves ('cutout': see cutpaste_recipe) or none is (the reference
-    returns None)."""
-    for cond, name in _CHAIN_2D:
-        if not cond(method):
-            continue
-        if name == "mixup" and "(same)" not in method and "(mix)" not in method:
-            continue
-        return name if name in PCGMIX_METHODS_2D + BASELINE_METHODS_2D else ""
-    return ""
+@dataclass(frozen=True)
+class Route:
+    """Where the reference's if-chain sends one method string, and who serves it here."""
+    branch: Optional[str]     # name of the branch reached; None: no branch returns (or none is named)
+    family: str               # "passthrough" | "splice" | "baseline" | "cutpaste" | "latent" | "refused"
+    plain: object = None      # plain_recipe's tuple, None, or the exception its parsers raised
+    salopt: object = None     # salopt_recipe's tuple, None, or the exception it raised
+    soft_targets: bool = False
+    refusal: str = ""         # "refused": why
 
 
-def _branch_1d(method: str) -> Optional[str]:
-    """The reference's 1D if-chain (augmentations.py:734-1618): the name of the first branch that
-    returns, or "" when that branch is not implemented here.  Every branch draws the same gate
-    (``Random(step).uniform(0, 1) < p``), so a branch that falls through — ``mixup`` without
-    ``(same)`` or ``(mix)``, augmentations.py:829-862 — leaves the decision to the next one."""
-    for cond, name in _CHAIN_1D:
-        if not cond(method):
-            continue
-        if name == "mixup" and "(same)" not in method and "(mix)" not in method:
-            continue
-        return name if name in PCGMIX_METHODS_1D else ""
-    return ""                   # falls off the end: the reference returns None
+def _recorded(fn, *args):
+    """``fn(*args)``, or the exception a malformed parameter makes it raise: ``route`` itself never
+    raises, the function that owns the answer does (``_value``)."""
+    try:
+        return fn(*args)
+    except (ValueError, IndexError, NotImplementedError) as exc:
+        return exc
+
+
+def _value(answer):
+    if isinstance(answer, Exception):
+        raise answer.with_traceback(None)      # the cached object: do not pile tracebacks up on it
+    return answer
 
 
 @functools.lru_cache(maxsize=256)
-def select_method(method: str, is2d: bool) -> Optional[str]:
-    """Which of our branches the reference's if-chain would reach, or None for passthrough.
+def route(method: str, is2d: bool) -> Route:
+    """One walk of the reference's if-chain for ``method``: the first branch that returns.  Every
+    branch draws the same gate (``Random(step).uniform(0, 1) < p``), so the one branch that falls
+    through — ``mixup`` without '(same)' or '(mix)', augmentations.py:829-862, augmentations2d.py:
+    547-572 — leaves the decision to the next one.  Never raises: what is not served is "refused"."""
+    chain = _CHAIN_2D if is2d else _CHAIN_1D
+    soft = "(mixAll)" in method                                # augmentations.py:915-917, 978-980
+    if not any(name in method for name, _, _ in chain):
+        return Route(None, "passthrough", soft_targets=soft)   # augmentations.py:731-732
+    branch = line = None
+    for name, at, cond in chain:
+        if cond(method) and (name != "mixup" or "(same)" in method or "(mix)" in method):
+            branch, line = name, at
+            break
+    family = (_FAMILY_2D if is2d else _FAMILY_1D).get(branch, "refused")
+    refusal = ""
+    if branch is None:
+        refusal = f"method {method!r} names a reference augmentation but reaches no branch that returns"
+    elif family == "refused":
+        refusal = (f"method {method!r} reaches the reference's branch {branch!r} (line {line}), which is "
+                   f"not served: the reference's 2-tuple branches, manifold-*, (UMC-subset) and "
+                   f"gaussiannoise are out of scope")
+    elif not is2d:
+        sel = next((s for s in _UNSUPPORTED_SELECTORS if s in method), None)
+        if family == "splice" and sel is not None:
+            refusal = f"partner selector {sel!r} is out of scope (SURVEY.md §2)"
+        elif branch == "cutout" and "manifold" in method:
+            refusal = "manifold-cutout needs max_depth, which the reference binds for FCN only"
+        elif branch == "latentmixup" and ("durratiocutmix" in method or "wavcutmix" in method):
+            # stricter than :1472: such a string gets past :1080 / :1101 / :1184 only through their
+            # exclusions ('(plus)', '(UMC', 'durratiowavcutmix') and has been refused from the start
+            refusal = f"method {method!r}: latentmixup next to a durratiocutmix / wavcutmix variant is not served"
+    if refusal:
+        return Route(branch, "refused", soft_targets=soft, refusal=refusal)
+    if family == "baseline":
+        soft = soft or (branch == "mixup" and "(same)" not in method)       # 'mixup(mix)', :857
+    if family != "splice":
+        return Route(branch, family, soft_targets=soft)
+    return Route(branch, family, _recorded(_plain, method, branch, is2d),
+                 None if is2d else _recorded(_salopt, method, branch), soft)
 
-    Raises NotImplementedError for reference augmentations outside this package's scope."""
-    ours = PCGMIX_METHODS_2D + BASELINE_METHODS_2D if is2d else PCGMIX_METHODS_1D
-    known = _REFERENCE_METHODS_2D if is2d else _REFERENCE_METHODS_1D
-    if not any(m in method for m in known):
-        return None                                            # augmentations.py:731-732
-    hit = (_branch_2d(method) if is2d else _branch_1d(method)) or None
-    if hit is None:
-        raise NotImplementedError(
-            f"method {method!r} selects no augmentation that select_method() serves {ours}; the "
-            f"cut-and-paste family, durmixrespscale, cutout and latentmixup are answered by "
-            f"cutpaste_recipe() / latent_recipe(), which augment() asks first; the reference's "
-            f"2-tuple branches, manifold-*, (UMC-subset), (sameCVD) and gaussiannoise are not served")
-    for sel in _UNSUPPORTED_SELECTORS:
-        if sel in method and not is2d and hit in SPLICE_METHODS_1D:
-            raise NotImplementedError(f"partner selector {sel!r} is out of scope (SURVEY.md §2)")
-    return hit
+
+def _plan_kind(r: Route, is2d: bool) -> str:
+    if r.family != "baseline":
+        return "splice"
+    return r.branch + "2d" if is2d else r.branch
+
+
+def _waveform_route(method: str, is2d: bool) -> Route:
+    """``route`` for the callers that go on to launch a splice or a baseline (or nothing, on
+    passthrough): every other family raises NotImplementedError."""
+    r = route(method, is2d)
+    if r.family in ("refused", "cutpaste", "latent"):
+        raise NotImplementedError(r.refusal or f"method {method!r} ({r.branch}) is not an augmentation of "
+                                  f"the waveform that make_plan() serves: see cutpaste_plan() / latent_plan()")
+    return r
+
+
+def select_method(method: str, is2d: bool) -> Optional[str]:
+    """Which splice or baseline branch the reference's if-chain reaches, or None for passthrough.
+
+    Raises NotImplementedError for reference augmentations outside this package's scope — and for
+    the cut-and-paste family and 1D latentmixup, which ``cutpaste_recipe`` / ``latent_recipe`` name."""
+    return _waveform_route(method, is2d).branch
 
 
 @functools.lru_cache(maxsize=256)
@@ -205,27 +256,20 @@ def parse_alpha(method: str, name: str) -> float:
 
 
 @functools.lru_cache(maxsize=256)
-def parse_magwarp(method: str):
-    """'durmixmagwarp(sigma,knot)' (augmentations.py:919-923); defaults 0.2, 4."""
-    sigma, knot = 0.2, 4
-    parts = method.split("durmixmagwarp(")
-    if len(parts) > 1:
-        sigma = float(parts[1].split(",")[0])
-        knot = int(method.split(",")[1].split(")")[0])
-    return sigma, knot
-
-
-@functools.lru_cache(maxsize=256)
 def parse_warp(method: str, name: str):
-    """'magnitudewarp(sigma,knot)' (augmentations.py:1039-1042; defaults 0.2, 4) and
-    'timewarp(sigma,knot)' (:1015-1018; defaults 0.05, 2).  As in the reference, the knot count is
-    read behind the method string's FIRST comma."""
+    """'durmixmagwarp(sigma,knot)' (augmentations.py:919-923) and 'magnitudewarp(sigma,knot)'
+    (:1039-1042), defaults 0.2, 4; 'timewarp(sigma,knot)' (:1015-1018), defaults 0.05, 2.  As in the
+    reference, the knot count is read behind the method string's FIRST comma."""
     sigma, knot = (0.05, 2) if name == "timewarp" else (0.2, 4)
     parts = method.split(name + "(")
     if len(parts) > 1:
         sigma = float(parts[1].split(",")[0])
         knot = int(method.split(",")[1].split(")")[0])
     return sigma, knot
+
+
+def parse_magwarp(method: str):
+    return parse_warp(method, "durmixmagwarp")
 
 
 @functools.lru_cache(maxsize=256)
@@ -238,16 +282,21 @@ def parse_timemask(method: str) -> float:
 
 
 @functools.lru_cache(maxsize=256)
-def parse_respscale(method: str):
-    """'respiratoryscale(min,max)' in breaths per minute -> (min, max) in Hz (augmentations.py:
-    791-795): min through float(), max through int() and from behind the string's FIRST comma —
-    so 'respiratoryscale(12,20.5)' raises ValueError as the reference does."""
+def parse_respscale(method: str, name: str = "respiratoryscale"):
+    """'respiratoryscale(min,max)' (augmentations.py:791-795) or, with ``name``,
+    'durmixrespscale(min,max)' (:760-764) in breaths per minute -> (min, max) in Hz: min through
+    float(), max through int() and from behind the string's FIRST comma — so
+    'respiratoryscale(12,20.5)' raises ValueError as the reference does."""
     lo, hi = 12 / 60, 20 / 60
-    parts = method.split("respiratoryscale(")
+    parts = method.split(name + "(")
     if len(parts) > 1:
         lo = float(parts[1].split(",")[0]) / 60
         hi = int(method.split(",")[1].split(")")[0]) / 60
     return lo, hi
+
+
+def parse_durmixrespscale(method: str):
+    return parse_respscale(method, "durmixrespscale")
 
 
 def mask_spans(method: str, frames: np.ndarray, step: int, sig_len: int) -> np.ndarray:
@@ -265,75 +314,71 @@ def mask_spans(method: str, frames: np.ndarray, step: int, sig_len: int) -> np.n
     return np.clip(spans, 0, sig_len).astype(np.int32)
 
 
-def respiration_row(method: str, step: int, sig_len: int, sample_rate) -> np.ndarray:
-    """respiratoryscale's sinusoid (augmentations.py:796-799), with numpy as the reference builds
-    it: the gate's own ``u = Random(step).random()`` gives rate = min + (max-min)*u and phase =
-    2*pi*u (``Random(step).uniform`` twice on fresh generators)."""
-    lo, hi = parse_respscale(method)
-    return _respiration_row(lo, hi, step, sig_len, sample_rate)
+def respiration_row(band, step: int, sig_len: int, sample_rate) -> np.ndarray:
+    """The sinusoid of respiratoryscale / durmixrespscale (augmentations.py:796-799, 765-768) for
+    ``band`` = (min, max) in Hz, with numpy as the reference builds it: the gate's own ``u =
+    Random(step).random()`` gives rate = min + (max-min)*u and phase = 2*pi*u
+    (``Random(step).uniform`` twice on fresh generators)."""
+    lo, hi = band
+    u = _lib.load().pcgmix_py_uniform01(int(step))
+    rate = lo + (hi - lo) * u
+    phase = 0 + (2 * np.pi - 0) * u
+    t = np.linspace(0, sig_len / sample_rate, sig_len)
+    return np.sin(2 * np.pi * rate * t + phase)
 
 
-@functools.lru_cache(maxsize=256)
-def plain_recipe(method: str, is2d: bool):
-    """(name, p, alpha, sigma, knots) when ``method`` is a plain splice — same-label partners, no
-    '(rand)' offsets, no saliency, no 2D mask — i.e. what ``pcgmix_splice_same_label_f32`` does in
-    one call; None otherwise (the general ``make_plan`` path handles those)."""
-    name = select_method(method, is2d)
-    if name is None or (not is2d and name not in SPLICE_METHODS_1D):
-        return None
+def _plain(method: str, name: str, is2d: bool):
+    """Route.plain of a splice branch."""
     if is2d:
         if name != "durratiomixup" or "(salopt" in method:
             return None
         return name, parse_probability(method), 1.0, 0.0, 0          # augmentations2d.py:411
     if any(t in method for t in ("(rand)", "(salopt", "(samePCG)", "(sameDataset)", "(mixAll)")):
         return None
-    sigma, knot = parse_magwarp(method) if name == "durmixmagwarp" else (0.0, -2)
+    sigma, knot = parse_warp(method, name) if name == "durmixmagwarp" else (0.0, -2)
     return name, parse_probability(method), parse_alpha(method, name), sigma, knot + 2
 
 
-@functools.lru_cache(maxsize=256)
+def _salopt(method: str, name: str):
+    """Route.salopt of a 1D splice branch."""
+    if "(salopt" not in method or any(t in method for t in ("(samePCG)", "(sameDataset)", "(mixAll)")):
+        return None
+    mode = _salopt_mode(method)
+    sigma, knot = parse_warp(method, name) if name == "durmixmagwarp" else (0.0, -2)
+    return mode, parse_alpha(method, name), sigma, knot + 2
+
+
+def _salopt_mode(method: str) -> int:
+    if "(saloptenv" in method:
+        return 0
+    if "(saloptsum" in method:
+        return 1
+    raise NotImplementedError("only (saloptenv…) and (saloptsum…) exist in the reference")
+
+
+def plain_recipe(method: str, is2d: bool):
+    """(name, p, alpha, sigma, knots) when ``method`` is a plain splice — same-label partners, no
+    '(rand)' offsets, no saliency, no 2D mask — i.e. what ``pcgmix_augment_plain_f32`` does in
+    one call; None otherwise (the general ``make_plan`` path handles those)."""
+    return _value(_waveform_route(method, is2d).plain)
+
+
 def salopt_recipe(method: str):
     """(mode, alpha, sigma, knots) when ``method`` is a saliency-guided splice with same-label
     partners — what ``pcgmix_ctx_salopt_begin/_finish`` do around the saliency pass; None otherwise
     ('(samePCG)', '(sameDataset)', '(mixAll)': the general ``make_plan`` path)."""
-    name = select_method(method, False)
-    if name is None or name not in SPLICE_METHODS_1D or "(salopt" not in method:
-        return None
-    if any(t in method for t in ("(samePCG)", "(sameDataset)", "(mixAll)")):
-        return None
-    if "(saloptenv" in method:
-        mode = 0
-    elif "(saloptsum" in method:
-        mode = 1
-    else:
-        raise NotImplementedError("only (saloptenv…) and (saloptsum…) exist in the reference")
-    sigma, knot = parse_magwarp(method) if name == "durmixmagwarp" else (0.0, -2)
-    return mode, parse_alpha(method, name), sigma, knot + 2
+    return _value(_waveform_route(method, False).salopt)
 
 
-# Names whose branch comes BEFORE 'latentmixup' in the reference's 1D if-chain (augmentations.py:
-# 734-1396) and is entered on a bare substring test; the bare-'mixup' branch (:829) excludes
-# 'latentmixup' by its own condition, and what comes later ('cutmix', 'cutout', ...) never gets a
-# turn.
-_BEFORE_LATENT_1D = (
-    "durmixrespscale", "respiratoryscale", "timemask", "durmixmagwarp", "durratiomixup",
-    "wav-durratiocutmix", "timewarp", "magnitudewarp", "gaussiannoise", "durratiocutmix",
-    "lengthcutmix", "datasetcutmix", "wavcutmix", "lc-nointrusion", "labelcutmix", "swapsysdia",
-    "cont-cutmix", "saliency-cutmix")
 # max_model_depth of the reference's 1D branch (augmentations.py:1484-1493) for the models served here
 LATENT_MAX_DEPTH_1D = {"Potes": 1, "resnet9": 3}
 
 
-@functools.lru_cache(maxsize=256)
 def latent_recipe(method: str):
     """``(p,)`` when the reference's 1D if-chain reaches its ``latentmixup`` branch for ``method``
-    (augmentations.py:1472-1506), None otherwise.  ``select_method`` keeps refusing the name: it
-    answers "which augmentation of the WAVEFORM runs", and every caller of it goes on to launch
-    one; latentmixup leaves the waveform alone and needs the model, so ``augment()`` and the
-    training step ask here first."""
-    if "latentmixup" not in method or any(n in method for n in _BEFORE_LATENT_1D):
-        return None
-    return (parse_probability(method),)
+    (augmentations.py:1472-1506), None otherwise.  latentmixup leaves the waveform alone and needs
+    the model, so it is a family of its own (``latent_plan``) and ``select_method`` refuses it."""
+    return (parse_probability(method),) if route(method, False).family == "latent" else None
 
 
 def latent_depth(model_name, step: int) -> int:
@@ -358,7 +403,7 @@ def latent_plan(method: str, model_name, labels, step: int, batch: int) -> MixPl
         latent_depth(model_name, step)                         # raises
     if not (recipe[0] >= 1.0 or gate_fires(method, step)):
         return MixPlan(fired=False, step=step)
-    plan = MixPlan(fired=True, name="latentmixup", step=step)
+    plan = MixPlan(fired=True, name="latentmixup", step=step, kind="latent")
     plan.mix = shuffle_within_groups(_host_labels(labels, batch).astype(np.int64, copy=False), step)
     plan.depth = latent_depth(model_name, step)
     plan.lam64, _ = draw_lambda_knots(step, 1.0, 0.0, 0)
@@ -369,12 +414,7 @@ def latent_plan(method: str, model_name, labels, step: int, batch: int) -> MixPl
 def soft_targets(method: str) -> bool:
     """True when a fired step blends the one-hot targets into floats: '(mixAll)' (augmentations.py:
     915-917, 978-980) and 'mixup(mix)' (:857).  A training step then needs the float targets."""
-    if "(mixAll)" in method:
-        return True
-    try:
-        return select_method(method, False) == "mixup" and "(same)" not in method
-    except NotImplementedError:
-        return False
+    return route(method, False).soft_targets
 
 
 def gate_fires(method: str, step: int) -> bool:
@@ -585,12 +625,13 @@ def make_plan(method: str, labels, frames: np.ndarray, wav: Sequence[str], step:
     callable lets rejected steps skip the sync.  ``sample_rate`` (``args.sample_rate``) and
     ``sig_len`` (T) are needed by respiratoryscale; timemask clips its spans to ``sig_len``.
     The 2D baselines need the image's F (``n_freq``) and W (``n_cols``); ``channels`` is then C."""
-    name = select_method(method, is2d)
+    r = _waveform_route(method, is2d)
+    name = r.branch
     if name is None or not gate_fires(method, step):
         return MixPlan(fired=False, step=step)
     if frames.shape[0] != batch:
         raise ValueError("labels/frames do not match the batch size")
-    plan = MixPlan(fired=True, name=name, step=step, is2d=is2d)
+    plan = MixPlan(fired=True, name=name, step=step, is2d=is2d, kind=_plan_kind(r, is2d))
     if is2d and plan.kind != "splice":
         if n_freq is None or n_cols <= 0:
             raise ValueError("2D baselines need make_plan(..., n_freq=F, n_cols=W)")
@@ -603,19 +644,14 @@ def make_plan(method: str, labels, frames: np.ndarray, wav: Sequence[str], step:
     # so the order BETWEEN the two streams is free — a callable `labels` that has to wait for the
     # GPU is asked as late as possible, after the ~0.1 ms of normal draws.
     alpha = 1.0 if is2d else parse_alpha(method, name)                      # augmentations2d.py:411
-    sigma, knot = parse_magwarp(method) if (not is2d and name == "durmixmagwarp") else (0.0, -2)
+    sigma, knot = parse_warp(method, name) if (not is2d and name == "durmixmagwarp") else (0.0, -2)
     # seed -> beta (augmentations.py:661-663) -> normal right behind it (:677)
     plan.lam64, knots = draw_lambda_knots(step, alpha, sigma, batch * (knot + 2) * channels)
     plan.lam32 = np.float32(plan.lam64)                                     # augmentations.py:903
     if knot + 2:
         plan.n_knots = knot + 2
         plan.knots = knots_array(knots, (batch, knot + 2, channels))
-    if callable(labels):
-        labels = labels()
-    labels = np.asarray(labels).reshape(-1)
-    if labels.shape[0] != batch:
-        raise ValueError("labels/frames do not match the batch size")
-    plan.mix = partner_indices(method, labels, wav, step, is2d)
+    plan.mix = partner_indices(method, _host_labels(labels, batch), wav, step, is2d)
     if is2d and name != "durratiomixup":
         plan.zero_rect = mask_rectangles(method, name, frames, step, channels, n_cols)
     if not is2d and "(rand)" in method and "(salopt" not in method:
@@ -623,12 +659,7 @@ def make_plan(method: str, labels, frames: np.ndarray, wav: Sequence[str], step:
     # saliency-guided placement: 1D augmentations.py:905-913; 2D only under durratiomixup
     # (augmentations2d.py:416-423 — the mask variants never look at '(salopt')
     if (not is2d or name == "durratiomixup") and "(salopt" in method:
-        if "(saloptenv" in method:
-            plan.salopt_mode = 0
-        elif "(saloptsum" in method:
-            plan.salopt_mode = 1
-        else:
-            raise NotImplementedError("only (saloptenv…) and (saloptsum…) exist in the reference")
+        plan.salopt_mode = _salopt_mode(method)
     if not is2d:
         plan.mix_all = "(mixAll)" in method
     return plan
@@ -642,11 +673,7 @@ def _baseline_plan(plan: MixPlan, method: str, labels, frames: np.ndarray, step:
         # get_lambda(alpha=1): np.random.seed(step); beta(1, 1) (augmentations.py:841, 851)
         plan.lam64, _ = draw_lambda_knots(step, 1.0, 0.0, 0)
         plan.lam32 = np.float32(plan.lam64)
-        if callable(labels):
-            labels = labels()
-        labels = np.asarray(labels).reshape(-1)
-        if labels.shape[0] != batch:
-            raise ValueError("labels/frames do not match the batch size")
+        labels = _host_labels(labels, batch)
         if "(same)" in method:                                    # augmentations.py:840
             plan.mix = shuffle_within_groups(labels.astype(np.int64, copy=False), step)
         else:                                                     # '(mix)', augmentations.py:850
@@ -667,7 +694,7 @@ def _baseline_plan(plan: MixPlan, method: str, labels, frames: np.ndarray, step:
     elif name == "respiratoryscale":
         if sample_rate is None or sig_len is None:
             raise ValueError("respiratoryscale needs make_plan(..., sample_rate=, sig_len=)")
-        plan.scale_row = respiration_row(method, step, int(sig_len), sample_rate)
+        plan.scale_row = respiration_row(parse_respscale(method), step, int(sig_len), sample_rate)
     return plan
 
 
@@ -795,85 +822,17 @@ def rand_keepdur_segments(frames: np.ndarray, mix: np.ndarray, off: np.ndarray, 
 
 
 # ---- the cut-and-paste family, durmixrespscale and bare cutout --------------------------------------
-# Names planned by ``cutpaste_plan`` (1D: augmentations.py:734, 983, 1101, 1121, 1153, 1184, 1285,
-# 1569; 2D: augmentations2d.py:429).
-CUTPASTE_METHODS_1D = ("durmixrespscale", "wav-durratiocutmix", "durratiocutmix", "lengthcutmix",
-                       "datasetcutmix", "wavcutmix", "labelcutmix", "cutout")
-CUTPASTE_METHODS_2D = ("cutout",)
 _KEEPDUR_1D = ("wav-durratiocutmix", "durratiocutmix")
-_CUTMIX_1D = ("lengthcutmix", "datasetcutmix", "wavcutmix", "labelcutmix")
 CUTPASTE_MAX_OVERLAP = 10          # PCGMIX_CUTPASTE_MAX_OVERLAP: cutmix_multidim_tensors' overlap=10
 
-# The reference's WHOLE 1D if-chain, in its order (augmentations.py:734 ... 1616); ``None`` marks a
-# branch that is somebody else's (served through select_method / latent_recipe, or refused).
-_FULL_CHAIN_1D = (
-    (_has("durmixrespscale"), "durmixrespscale"),                                        # :734
-    (_has("respiratoryscale"), None), (_has("timemask"), None),                          # :777, :807
-    (lambda m: "mixup" in m and "latentmixup" not in m and "durratiomixup" not in m, "mixup"),  # :829
-    (_has("durmixmagwarp"), None), (_has("durratiomixup"), None),                        # :864, :931
-    (_has("wav-durratiocutmix"), "wav-durratiocutmix"),                                  # :983
-    (_has("timewarp"), None), (_has("magnitudewarp"), None), (_has("gaussiannoise"), None),
-    (lambda m: "(UMC-subset)durratiocutmix" in m and "(plus)" not in m and "(plusplus)" not in m, None),
-    (lambda m: "durratiocutmix" in m and "(plus)" not in m and "(plusplus)" not in m
-     and "(UMC" not in m and "wav-durratiocutmix" not in m, "durratiocutmix"),           # :1101
-    (_has("lengthcutmix"), "lengthcutmix"), (_has("datasetcutmix"), "datasetcutmix"),    # :1121, :1153
-    (lambda m: "wavcutmix" in m and "durratiowavcutmix" not in m, "wavcutmix"),          # :1184
-    (_has("lc-nointrusion"), None),                                                      # :1215
-    (_has("labelcutmix"), "labelcutmix"),                                                # :1285
-    (_has("swapsysdia"), None), (_has("cont-cutmix"), None), (_has("saliency-cutmix"), None),
-    (_has("latentmixup"), None),                                                         # :1472
-    (lambda m: "cutmix" in m and "saliency" not in m and "label" not in m, None),        # :1508
-    (lambda m: "cutout" in m and "saliency" not in m, "cutout"),                         # :1569
-)
 
-
-@functools.lru_cache(maxsize=256)
 def cutpaste_recipe(method: str, is2d: bool = False) -> Optional[str]:
     """The branch name when the reference's if-chain reaches, for ``method``, one of the branches
     ``cutpaste_plan`` serves — the heart-cycle cut-and-paste methods, ``durmixrespscale`` and bare
     ``cutout`` in 1D (``CUTPASTE_METHODS_1D``), bare ``cutout`` in 2D — and None otherwise (an
-    earlier branch takes the string, or a later one, or none).  ``select_method`` keeps refusing
-    these names; ``augment()`` asks here first, as it does with ``latent_recipe``."""
-    if is2d:
-        if not any(n in method for n in _REFERENCE_METHODS_2D):
-            return None
-        for cond, name in _CHAIN_2D:
-            if cond(method):
-                return "cutout" if name == "cutout" else None
-        return None
-    if not any(n in method for n in _REFERENCE_METHODS_1D):
-        return None                                            # augmentations.py:731-732
-    for cond, name in _FULL_CHAIN_1D:
-        if not cond(method):
-            continue
-        if name == "mixup":                                    # falls through without a selector
-            if "(same)" in method or "(mix)" in method:
-                return None
-            continue
-        if name == "cutout" and "manifold" in method:          # needs max_depth: bound for FCN only
-            return None
-        return name
-    return None
-
-
-@functools.lru_cache(maxsize=256)
-def parse_durmixrespscale(method: str):
-    """'durmixrespscale(min,max)' -> (min, max) in Hz (augmentations.py:760-764): as
-    ``parse_respscale``, split on the branch's own name."""
-    lo, hi = 12 / 60, 20 / 60
-    parts = method.split("durmixrespscale(")
-    if len(parts) > 1:
-        lo = float(parts[1].split(",")[0]) / 60
-        hi = int(method.split(",")[1].split(")")[0]) / 60
-    return lo, hi
-
-
-def _respiration_row(lo: float, hi: float, step: int, sig_len: int, sample_rate) -> np.ndarray:
-    u = _lib.load().pcgmix_py_uniform01(int(step))
-    rate = lo + (hi - lo) * u
-    phase = 0 + (2 * np.pi - 0) * u
-    t = np.linspace(0, sig_len / sample_rate, sig_len)
-    return np.sin(2 * np.pi * rate * t + phase)
+    earlier branch takes the string, or a later one, or none)."""
+    r = route(method, is2d)
+    return r.branch if r.family == "cutpaste" else None
 
 
 @functools.lru_cache(maxsize=16)
@@ -972,27 +931,29 @@ def cutpaste_plan(method: str, labels, frames: np.ndarray, wav: Optional[Sequenc
     zero-argument callable (asked after the gate).  1D: ``sig_len`` = T; ``batch_size`` =
     ``args.batch_size`` (lengthcutmix), ``sample_rate`` = ``args.sample_rate`` (durmixrespscale).
     2D: ``n_freq`` = F, ``n_cols`` = W."""
-    name = cutpaste_recipe(method, is2d)
-    if name is None:
+    r = route(method, is2d)
+    if r.family != "cutpaste":
         raise ValueError(f"{method!r} reaches none of the branches cutpaste_plan serves")
+    name = r.branch
     if not gate_fires(method, step):
         return MixPlan(fired=False, step=step)
     frames = np.asarray(frames)
     if frames.ndim != 2 or frames.shape != (batch, 5):
         raise ValueError("labels/frames do not match the batch size")
-    plan = MixPlan(fired=True, name=name, step=step, is2d=is2d)
+    kind = "cutout2d" if is2d else name if name == "cutout" else \
+        "mixscale" if name == "durmixrespscale" else "cutpaste"
+    plan = MixPlan(fired=True, name=name, step=step, is2d=is2d, kind=kind)
     if is2d:                                                   # augmentations2d.py:429-459
         if n_freq is None or n_cols <= 0:
             raise ValueError("2D cutout needs cutpaste_plan(..., n_freq=F, n_cols=W)")
         rect = mask_rectangles(method, "durmixcutout", frames, step, int(n_freq), int(n_cols))
         rect[:, 2:] = np.clip(rect[:, 2:], 0, int(n_cols))     # the reference's slice clips
-        plan.zero_rect, plan.family = rect, "cutout2d"
+        plan.zero_rect = rect
         return plan
     if name == "cutout":                                       # :1569-1616
         per_ch = "(ch)" in method
         plan.spans = cutout_spans(frames, step, sig_len, channels, per_ch)
         plan.span_rows = channels if per_ch else 1
-        plan.family = "cutout"
         return plan
     _validate_cycles(frames, sig_len)
     f1 = frames.astype(np.int64, copy=False)
@@ -1007,11 +968,8 @@ def cutpaste_plan(method: str, labels, frames: np.ndarray, wav: Optional[Sequenc
         plan.lam32 = np.float32(plan.lam64)
         if "(rand)" in method:
             plan.rand_off = rand_offsets(f1, plan.mix, step)
-        lo, hi = parse_durmixrespscale(method)
-        plan.scale_row = _respiration_row(lo, hi, step, int(sig_len), sample_rate)
-        plan.family = "mixscale"
+        plan.scale_row = respiration_row(parse_respscale(method, name), step, int(sig_len), sample_rate)
         return plan
-    plan.family = "cutpaste"
     if wav is None and name in ("wav-durratiocutmix", "wavcutmix", "datasetcutmix"):
         raise ValueError(f"{name} groups the batch by recording: it needs wav")
     if name in ("wav-durratiocutmix", "wavcutmix"):            # get_same_wav_mix_indices, :528

@@ -456,22 +456,25 @@ LATENT_GRAPH_MESSAGE = ("latentmixup is not wired into the captured step: its pe
                         "lambda have no slot in the graph's static block; use train_step")
 
 
+def method_route(args):
+    """``hostprep.route`` of ``args.method`` for the data set's dimensionality."""
+    return augmentations.hostprep.route(args.method, args.dataset in SPECTROGRAM_DATASETS)
+
+
 def latent_method(args) -> bool:
     """True when ``args.method`` reaches the reference's 1D ``latentmixup`` branch on a time-series
-    dataset (``hostprep.latent_recipe``)."""
-    return args.dataset not in SPECTROGRAM_DATASETS \
-        and augmentations.hostprep.latent_recipe(args.method) is not None
+    dataset."""
+    return method_route(args).family == "latent"
 
 
 def cutpaste_method(args) -> bool:
-    """True when ``args.method`` reaches a branch of ``hostprep.cutpaste_recipe`` — the cut-and-paste
-    family, durmixrespscale, bare cutout: eager ``train_step`` only."""
-    return augmentations.hostprep.cutpaste_recipe(
-        args.method, args.dataset in SPECTROGRAM_DATASETS) is not None
+    """True when ``args.method`` reaches the cut-and-paste family, durmixrespscale or bare cutout:
+    eager ``train_step`` only."""
+    return method_route(args).family == "cutpaste"
 
 
 def cutpaste_graph_message(args) -> str:
-    return (f"method {args.method!r} ({augmentations.hostprep.cutpaste_recipe(args.method, False)}) is not "
+    return (f"method {args.method!r} ({method_route(args).branch}) is not "
             f"wired into the captured step: its per-step segment tables have no slot in the graph's "
             f"static block; use train_step")
 
@@ -616,7 +619,7 @@ class GraphedTrainStep:
         self._pay_t = self._payload[12 + n_lab:12 + n_lab + n_t].reshape(batch_size, args.num_classes)
         self._rows = np.arange(batch_size)
         self.labels_mode = bool(                               # same test as _fwd_bwd's
-            isinstance(self.ce, CELoss) and not augmentations.hostprep.soft_targets(args.method)
+            isinstance(self.ce, CELoss) and not method_route(args).soft_targets
             and args.num_classes <= 255
             and fused_loss_model(model, self.ce, self.x, self.t, None) is not None)
         self._pay_bytes = (12 + n_lab) * 4 if self.labels_mode else self._payload.nbytes
@@ -850,7 +853,7 @@ class GraphedTrainStep:
                     augmentations._salopt_step(srec, g, data, None, labels_np, frames_np, step,
                                                out=self.x)
         else:
-            if hostprep.select_method(args.method, False):
+            if method_route(args).family != "passthrough":
                 plan = hostprep.make_plan(args.method, labels_np, frames_np, wav, step, B, C,
                                           sample_rate=getattr(args, "sample_rate", None), sig_len=T)
             fired = plan.fired
