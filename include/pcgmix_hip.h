@@ -31,7 +31,7 @@ extern "C" {
  * language binding does not need the HIP headers). */
 typedef struct ihipStream_t* pcgmix_stream_t;
 
-#define PCGMIX_ABI_VERSION 21
+#define PCGMIX_ABI_VERSION 22
 
 /* ABI version of the loaded library (== PCGMIX_ABI_VERSION it was built with). */
 int pcgmix_abi_version(void);
@@ -752,6 +752,16 @@ int pcgmix_augment_plain_begin(pcgmix_ctx* ctx, const float* x, float* y, const 
                                int num_classes, int B, int C, int T, pcgmix_stream_t stream);
 int pcgmix_augment_plain_finish(pcgmix_ctx* ctx, const int64_t* frames, uint64_t step, float lam,
                                 int64_t* mix_out);
+/* begin with the step's boundaries (HOST int64 (B,5), the array finish will get) at hand: the kernel is
+ * told every sample's own cycle [frames[b,0], frames[b,4]) in its arguments and loads its own rows — and
+ * stores the elements outside the cycle, which are copies whatever partner is drawn — while it waits for
+ * the records.  Nothing is validated here (a sample whose edges are out of range is left to the records);
+ * finish reports malformed boundaries as before.  frames == NULL: as pcgmix_augment_plain_begin.  If finish
+ * is handed boundaries whose cycles reach outside the ones given here, it gives the kernel up and runs the
+ * step unarmed: same result.  pcgmix_augment_plain_f32 passes its boundaries the same way. */
+int pcgmix_augment_plain_begin_edges(pcgmix_ctx* ctx, const float* x, float* y, const int64_t* target_ohe_dev,
+                                     int num_classes, int B, int C, int T, const int64_t* frames,
+                                     pcgmix_stream_t stream);
 int pcgmix_ctx_armed_debug(pcgmix_ctx* ctx, unsigned long long timeout_ticks, int stall_ms);
 
 /* Diagnostic: mean host nanoseconds per pcgmix_augment_plain_f32 call since the last query, by

@@ -547,7 +547,8 @@ def splice_plain(recipe, data: torch.Tensor, labels, frames, step: int,
         ctx = _CTX.get(idx) or step_context(idx)
         if out is None:
             out = torch.empty_like(data)
-        err = lib.pcgmix_augment_plain_begin(ctx, data.data_ptr(), out.data_ptr(), ohe_ptr, n_cls, B, C, T, stream)
+        err = lib.pcgmix_augment_plain_begin_edges(ctx, data.data_ptr(), out.data_ptr(), ohe_ptr, n_cls, B, C, T,
+                                                   fr_ptr, stream)
         if err == 0:
             lam, _ = hostprep.draw_lambda_knots(step, alpha, sigma, 0)
             mix_buf, mix = _index_out(B)
@@ -556,7 +557,7 @@ def splice_plain(recipe, data: torch.Tensor, labels, frames, step: int,
                 _check_splice(err, "pcgmix_augment_plain_finish")
             return out, mix
         if err != _NOT_ARMED:
-            _lib.check(err, "pcgmix_augment_plain_begin")
+            _lib.check(err, "pcgmix_augment_plain_begin_edges")
     # numpy's global stream, as the reference: seed -> beta -> normal (c_float rounds lam like
     # np.float32, :903); the block was usually drawn ahead by the library (hostprep)
     lam, knots = hostprep.draw_lambda_knots(step, alpha, sigma, B * n_knots * C)

@@ -212,14 +212,17 @@ struct PyRandom {
     if (idx >= 624) regen();
   }
 
-  uint32_t next32() {
-    if (idx >= 624) regen();
-    uint32_t y = mt[idx++];
+  static uint32_t temper(uint32_t y) {
     y ^= (y >> 11);
     y ^= (y << 7) & 0x9d2c5680u;
     y ^= (y << 15) & 0xefc60000u;
     y ^= (y >> 18);
     return y;
+  }
+
+  uint32_t next32() {
+    if (idx >= 624) regen();
+    return temper(mt[idx++]);
   }
 
   double random() {  // 53-bit resolution, genrand_res53
@@ -244,6 +247,75 @@ struct PyRandom {
   }
 };
 
+// Random(seed) regenerated once, with its first block of 624 output words tempered into a flat array.  Every
+// label group of a step draws from a FRESH Random(step) (augmentations.py:500-514): the groups read `temp`
+// from index 0 instead of copying the 2.5 KB state and tempering word by word on the way.
+struct SeededBlock {
+  PyRandom st;               // twisted, idx == 0
+  uint32_t temp[624];        // temper(st.mt[i])
+  void make(uint64_t seed) {
+    new (&st) PyRandom(seed);
+    st.twist();
+    for (int i = 0; i < 624; ++i) temp[i] = PyRandom::temper(st.mt[i]);
+  }
+};
+
+// Random(seed).sample(members, k = n) -> out[0 .. n-1], bit-identical to Lib/random.py's pool branch
+//     for i in range(n): j = _randbelow(n - i); result[i] = pool[j]; pool[j] = pool[n - i - 1]
+// with _randbelow(m) = the first getrandbits(m.bit_length()) below m (one 32-bit word each: n < 2^31).
+// About 30 % of the words are rejected, unpredictably: the loop has no branch on the draw — a word
+// advances i by its accept bit, and a rejected one (r < 2^k <= 2 m <= 2 n) reads and rewrites a pool entry
+// that does not matter.  pool: scratch of 2 n entries.  A group that needs more than the block's 624 words
+// (in expectation at about 430 members) goes on with an ordinary generator from the stored state.
+void py_sample_all(const SeededBlock& sb, const int64_t* members, size_t n, int64_t* pool, int64_t* out) {
+  std::memcpy(pool, members, n * sizeof(int64_t));
+  std::memset(pool + n, 0, n * sizeof(int64_t));
+  size_t i = 0;
+  int pos = 0;
+  while (i < n && pos < 624) {
+    const uint64_t m = n - i;
+    const uint64_t r = sb.temp[pos++] >> (__builtin_clzll(m) - 32);      // getrandbits(m.bit_length())
+    const int64_t acc = (int64_t)(r < m);
+    const int64_t at = pool[r], last = pool[m - 1];
+    out[i] = at;
+    pool[r] = at ^ ((at ^ last) & -acc);
+    i += (size_t)acc;
+  }
+  if (i < n) {
+    PyRandom g = sb.st;
+    g.idx = 624;                                     // the block is used up: regenerate on the next word
+    for (; i < n; ++i) {
+      const uint64_t m = n - i, j = g.randbelow(m);
+      out[i] = pool[j];
+      pool[j] = pool[m - 1];
+    }
+  }
+}
+
+// Members of every group in ascending order, group after group, in ONE pass over the batch behind a count:
+// start[g] .. start[g + 1] of `order`.  gid[b] in [0, n_groups).
+void group_members(const int* gid, int B, int n_groups, std::vector<int64_t>& order, std::vector<size_t>& start) {
+  start.assign((size_t)n_groups + 1, 0);
+  for (int b = 0; b < B; ++b) ++start[(size_t)gid[b] + 1];
+  for (int g = 0; g < n_groups; ++g) start[(size_t)g + 1] += start[(size_t)g];
+  order.resize((size_t)B);
+  std::vector<size_t> fill(start.begin(), start.end() - 1);
+  for (int b = 0; b < B; ++b) order[fill[(size_t)gid[b]]++] = b;
+}
+
+// groups of equal key in order of first appearance (augmentations.py:500-510): gid[b], returns their number
+int group_ids(const int64_t* keys_in, int B, std::vector<int64_t>& keys, std::vector<int>& gid) {
+  keys.clear();
+  gid.resize((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    size_t g = 0;
+    while (g < keys.size() && keys[g] != keys_in[b]) ++g;
+    if (g == keys.size()) keys.push_back(keys_in[b]);
+    gid[(size_t)b] = (int)g;
+  }
+  return (int)keys.size();
+}
+
 }  // namespace
 
 extern "C" double pcgmix_py_uniform01(uint64_t seed) {
@@ -260,25 +332,20 @@ extern "C" int64_t pcgmix_py_randint0(uint64_t seed, int64_t hi) {
 extern "C" int pcgmix_partner_permutation_i64(const int32_t* group_id, int B, int n_groups,
                                               uint64_t seed, int64_t* mix) {
   if (!group_id || !mix || B < 0 || n_groups < 0) return hipErrorInvalidValue;
-  std::vector<std::vector<int64_t>> members((size_t)n_groups);
-  for (int b = 0; b < B; ++b) {
-    const int g = group_id[b];
-    if (g < 0 || g >= n_groups) return hipErrorInvalidValue;
-    members[(size_t)g].push_back(b);
+  for (int b = 0; b < B; ++b)
+    if (group_id[b] < 0 || group_id[b] >= n_groups) return hipErrorInvalidValue;
+  std::vector<int64_t> order, pool((size_t)2 * B + 2), perm((size_t)B + 1);
+  std::vector<size_t> start;
+  group_members(group_id, B, n_groups, order, start);
+  SeededBlock* sb = static_cast<SeededBlock*>(::operator new(sizeof(SeededBlock)));
+  sb->make(seed);                                   // a fresh Random(seed) per group, as the reference
+  for (int g = 0; g < n_groups; ++g) {
+    const size_t n = start[(size_t)g + 1] - start[(size_t)g];
+    const int64_t* idx = order.data() + start[(size_t)g];
+    py_sample_all(*sb, idx, n, pool.data(), perm.data());
+    for (size_t i = 0; i < n; ++i) mix[idx[i]] = perm[i];
   }
-  std::vector<int64_t> pool;
-  for (const auto& idx : members) {
-    const size_t n = idx.size();
-    if (!n) continue;
-    PyRandom rng(seed);  // a fresh Random(seed) per group, as the reference
-    pool = idx;
-    // sample(population, k = n): pool branch of Lib/random.py
-    for (size_t i = 0; i < n; ++i) {
-      const uint64_t j = rng.randbelow((uint64_t)(n - i));
-      mix[idx[i]] = pool[j];
-      pool[j] = pool[n - i - 1];
-    }
-  }
+  ::operator delete(sb);
   return hipSuccess;
 }
 
@@ -339,30 +406,12 @@ extern "C" int pcgmix_splice_same_label_f32(const float* x, float* y, const int6
   if (!x || !y || !labels || !frames || !staging || !dev_idx || !mix_out || B <= 0 || C <= 0 ||
       T <= 0 || (knots && (!spline_op || n_knots < 2)))
     return hipErrorInvalidValue;
-  // groups of equal label in order of first appearance (augmentations.py:500-510)
-  std::vector<int64_t> keys;
-  std::vector<std::vector<int64_t>> members;
-  for (int b = 0; b < B; ++b) {
-    size_t g = 0;
-    while (g < keys.size() && keys[g] != labels[b]) ++g;
-    if (g == keys.size()) {
-      keys.push_back(labels[b]);
-      members.emplace_back();
-    }
-    members[g].push_back(b);
-  }
-  // a fresh Random(step) per group: initialise the generator once, copy its state per group
-  const PyRandom seeded(step);
-  std::vector<int64_t> pool;
-  for (const auto& idx : members) {
-    const size_t n = idx.size();
-    PyRandom rng = seeded;
-    pool = idx;
-    for (size_t i = 0; i < n; ++i) {                 // sample(population, k = n): pool branch
-      const uint64_t j = rng.randbelow((uint64_t)(n - i));
-      mix_out[idx[i]] = pool[j];
-      pool[j] = pool[n - i - 1];
-    }
+  {
+    std::vector<int64_t> keys;
+    std::vector<int> gid;
+    const int n_groups = group_ids(labels, B, keys, gid);
+    const int perr = pcgmix_partner_permutation_i64(gid.data(), B, n_groups, step, mix_out);
+    if (perr) return perr;
   }
   int32_t* st = static_cast<int32_t*>(staging);
   const int perr = pcgmix_pack_plan_i32(frames, mix_out, nullptr, nullptr, B, T, st);
@@ -560,9 +609,10 @@ struct pcgmix_ctx {
   uint32_t token = 0;
   std::map<std::pair<int, int>, double*> ops;   // (T, n_knots) -> device operator
   uint64_t gate_step = ~0ull;      // generator seeded for this step (pcgmix_ctx_gate), reusable
-  PyRandom* seeded = nullptr;
-  std::vector<int64_t> keys, pool, idx;   // per-step scratch of the partner draw
+  SeededBlock* seeded = nullptr;
+  std::vector<int64_t> keys, pool, idx, perm;   // per-step scratch of the partner draw
   std::vector<int> gid;
+  std::vector<size_t> gstart;
   std::vector<char> payload;       // pcgmix_ctx_set_payload: rides with the next index block
   void* payload_dst = nullptr;
   void* ws = nullptr;              // displacement-search workspace of the saliency-guided step
@@ -582,6 +632,8 @@ struct pcgmix_ctx {
     float* y = nullptr;
     int B = 0, C = 0, T = 0, my_slot = 0;
     hipStream_t s = nullptr;
+    bool edges = false;                  // the plain kernel was given the own cycle edges (EdgePack):
+    uint32_t edge_w[pcgmix::kPackB];     //   what it got, lo | hi << 16 per sample
   } armed_open;
   hipStream_t armed_stream = nullptr;    // stream of the last armed launch
   bool armed_any = false;
@@ -596,7 +648,7 @@ struct pcgmix_ctx {
     std::atomic<int> job{0};          // 0 idle | 1 posted | 2 done
     std::atomic<bool> quit{false};
     uint64_t step = 0;
-    PyRandom* state = nullptr;
+    SeededBlock* state = nullptr;
     int fork_generation = 0;       // of the process that started the helper
     long long hits = 0, misses = 0;
   } ahead;
@@ -643,8 +695,7 @@ void seed_ahead_run(pcgmix_ctx* c) {
       a.cv.wait(lk, [&] { return a.job.load(std::memory_order_acquire) == 1 || a.quit.load(); });
     }
     if (a.quit.load()) return;
-    new (a.state) PyRandom(a.step);
-    a.state->twist();
+    a.state->make(a.step);
     a.job.store(2, std::memory_order_release);
   }
 }
@@ -658,14 +709,13 @@ void seed_for_step(pcgmix_ctx* c, uint64_t step) {
       a.job.load(std::memory_order_acquire) != 0) {
     while (a.job.load(std::memory_order_acquire) == 1) _mm_pause();      // <= one seeding
     have = a.step == step;
-    if (have) std::memcpy(static_cast<void*>(c->seeded), a.state, sizeof(PyRandom));
+    if (have) std::swap(c->seeded, a.state);       // (the helper touches a.state only between job 1 and 2)
     a.job.store(0, std::memory_order_relaxed);
   }
   if (have) {
     ++a.hits;
   } else {
-    new (c->seeded) PyRandom(step);
-    c->seeded->twist();
+    c->seeded->make(step);
     ++a.misses;
   }
   c->gate_step = step;
@@ -679,7 +729,7 @@ void seed_ahead_post(pcgmix_ctx* c, uint64_t step) {
   if (!a.state) {
     static const int once = pthread_atfork(nullptr, nullptr, ctx_mark_forked);
     (void)once;
-    a.state = static_cast<PyRandom*>(::operator new(sizeof(PyRandom)));
+    a.state = static_cast<SeededBlock*>(::operator new(sizeof(SeededBlock)));
     a.fork_generation = g_ctx_fork_generation.load(std::memory_order_relaxed);
     a.th = std::thread([c] { seed_ahead_run(c); });
   }
@@ -701,7 +751,7 @@ extern "C" int pcgmix_ctx_create(int device, pcgmix_ctx** out) {
   if ((e = hipSetDevice(device)) != hipSuccess) return (int)e;
   pcgmix_ctx* c = new pcgmix_ctx();
   c->device = device;
-  c->seeded = static_cast<PyRandom*>(::operator new(sizeof(PyRandom)));
+  c->seeded = static_cast<SeededBlock*>(::operator new(sizeof(SeededBlock)));
   e = hipHostMalloc(reinterpret_cast<void**>(&c->flag), 64, hipHostMallocMapped | hipHostMallocCoherent);
   if (e == hipSuccess) {
     std::memset(c->flag, 0, 64);       // word 0: label token, word 8: abort word of the armed step
@@ -754,7 +804,7 @@ extern "C" void pcgmix_ctx_destroy(pcgmix_ctx* c) {
 extern "C" double pcgmix_ctx_gate(pcgmix_ctx* c, uint64_t step) {
   if (!c) return 2.0;
   seed_for_step(c, step);
-  PyRandom r = *c->seeded;
+  PyRandom r = c->seeded->st;
   return 0.0 + (1.0 - 0.0) * r.random();
 }
 
@@ -892,33 +942,24 @@ int pack_frames16(const int64_t* frames, int B, int T, int16_t* fr16) {
 }
 
 // Groups of equal label in order of first appearance (augmentations.py:500-510), each permuted by
-// a fresh Random(step).sample: one initialisation (c->seeded), state copied per group.  Scratch
+// a fresh Random(step).sample: one initialisation (c->seeded, its first block tempered), read per group.  Scratch
 // lives in the context (no allocation per step): gid[b] = group of sample b, members of group g =
 // the samples b with gid[b] == g in ascending order.
 void draw_partners(pcgmix_ctx* c, const int64_t* labels, int B, int64_t* mix_out, int32_t* mixp,
                    int16_t* mixp16 = nullptr) {
-  c->keys.clear();
-  c->gid.resize((size_t)B);
-  c->pool.resize((size_t)B);
-  c->idx.resize((size_t)B);
-  for (int b = 0; b < B; ++b) {
-    size_t g = 0;
-    while (g < c->keys.size() && c->keys[g] != labels[b]) ++g;
-    if (g == c->keys.size()) c->keys.push_back(labels[b]);
-    c->gid[(size_t)b] = (int)g;
-  }
-  for (size_t g = 0; g < c->keys.size(); ++g) {
-    size_t n = 0;
-    for (int b = 0; b < B; ++b)
-      if (c->gid[(size_t)b] == (int)g) c->idx[n++] = b;
-    PyRandom rng = *c->seeded;
-    std::memcpy(c->pool.data(), c->idx.data(), n * sizeof(int64_t));
-    for (size_t i = 0; i < n; ++i) {                 // sample(population, k = n): pool branch
-      const uint64_t j = rng.randbelow((uint64_t)(n - i));
-      mix_out[c->idx[i]] = c->pool[j];
-      if (mixp16) mixp16[c->idx[i]] = (int16_t)c->pool[j];
-      else mixp[c->idx[i]] = (int32_t)c->pool[j];
-      c->pool[j] = c->pool[n - i - 1];
+  const int n_groups = group_ids(labels, B, c->keys, c->gid);
+  group_members(c->gid.data(), B, n_groups, c->idx, c->gstart);
+  c->pool.resize((size_t)2 * B + 2);
+  c->perm.resize((size_t)B + 1);
+  for (int g = 0; g < n_groups; ++g) {
+    const size_t n = c->gstart[(size_t)g + 1] - c->gstart[(size_t)g];
+    const int64_t* idx = c->idx.data() + c->gstart[(size_t)g];
+    py_sample_all(*c->seeded, idx, n, c->pool.data(), c->perm.data());
+    for (size_t i = 0; i < n; ++i) {
+      const int64_t v = c->perm[i];
+      mix_out[idx[i]] = v;
+      if (mixp16) mixp16[idx[i]] = (int16_t)v;
+      else mixp[idx[i]] = (int32_t)v;
     }
   }
 }
@@ -1226,8 +1267,9 @@ int armed_begin(PlainStep& p, bool arm_warp) {
                                              reinterpret_cast<double*>(sl.dev), op_dev, p.n_knots, B, C, T, s,
                                              c->payload.data(), (int)c->payload.size(), c->payload_dst)
                : pcgmix::launch_mix_armed(p.x, p.y, a, B, C, T, s, c->payload.data(), (int)c->payload.size(),
-                                          c->payload_dst);
+                                          c->payload_dst, p.frames, o.edge_w);
   if (err) return err;
+  o.edges = !arm_warp && p.frames != nullptr;
   c->armed_stream = s;
   c->armed_any = true;
   c->payload.clear();                        // (it travelled in the launch's arguments)
@@ -1254,6 +1296,12 @@ int armed_finish(PlainStep& p) {
   o.open = false;
   int16_t fr16[pcgmix::kPackB * 5], mix16[pcgmix::kPackB];
   const int bad16 = pack_frames16(p.frames, B, T, fr16);
+  // The kernel has stored what lies outside the cycles it was launched with: the records must not blend
+  // there.  (A caller that hands finish other boundaries than begin — the binding never does.)
+  int moved = 0;
+  if (o.edges && !bad16)
+    for (int b = 0; b < B; ++b)
+      moved |= (int)(fr16[b * 5] < (int)(o.edge_w[b] & 0xffffu)) | (int)(fr16[b * 5 + 4] > (int)(o.edge_w[b] >> 16));
   p.lap(1);
   seed_for_step(c, p.step);
   p.lap(2);
@@ -1264,6 +1312,12 @@ int armed_finish(PlainStep& p) {
     return bad16 ? bad16 : (int)e;
   }
   p.lap(3);
+  if (moved) {                               // give the kernel up; the unarmed splice rewrites all of y behind it
+    armed_write(c, o.seq | pcgmix::kArmedAbort, nullptr, nullptr, B);
+    ++c->armed_aborted;
+    return pcgmix_augment_plain_f32(c, o.x, o.y, nullptr, 0, lab64a, p.frames, p.step, p.lam, nullptr, 0,
+                                    p.mix_out, B, C, T, reinterpret_cast<pcgmix_stream_t>(s));
+  }
   draw_partners(c, lab64a, B, p.mix_out, nullptr, mix16);
   p.lap(4);
   if (c->armed_stall_ms > 0) {
@@ -1472,9 +1526,9 @@ extern "C" int pcgmix_augment_plain_f32(pcgmix_ctx* c, const float* x, float* y,
 // The armed plain step in two calls, for a caller that has host work of its own between the launch and the
 // moment lambda is known (the Python binding draws lambda from numpy's stream there): begin = validation,
 // eligibility, the launch; finish = boundaries, labels, partners, records.
-extern "C" int pcgmix_augment_plain_begin(pcgmix_ctx* c, const float* x, float* y,
-                                          const int64_t* target_ohe_dev, int num_classes, int B, int C,
-                                          int T, pcgmix_stream_t stream) {
+extern "C" int pcgmix_augment_plain_begin_edges(pcgmix_ctx* c, const float* x, float* y,
+                                                const int64_t* target_ohe_dev, int num_classes, int B, int C,
+                                                int T, const int64_t* frames, pcgmix_stream_t stream) {
   if (!c || !x || !y || !target_ohe_dev || num_classes <= 0 || B <= 0 || C <= 0 || T <= 0)
     return hipErrorInvalidValue;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -1487,9 +1541,15 @@ extern "C" int pcgmix_augment_plain_begin(pcgmix_ctx* c, const float* x, float* 
     return PCGMIX_NOT_ARMED;
   DeviceGuard guard(c->device);
   if (guard.err != hipSuccess) return (int)guard.err;
-  PlainStep p{c, x, y, target_ohe_dev, num_classes, nullptr, nullptr, 0, 0.f, nullptr, 0, nullptr,
+  PlainStep p{c, x, y, target_ohe_dev, num_classes, nullptr, frames, 0, 0.f, nullptr, 0, nullptr,
               B, C, T, s, stream, std::chrono::steady_clock::now()};
   return armed_begin(p, false);
+}
+
+extern "C" int pcgmix_augment_plain_begin(pcgmix_ctx* c, const float* x, float* y,
+                                          const int64_t* target_ohe_dev, int num_classes, int B, int C,
+                                          int T, pcgmix_stream_t stream) {
+  return pcgmix_augment_plain_begin_edges(c, x, y, target_ohe_dev, num_classes, B, C, T, nullptr, stream);
 }
 
 extern "C" int pcgmix_augment_plain_finish(pcgmix_ctx* c, const int64_t* frames, uint64_t step, float lam,

@@ -87,7 +87,8 @@ int launch_mix_karg(const float* x, float* y, const int16_t* frames16, const int
 // (float bits) for the plain launch, which may be made before lambda is drawn.
 // stamp | kArmedAbort in a record = "give up": written by the host (bad input after the launch) or
 // by a relay that saw nothing within timeout_ticks of the 100 MHz clock (then also *abort_h = seq);
-// every wave leaves without touching y.
+// every wave leaves `y` partly written (the plain kernel has stored the elements that do not depend on the
+// record by then, see EdgePack; the splice + warp kernel has stored nothing).
 constexpr uint32_t kArmedAbort = 0x80000000u;
 constexpr int kArmedRecWords = 8;            // 64 bytes per sample: six index words, lambda, (device) knots-ready
 struct ArmedArgs {
@@ -101,8 +102,23 @@ struct ArmedArgs {
   uint32_t seq;                              // 1 .. 0x7fffffff
   unsigned long long timeout_ticks;
 };
+// Own cycle [lo, hi) = [frames[b,0], frames[b,4]) of every sample as two int16 in one dword (lo | hi << 16),
+// BY VALUE in the plain armed kernel's arguments: known on the host when the kernel is launched, and all the
+// kernel needs to tell which output elements are plain copies of the own row whatever partner is drawn (the
+// blended ranges lie inside the own cycle).  Those are loaded and stored BEFORE the wait for the record;
+// the own values of the others are loaded before it and kept.  n == 0: edges unknown, every element waits.
+struct EdgePack {
+  uint32_t w[kPackB];
+  int n;
+};
+// Own quads a lane of the plain armed kernel holds in registers across the wait (16 VGPRs).
+constexpr int kArmedHold = 4;
+// frames_host: the (B,5) int64 boundaries on the host, or nullptr (no early phase).  A sample whose
+// edges are not 0 <= lo <= hi <= T gets [0, T): nothing of it is stored early.  edges_out (kPackB words):
+// the dwords the kernel got, for the caller to hold the records against.
 int launch_mix_armed(const float* x, float* y, const ArmedArgs& a, int B, int C, int T, hipStream_t s,
-                     const void* pay = nullptr, int pay_bytes = 0, void* pay_dst = nullptr);
+                     const void* pay = nullptr, int pay_bytes = 0, void* pay_dst = nullptr,
+                     const int64_t* frames_host = nullptr, uint32_t* edges_out = nullptr);
 // The same for the splice + warp kernel (durmixmagwarp): knots_host = this step's knots (B, n_knots, C)
 // float64 in device-readable pinned memory, knots_dev = device scratch of the same size (each sample's
 // relay copies its knots there once), spline_op the constant operator on the device.
@@ -233,6 +249,47 @@ __device__ __forceinline__ int blend_shift(const StateMap& sm, int t, bool& hit)
 __device__ __forceinline__ float blend(float own, float other, float lam, float oml) {
   // x*lam + partner*(1-lam) as three separately rounded fp32 ops (augmentations.py:294)
   return __fadd_rn(__fmul_rn(own, lam), __fmul_rn(other, oml));
+}
+
+// One quad of sample positions t0 .. t0+3 of a row against the blended ranges.  The partner quad is
+// fetched with ONE unaligned 16-byte load at the shift of the first blended element, from src0 (clamped
+// into the row).  Returned mask: bit e = element e blends; bit 4+e = element e blends with a different
+// shift (a state boundary inside the quad) or the quad load had to be clamped: patched by a scalar load.
+__device__ __forceinline__ int quad_plan(const StateMap& sm, int t0, int T, int& src0) {
+  bool hit[4];
+  int d[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) d[e] = blend_shift(sm, t0 + e, hit[e]);
+  const int dsel = hit[0] ? d[0] : hit[1] ? d[1] : hit[2] ? d[2] : hit[3] ? d[3] : 0;
+  src0 = t0 + dsel;
+  src0 = src0 < 0 ? 0 : (src0 > T - 4 ? T - 4 : src0);
+  const bool clamped = src0 != t0 + dsel;
+  int mask = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (hit[e]) mask |= 1 << e;
+    if (hit[e] && (clamped || d[e] != dsel)) mask |= 16 << e;
+  }
+  return mask;
+}
+
+// The quad's four output elements from the own quad, the partner quad quad_plan asked for and its mask;
+// par_row = the partner's row (x + partner base + c * T).
+__device__ __forceinline__ void quad_blend(float (&out)[4], const float4_a& own, const float4_u& par,
+                                           const float* __restrict__ par_row, const StateMap& sm, int t0,
+                                           int mask, float lam, float oml) {
+  const float o[4] = {own.x, own.y, own.z, own.w};
+  const float pv[4] = {par.x, par.y, par.z, par.w};
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    float v = pv[e];
+    if (mask & (16 << e)) {  // rare: patch with the element's own shift
+      bool h;
+      const int de = blend_shift(sm, t0 + e, h);
+      v = par_row[t0 + e + de];
+    }
+    out[e] = (mask & (1 << e)) ? blend(o[e], v, lam, oml) : o[e];
+  }
 }
 
 // pcgmix_saliency.hip: the displacement search of pcgmix_salopt_disp_f32; disp == nullptr leaves

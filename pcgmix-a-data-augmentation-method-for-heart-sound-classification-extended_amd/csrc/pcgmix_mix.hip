@@ -143,20 +143,8 @@ __device__ __forceinline__ void mix_body(
       const int ii = valid ? i : 0;
       const int c = ii / T;
       const int t0 = ii - c * T;
-      bool hit[4];
-      int d[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) d[e] = blend_shift(sm, t0 + e, hit[e]);
-      const int dsel = hit[0] ? d[0] : hit[1] ? d[1] : hit[2] ? d[2] : hit[3] ? d[3] : 0;
-      int src0 = t0 + dsel;
-      src0 = src0 < 0 ? 0 : (src0 > T - 4 ? T - 4 : src0);
-      const bool clamped = src0 != t0 + dsel;
-      int mask = valid ? 0x100 : 0;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (hit[e]) mask |= 1 << e;
-        if (hit[e] && (clamped || d[e] != dsel)) mask |= 16 << e;
-      }
+      int src0;
+      const int mask = (valid ? 0x100 : 0) | quad_plan(sm, t0, T, src0);
       own[q] = *reinterpret_cast<const float4_a*>(x + own_base + ii);
       // The zero-padded tail and the unmatched part of longer states never touch the partner row —
       // but the load is NOT predicated: `if (mask & 0xf) pz = *p` compiles to a branch around the load
@@ -179,19 +167,8 @@ __device__ __forceinline__ void mix_body(
       const int mask = masks[q];
       if (!(mask & 0x100)) continue;
       const int t0 = t0s[q], c = cs[q];
-      float o[4] = {own[q].x, own[q].y, own[q].z, own[q].w};
-      float pv[4] = {par[q].x, par[q].y, par[q].z, par[q].w};
       float out[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float v = pv[e];
-        if (mask & (16 << e)) {  // rare: patch with the element's own shift
-          bool h;
-          const int de = blend_shift(sm, t0 + e, h);
-          v = x[par_base + (size_t)c * T + t0 + e + de];
-        }
-        out[e] = (mask & (1 << e)) ? blend(o[e], v, lam, oml) : o[e];
-      }
+      quad_blend(out, own[q], par[q], x + par_base + (size_t)c * T, sm, t0, mask, lam, oml);
       if (WARP) spline_apply<4>(out, lds + (size_t)(c - c_lo) * rec_per_ch, thr, n_knots, t0);
       if (c >= zr0 && c < zr1) {
 #pragma unroll
@@ -534,8 +511,9 @@ __global__ __launch_bounds__(kThreads) void mix_warp_karg_kernel(
 // The plain splice armed before its index block exists (pcgmix_kernels.h, ArmedArgs).
 #ifdef PCGMIX_PHASE_CLOCK
 // probe build: per launch parity (seq & 1) and sample: block (0,b) entry | relay saw the host's record |
-// block (1,b) saw the relayed record | block (1,b) done; [..][kPackB] = block (0,0): entry | labels flagged
-__device__ long long g_armed_clock[2][kPackB + 1][4];
+// block (1,b) saw the relayed record | block (1,b) done | block (1,b) early phase done (plain kernel);
+// [..][kPackB] = block (0,0): entry | labels flagged
+__device__ long long g_armed_clock[2][kPackB + 1][8];
 #define PCGMIX_ACLOCK(b, i) g_armed_clock[a.seq & 1][b][i] = (long long)wall_clock64()
 #else
 #define PCGMIX_ACLOCK(b, i)
@@ -543,8 +521,7 @@ __device__ long long g_armed_clock[2][kPackB + 1][4];
 template <int U>
 __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
     const float* __restrict__ x, float* __restrict__ y, const ArmedArgs a, int B, int C, int T, int epb,
-    int chunks, const PayPack pay, uint4* __restrict__ pay_dst) {
-  extern __shared__ __align__(16) double lds[];
+    int chunks, const PayPack pay, uint4* __restrict__ pay_dst, const EdgePack edges) {
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63;
   if ((blockIdx.x | blockIdx.y) == 0) {
@@ -561,9 +538,73 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
   }
   if (b >= B) return;
   const unsigned long long t0 = wall_clock64();
+  if (blockIdx.x == 0 && threadIdx.x == 0) { PCGMIX_ACLOCK(b, 0); }
+  // ---- early phase: what does not depend on the record.  A quad of positions entirely outside the own
+  // cycle [elo, ehi) is a copy of the own quad whatever partner is drawn: loaded and stored here, final.
+  // The own quads of the others are loaded here and held across the wait — kArmedHold of them per lane
+  // (the block's first kArmedHold / U chunks); a block that owns more chunks stores their final quads
+  // here as well and loads the rest behind the record.  Every element is stored exactly once: the late
+  // phase skips the final quads by the same test.
+  const int plane = C * T;
+  const size_t own_base = (size_t)b * plane;
+  const int lane_off = (int)threadIdx.x * 4;
+  int elo = 0, ehi = T;
+  if (edges.n) {
+    const uint32_t ew = edges.w[b];
+    elo = (int)(ew & 0xffffu);
+    ehi = (int)(ew >> 16);
+  }
+  auto is_final = [&](int tq) { return tq + 4 <= elo || tq >= ehi; };
+  // (U = 1 is for planes below 8,192 elements: at most 8 chunks per sample, the grid holds them all, one each)
+  constexpr int KJ = U == 1 ? 1 : kArmedHold / U;
+  float4_a own[kArmedHold];
+  int t0s[kArmedHold];                           // row position of the quad; -1: nothing left to do behind the record
+#pragma unroll
+  for (int j = 0; j < KJ; ++j) {
+    const int chunk = (int)blockIdx.x + j * (int)gridDim.x;
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      const int i = chunk < chunks ? chunk * epb + q * kThreads * 4 + lane_off : plane;
+      const bool valid = i < plane;
+      const int ii = valid ? i : 0;
+      own[j * U + q] = *reinterpret_cast<const float4_a*>(x + own_base + ii);
+      t0s[j * U + q] = valid ? ii - (ii / T) * T : -1;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < KJ; ++j) {
+    const int chunk = (int)blockIdx.x + j * (int)gridDim.x;
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      const int sl = j * U + q;
+      if (t0s[sl] >= 0 && is_final(t0s[sl])) {
+        __builtin_nontemporal_store(own[sl], reinterpret_cast<float4_a*>(y + own_base + chunk * epb +
+                                                                         q * kThreads * 4 + lane_off));
+        t0s[sl] = -1;
+      }
+    }
+  }
+  for (int chunk = (int)blockIdx.x + KJ * (int)gridDim.x; chunk < chunks; chunk += (int)gridDim.x) {
+    float4_a v[U];
+    bool fin[U];
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      const int i = chunk * epb + q * kThreads * 4 + lane_off;
+      fin[q] = i < plane && is_final(i - (i / T) * T);
+      // not predicated (mix_body, phase 1): a lane without a final quad reads the sample's first quad
+      size_t off = fin[q] ? own_base + i : own_base;
+      asm volatile("" : "+v"(off));
+      v[q] = *reinterpret_cast<const float4_a*>(x + off);
+    }
+#pragma unroll
+    for (int q = 0; q < U; ++q)
+      if (fin[q])
+        __builtin_nontemporal_store(v[q], reinterpret_cast<float4_a*>(y + own_base + chunk * epb +
+                                                                      q * kThreads * 4 + lane_off));
+  }
+  if (blockIdx.x == 1 && threadIdx.x == 0) { PCGMIX_ACLOCK(b, 4); }
   const uint32_t go = a.seq, stop = a.seq | kArmedAbort;
   const int word = lane < 7 ? lane : 6;          // six index words and lambda (word 6: float bits)
-  if (blockIdx.x == 0 && threadIdx.x == 0) { PCGMIX_ACLOCK(b, 0); }
   if (blockIdx.x == 0 && threadIdx.x < 64) {     // this sample's relay: host record -> device record
     const unsigned long long* src = a.rec_h + (size_t)b * kArmedRecWords + word;
     unsigned long long w;
@@ -623,12 +664,85 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
     sm.n[k] = n;
     sm.delta[k] = s - a0;
   }
-  // two chunks of the sample per block: (256,4,5000) is 2,560 chunks, more blocks than the chip holds at
-  // once (2,048 of four waves) — the last fifth would start, and begin to wait, when the first ones leave
+  // ---- late phase: the quads that are not final.  (Two chunks of the sample per block at (256,4,5000):
+  // 2,560 chunks are more blocks than the chip holds at once — 2,048 of four waves — and the last fifth
+  // would start, and begin to wait, when the first ones leave.)
   // lambda travels with the record: a caller may launch before it has drawn it (pcgmix_augment_plain_begin)
   const float lam = __int_as_float(lam_bits), oml = 1.0f - lam;
-  for (int chunk = blockIdx.x; chunk < chunks; chunk += gridDim.x)
-    mix_body<4, false, U>(x, y, lam, oml, nullptr, nullptr, 0, nullptr, C, T, epb, b, m, sm, lds, chunk);
+  const size_t par_base = (size_t)m * plane;
+  // held quads: the own values are in registers — ONE memory round trip, all partner loads of the lane in
+  // flight together.  A quad without a blended element (the unmatched part of a longer state) is stored
+  // as it is, without a load.
+  float4_u par[kArmedHold];
+  int masks[kArmedHold];
+#pragma unroll
+  for (int j = 0; j < KJ; ++j) {
+    const int chunk = (int)blockIdx.x + j * (int)gridDim.x;
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      const int sl = j * U + q;
+      masks[sl] = 0;
+      if (t0s[sl] >= 0) {
+        int src0;
+        masks[sl] = quad_plan(sm, t0s[sl], T, src0);
+        if (masks[sl] & 0xf) {
+          const int row = chunk * epb + q * kThreads * 4 + lane_off - t0s[sl];   // c * T
+          par[sl] = *reinterpret_cast<const float4_u*>(x + par_base + row + src0);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < KJ; ++j) {
+    const int chunk = (int)blockIdx.x + j * (int)gridDim.x;
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      const int sl = j * U + q;
+      if (t0s[sl] < 0) continue;
+      const int i = chunk * epb + q * kThreads * 4 + lane_off;
+      float4_a v = own[sl];
+      if (masks[sl] & 0xf) {
+        float out[4];
+        quad_blend(out, own[sl], par[sl], x + par_base + (i - t0s[sl]), sm, t0s[sl], masks[sl], lam, oml);
+        v.x = out[0]; v.y = out[1]; v.z = out[2]; v.w = out[3];
+      }
+      __builtin_nontemporal_store(v, reinterpret_cast<float4_a*>(y + own_base + i));
+    }
+  }
+  // further chunks (large planes only): own and partner loads together, as mix_body
+  for (int chunk = (int)blockIdx.x + KJ * (int)gridDim.x; chunk < chunks; chunk += (int)gridDim.x) {
+    float4_a ow[U];
+    float4_u pa[U];
+    int tq[U], mk[U];
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      const int i = chunk * epb + q * kThreads * 4 + lane_off;
+      const int t = i < plane ? i - (i / T) * T : -1;
+      const bool live = t >= 0 && !is_final(t);
+      int src0 = 0;
+      tq[q] = live ? t : -1;
+      mk[q] = live ? quad_plan(sm, t, T, src0) : 0;
+      // neither load is predicated (mix_body, phase 1): all 2 U loads of the lane in flight together
+      size_t ooff = live ? own_base + i : own_base;
+      asm volatile("" : "+v"(ooff));
+      ow[q] = *reinterpret_cast<const float4_a*>(x + ooff);
+      size_t poff = (mk[q] & 0xf) ? par_base + (i - t) + src0 : ooff;
+      asm volatile("" : "+v"(poff));
+      pa[q] = *reinterpret_cast<const float4_u*>(x + poff);
+    }
+#pragma unroll
+    for (int q = 0; q < U; ++q) {
+      if (tq[q] < 0) continue;
+      const int i = chunk * epb + q * kThreads * 4 + lane_off;
+      float4_a v = ow[q];
+      if (mk[q] & 0xf) {
+        float out[4];
+        quad_blend(out, ow[q], pa[q], x + par_base + (i - tq[q]), sm, tq[q], mk[q], lam, oml);
+        v.x = out[0]; v.y = out[1]; v.z = out[2]; v.w = out[3];
+      }
+      __builtin_nontemporal_store(v, reinterpret_cast<float4_a*>(y + own_base + i));
+    }
+  }
   if (blockIdx.x == 1 && threadIdx.x == 0) { PCGMIX_ACLOCK(b, 3); }
 }
 
@@ -904,12 +1018,13 @@ int pcgmix::launch_mix_karg(const float* x, float* y, const int16_t* frames16, c
 
 #ifdef PCGMIX_PHASE_CLOCK
 extern "C" int pcgmix_armed_phase_clock(long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcgmix::g_armed_clock), sizeof(long long) * 2 * (pcgmix::kPackB + 1) * 4);
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(pcgmix::g_armed_clock), sizeof(long long) * 2 * (pcgmix::kPackB + 1) * 8);
 }
 #endif
 
 int pcgmix::launch_mix_armed(const float* x, float* y, const ArmedArgs& a, int B, int C, int T,
-                             hipStream_t s, const void* pay_host, int pay_bytes, void* pay_dst) {
+                             hipStream_t s, const void* pay_host, int pay_bytes, void* pay_dst,
+                             const int64_t* frames_host, uint32_t* edges_out) {
   using namespace pcgmix;
   if (pay_bytes < 0 || pay_bytes > kPackPayBytes ||
       (pay_bytes > 0 && (!pay_host || !pay_dst || (reinterpret_cast<uintptr_t>(pay_dst) & 15))))
@@ -935,13 +1050,25 @@ int pcgmix::launch_mix_armed(const float* x, float* y, const ArmedArgs& a, int B
   // blockIdx.x, blockIdx.x + gridDim.x, ...
   unsigned per_sample = chunks;
   while (per_sample > 1 && per_sample * (unsigned)B > 2048u) per_sample = (per_sample + 1) / 2;
+  // own cycle edges: saturation only (the boundaries are validated after the launch, beside the label wait)
+  EdgePack edges;
+  edges.n = 0;
+  if (frames_host) {
+    for (int b = 0; b < B; ++b) {
+      const int64_t lo = frames_host[(size_t)b * 5], hi = frames_host[(size_t)b * 5 + 4];
+      const bool ok = (lo >= 0) & (lo <= hi) & (hi <= T);
+      edges.w[b] = ok ? (uint32_t)lo | ((uint32_t)hi << 16) : (uint32_t)T << 16;
+    }
+    edges.n = B;
+    if (edges_out) memcpy(edges_out, edges.w, sizeof(uint32_t) * (size_t)B);
+  }
   dim3 grid(per_sample, (unsigned)B), block(kThreads);
   if (U >= 2)
     hipLaunchKernelGGL((mix_armed_kernel<2>), grid, block, 0, s, x, y, a, B, C, T, epb,
-                       (int)chunks, pay, static_cast<uint4*>(pay_dst));
+                       (int)chunks, pay, static_cast<uint4*>(pay_dst), edges);
   else
     hipLaunchKernelGGL((mix_armed_kernel<1>), grid, block, 0, s, x, y, a, B, C, T, epb,
-                       (int)chunks, pay, static_cast<uint4*>(pay_dst));
+                       (int)chunks, pay, static_cast<uint4*>(pay_dst), edges);
   return (int)hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 """The armed plain step as a timeline (probe build, -DPCGMIX_PHASE_CLOCK): 100 MHz clock at block (0,0)
 entry / labels flagged, and per sample: relay entry / relay saw the host's record / block (1,b) saw the
-relayed record / block (1,b) done.  Two launches are kept (parity of the sequence number), so the gap
+relayed record / block (1,b) done / block (1,b) through its early phase (the loads and stores in front of
+the wait).  Two launches are kept (parity of the sequence number), so the gap
 between one kernel's last block and the next kernel's entry is visible.
 python profiles/probes/armed_phase_clock.py   (GPU box, repo root)"""
 import ctypes, glob, os, subprocess, sys
@@ -10,9 +11,11 @@ PKG = glob.glob(os.path.join(ROOT, "pcgmix-*_amd"))[0]
 out = os.path.join(ROOT, "build_probe", "libpcgmix_phase_clock.so")
 os.makedirs(os.path.dirname(out), exist_ok=True)
 srcs = sorted(glob.glob(os.path.join(PKG, "csrc", "*.hip")))
-subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-shared", "-std=c++17", "--offload-arch=gfx950",
-                "-ffp-contract=off", "-DPCGMIX_PHASE_CLOCK", "-I" + os.path.join(ROOT, "include"), "-o", out]
-               + srcs, check=True)
+if not (os.path.exists(out) and all(os.path.getmtime(out) >= os.path.getmtime(f) for f in
+                                   srcs + glob.glob(os.path.join(PKG, "csrc", "*.h")))):   # (built ahead: kept)
+  subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-fPIC", "-shared", "-std=c++17", "--offload-arch=gfx950",
+                  "-ffp-contract=off", "-DPCGMIX_PHASE_CLOCK", "-I" + os.path.join(ROOT, "include"), "-o", out]
+                 + srcs, check=True)
 import numpy as np
 import torch
 import pcgmix_amd  # noqa: F401
@@ -35,17 +38,19 @@ for (B, C, T) in [(256, 4, 5000), (256, 1, 5000)]:
             sc.count = k
             augmentations.augment(args, data, tgt, fr, wav, sc, None, dev, "")
         torch.cuda.synchronize()
-        buf = (ctypes.c_longlong * (2 * 257 * 4))()
+        buf = (ctypes.c_longlong * (2 * 257 * 8))()
         assert raw.pcgmix_armed_phase_clock(buf) == 0
-        t = np.frombuffer(buf, dtype=np.int64).reshape(2, 257, 4) / 100.0
+        t = np.frombuffer(buf, dtype=np.int64).reshape(2, 257, 8) / 100.0
         last = int(np.argmax(t[:, 256, 0])); prev = 1 - last
         L, P = t[last], t[prev]
         e0 = L[256, 0]
         print((B, C, T), "kernel entry -> labels flagged %.2f | flagged -> relays saw records: median %.2f min %.2f max %.2f | "
               "relay -> block 1 saw: median %.2f max %.2f | body (block 1): median %.2f max %.2f | entry -> last block done %.2f | "
               "relay entry after kernel entry: median %.2f max %.2f | previous kernel's last block done -> this entry %.2f | "
-              "period (entry to entry) %.2f" %
+              "period (entry to entry) %.2f | block 1 early phase done after kernel entry: median %.2f max %.2f, "
+              "before the relay saw the record: median %.2f min %.2f" %
               (L[256, 1] - e0, np.median(L[:B, 1]) - L[256, 1], L[:B, 1].min() - L[256, 1], L[:B, 1].max() - L[256, 1],
                np.median(L[:B, 2] - L[:B, 1]), (L[:B, 2] - L[:B, 1]).max(), np.median(L[:B, 3] - L[:B, 2]),
                (L[:B, 3] - L[:B, 2]).max(), L[:B, 3].max() - e0, np.median(L[:B, 0]) - e0, L[:B, 0].max() - e0,
-               e0 - P[:B, 3].max(), e0 - P[256, 0]), flush=True)
+               e0 - P[:B, 3].max(), e0 - P[256, 0], np.median(L[:B, 4]) - e0, L[:B, 4].max() - e0,
+               np.median(L[:B, 1] - L[:B, 4]), (L[:B, 1] - L[:B, 4]).min()), flush=True)
