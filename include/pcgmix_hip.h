@@ -31,7 +31,7 @@ extern "C" {
  * language binding does not need the HIP headers). */
 typedef struct ihipStream_t* pcgmix_stream_t;
 
-#define PCGMIX_ABI_VERSION 22
+#define PCGMIX_ABI_VERSION 23
 
 /* ABI version of the loaded library (== PCGMIX_ABI_VERSION it was built with). */
 int pcgmix_abi_version(void);
@@ -303,6 +303,17 @@ int pcgmix_salopt_mix_warp_f32(const float* x, float* y, const float* sal, const
  *   tables      device, the blob above
  *   spec        device, (B, n_mels, W) out
  *   frames_out  device, int32 (B, 5) out or NULL: boundaries in spectrogram columns
+ *
+ * Supported shapes (everything else: hipErrorInvalidValue, nothing is launched):
+ *   n_fft >= 4 and a multiple of 4; hop >= 1 (hop need not be n_fft/4); n_mels >= 1; W >= 1 (W may
+ *   exceed the 1 + T/hop frames of an item: the columns beyond them are zero); fmin < fmax, sr > 0;
+ *   n_fft/2 < T; std != 0; pad_mode 0 or 1; and one block's LDS plan (pcgmix_logmel_lds_layout:
+ *   padded row + power spectrogram of ceil32(1 + T/hop) frames + the n_mels x W image + tables) must
+ *   fit 158 KB.  The reference's shapes (n_fft 136 / T 5000 and n_fft 68 / T 2500, any n_mels x W up to
+ *   128 x 128) fit; n_fft = 272 at T = 10000 (a 4 kHz cycle) does not and is refused.  The per-recording
+ *   entry point transforms tiles of pcgmix_logmel_tile_frames() frames, so its plan does not depend
+ *   on the recording's length or on W.  Filters of any width are supported (up to 4 bins from LDS,
+ *   wider ones read their weights from the table), as are banks that leave bins unread at either end.
  */
 long long pcgmix_logmel_tables_size(int n_fft, int n_mels);
 int pcgmix_logmel_tables(int n_fft, int n_mels, float fmin, float fmax, float sr, void* out /* host */);
@@ -335,6 +346,22 @@ int pcgmix_logmel_hostframes_f32(const float* x, const int32_t* frames_host, con
  * order-independent); slice / reference / clip / normalise / pad per cycle.
  */
 int pcgmix_logmel_tile_frames(void);
+/* Host only: the LDS plan of one block of the per-cycle kernel (mode 0, 1 + T/hop frames, with the
+ * n_mels x W dB image) or of the per-recording tile kernel (mode 1, pcgmix_logmel_tile_frames()
+ * frames, no image; T is ignored), for inspection and tests.  out receives 20 int32:
+ *   [2i], [2i+1]  byte offset and size of region i = 0..6: padded row, power spectrogram, dB image,
+ *                 filter records, coefficients of the VALU rows, window, partial sums of the VALU rows.
+ *                 The partial sums lie over the dB image (same offset) when the image holds at least
+ *                 one k part of every 64-frame group at the table's row count; otherwise, and in
+ *                 mode 1, they have a region of their own.  All other regions are disjoint.
+ *   [14] total bytes   [15] bytes of partial sums the kernel writes when n_left_used rows are in
+ *   use (n_left_used < 0: all the table has; always <= [13])   [16] frames, padded to 32
+ *   [17] rows the table holds for the VALU   [18] 1 when the entry points accept the shape
+ *   (total <= [19]), else 0   [19] the limit, 158 KB.
+ * A shape of which one region alone exceeds the limit reports total = INT32_MAX, [18] = 0 and no
+ * regions.  Returns hipErrorInvalidValue for arguments the entry points refuse outright.   [host] */
+int pcgmix_logmel_lds_layout(int mode, int T, int n_fft, int hop, int n_mels, int W, int n_left_used,
+                             int32_t* out);
 int pcgmix_logmel_recordings_f32(const float* y, const int64_t* rec_off, const int32_t* rec_len,
                                  int R, const int32_t* tiles, int n_tiles, const int32_t* cycles,
                                  int n_cycles, const void* tables, float* db_scratch,

@@ -12,7 +12,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpcgmix_hip.so")
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _c_int = ctypes.c_int
 _c_float = ctypes.c_float
@@ -61,6 +61,7 @@ SIGNATURES = {
     "pcgmix_logmel_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int,
                                    _c_int, _c_float, _c_float, _c_int, _c_int, _ptr]),
     "pcgmix_logmel_tile_frames": (_c_int, []),
+    "pcgmix_logmel_lds_layout": (_c_int, [_c_int] * 7 + [_ptr]),
     "pcgmix_logmel_recordings_f32": (_c_int, [_ptr, _ptr, _ptr, _c_int, _ptr, _c_int, _ptr, _c_int, _ptr,
                                               _ptr, ctypes.c_longlong, _ptr, _ptr, _c_int, _c_int,
                                               _c_int, _c_float, _c_float, _c_int, _c_int, _ptr]),

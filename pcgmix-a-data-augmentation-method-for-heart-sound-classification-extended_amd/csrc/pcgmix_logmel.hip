@@ -109,9 +109,10 @@ __host__ __device__ inline MelTables mel_tables(int n_fft, int n_mels) {
   return t;
 }
 
+constexpr int kMelLdsLimit = 158 * 1024;   // dynamic LDS a block may ask for
 struct MelLayout {  // byte offsets into dynamic LDS
   int xrow, ps, img, melw, left, win, part, part_bytes, total;
-  int nfp, xr;
+  int nfp, xr, part_min;
 };
 // n_frames = frames one block transforms: 1 + T/hop of a heart-cycle item, or the tile size of
 // the per-recording pass; img_rows = n_mels when the block keeps a dB image in LDS, 0 otherwise.
@@ -126,23 +127,53 @@ __host__ __device__ inline MelLayout mel_layout(int n_frames, int n_fft, int hop
   L.xrow = o; o += L.xr * 4;                    // reflect-padded waveform, zero beyond (float)
   L.ps = o;   o += tb.m_tiles * 16 * L.nfp * 4; // power spectrogram [bin][frame]        (float)
   L.img = o;  o += (image ? n_mels * W : 0) * 4;  // dB image                            (float)
+  o = (o + 15) & ~15;                           // (an odd n_mels * W must not misalign the doubles behind it)
   L.melw = o; o += n_mels * 8 * 4;              // per band: klo, khi, 4 weights (+2 pad) (32 B)
   L.left = o; o += tb.n_left * (n_fft / 2 + kLeftPad) * 2 * 8;   // coefficients of the VALU bins (double)
   L.win = o;  o += (n_fft / 2 + 1) * 8;         // periodic Hann, n = 0 .. n_fft/2          (double)
   // partial sums of the VALU bins [wave job][bin][lane][re, im] (double): over the dB image, which
   // is written only after they are consumed, when that is large enough; else on their own
-  // (the kernel takes as many k parts as fit: one wave job = n_left_used rows x 64 lanes x 16 bytes)
-  if (image) {
+  // (the kernel takes as many k parts as fit: one wave job = n_left_used rows x 64 lanes x 16 bytes).
+  // "Large enough" = one k part of every 64-frame group at the table's full row count: the kernel
+  // never takes fewer than one part, so a smaller image (n_mels * W * 4 < part_min) must not carry
+  // them.  Their own region holds a part per wave (at most kLeftPad), fewer where that would not fit
+  // the block's LDS, never less than one.
+  const int n_fg = (L.nfp + 63) / 64;
+  L.part_min = n_fg * tb.n_left * 64 * 16;
+  if (image && n_mels * W * 4 >= L.part_min) {
     L.part = L.img;
     L.part_bytes = n_mels * W * 4;
   } else {
     o = (o + 15) & ~15;
     L.part = o;
-    L.part_bytes = kMelWaves * tb.n_left * 64 * 16;
+    int parts = kMelWaves / n_fg;
+    parts = parts > kLeftPad ? kLeftPad : parts;
+    const int room = L.part_min > 0 && o < kMelLdsLimit ? (kMelLdsLimit - o) / L.part_min : 0;
+    parts = parts > room ? room : parts;
+    L.part_bytes = (parts < 1 ? 1 : parts) * L.part_min;
     o += L.part_bytes;
   }
   L.total = o;
   return L;
+}
+// k parts the VALU rows are summed in (one wave each per 64-frame group): as many as there are
+// waves and as their sums fit, 1 .. kLeftPad.  mel_layout guarantees room for one part of tb.n_left rows.
+__host__ __device__ inline int mel_left_parts(const MelLayout& L, int n_left_used) {
+  const int n_fg = (L.nfp + 63) / 64;              // 64-frame groups
+  int parts = kMelWaves / n_fg;
+  const int fit = L.part_bytes / (n_left_used * 64 * 16) / n_fg;
+  parts = parts > fit ? fit : parts;
+  return parts < 1 ? 1 : (parts > kLeftPad ? kLeftPad : parts);
+}
+// Host: whether every region of mel_layout is small enough on its own, in 64-bit arithmetic — the
+// layout itself is int arithmetic in the kernel and is only evaluated for shapes that pass this.
+inline bool mel_shape_small(long long n_frames, int n_fft, int hop, int n_mels, int W, bool image) {
+  const MelTables tb = mel_tables(n_fft, n_mels);
+  const long long cap = kMelLdsLimit;
+  const long long nfp = (n_frames + 31) / 32 * 32;
+  return ((nfp - 1) * hop + n_fft + 12) * 4 <= cap && (long long)tb.m_tiles * 16 * nfp * 4 <= cap &&
+         (image ? (long long)n_mels * W * 4 : 0) <= cap && (long long)n_mels * 32 <= cap &&
+         (long long)tb.n_left * (n_fft / 2 + kLeftPad) * 16 <= cap;
 }
 
 // power_to_db's 10 * log10(max(amin, S)), amin = 1e-10, as 10 log10(2) * v_log_f32: the hardware
@@ -330,10 +361,7 @@ __global__ __launch_bounds__(kMelThreads) void logmel_kernel(
   if (n_left_used > 0) {                             // block-uniform
     const int nh = n_fft / 2, ncol = nh + kLeftPad;
     const int n_fg = (L.nfp + 63) / 64;              // 64-frame groups
-    int parts = kMelWaves / n_fg;                    // k parts, one wave each per frame group
-    const int fit = L.part_bytes / (n_left_used * 64 * 16) / n_fg;   // ... as far as their sums fit
-    parts = parts > fit ? fit : parts;
-    parts = parts < 1 ? 1 : (parts > kLeftPad ? kLeftPad : parts);
+    const int parts = mel_left_parts(L, n_left_used);   // k parts, one wave each per frame group
     const int kper = (nh + parts - 1) / parts;       // parts * kper <= nh + parts - 1 < nh + kLeftPad
     // the row count as a compile-time constant: straight-line code per k (with a run-time count every
     // row became its own branch with its own LDS wait)
@@ -844,15 +872,16 @@ namespace pcgmix {
 static int launch_logmel_cycles(const float* x, const int32_t* frames, const MelEnds* ends, const void* tables,
                                 float* spec, int32_t* frames_out, int B, int T, int n_fft, int hop,
                                 int n_mels, float mean, float std, int W, int pad_mode, hipStream_t s) {
+  if (!mel_shape_small(1LL + T / hop, n_fft, hop, n_mels, W, true)) return hipErrorInvalidValue;
   const MelLayout L = mel_layout(1 + T / hop, n_fft, hop, n_mels, W);
-  if (L.total > 158 * 1024) return hipErrorInvalidValue;
+  if (L.total > kMelLdsLimit) return hipErrorInvalidValue;
   static unsigned long long lds_ok[4] = {0, 0, 0, 0};
   const bool ks9 = mel_tables(n_fft, n_mels).ksteps == 9;      // the reference's n_fft = 136
   const unsigned char* tb = static_cast<const unsigned char*>(tables);
 #define PCGMIX_MEL(KSV, EN, SLOT, ENDARG)                                                              \
   do {                                                                                               \
     auto kern = logmel_kernel<false, KSV, EN>;                                                       \
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(kern), &lds_ok[SLOT], 158 * 1024)) \
+    if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(kern), &lds_ok[SLOT], kMelLdsLimit)) \
       return (int)e;                                                                                 \
     hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kMelThreads), (size_t)L.total, s, x, frames, nullptr, \
                        nullptr, nullptr, tb, spec, nullptr, 0LL, frames_out, B, T, n_fft, hop, n_mels, mean, \
@@ -910,6 +939,45 @@ extern "C" int pcgmix_logmel_hostframes_f32(const float* x, const int32_t* frame
 
 extern "C" int pcgmix_logmel_tile_frames(void) { return pcgmix::kTileFrames; }
 
+// Host only: the LDS plan of one block, for inspection and tests (include/pcgmix_hip.h).
+extern "C" int pcgmix_logmel_lds_layout(int mode, int T, int n_fft, int hop, int n_mels, int W,
+                                        int n_left_used, int32_t* out) {
+  using namespace pcgmix;
+  if (!out || (mode != 0 && mode != 1) || n_fft < 4 || (n_fft & 3) || hop < 1 || n_mels < 1 || W < 1 ||
+      (mode == 0 && T < 2))
+    return hipErrorInvalidValue;
+  const MelTables tb = mel_tables(n_fft, n_mels);
+  if (n_left_used > tb.n_left) return hipErrorInvalidValue;
+  const int used = n_left_used < 0 ? tb.n_left : n_left_used;
+  const bool image = mode == 0;
+  const long long n_frames = image ? 1 + (long long)T / hop : kTileFrames;
+  for (int i = 0; i < 20; ++i) out[i] = 0;
+  out[19] = kMelLdsLimit;
+  if (!mel_shape_small(n_frames, n_fft, hop, n_mels, W, image)) {
+    out[14] = INT32_MAX;                             // some region alone is beyond the limit
+    return hipSuccess;
+  }
+  const MelLayout L = mel_layout((int)n_frames, n_fft, hop, n_mels, W, image);
+  const int n_fg = (L.nfp + 63) / 64;
+  const int reg[7][2] = {{L.xrow, L.xr * 4},
+                         {L.ps, tb.m_tiles * 16 * L.nfp * 4},
+                         {L.img, image ? n_mels * W * 4 : 0},
+                         {L.melw, n_mels * 32},
+                         {L.left, tb.n_left * (n_fft / 2 + kLeftPad) * 16},
+                         {L.win, (n_fft / 2 + 1) * 8},
+                         {L.part, L.part_bytes}};
+  for (int i = 0; i < 7; ++i) {
+    out[2 * i] = reg[i][0];
+    out[2 * i + 1] = reg[i][1];
+  }
+  out[14] = L.total;
+  out[15] = used > 0 ? n_fg * mel_left_parts(L, used) * used * 64 * 16 : 0;
+  out[16] = L.nfp;
+  out[17] = tb.n_left;
+  out[18] = L.total <= kMelLdsLimit;
+  return hipSuccess;
+}
+
 extern "C" int pcgmix_logmel_recordings_f32(
     const float* y, const int64_t* rec_off, const int32_t* rec_len, int R, const int32_t* tiles,
     int n_tiles, const int32_t* cycles, int n_cycles, const void* tables, float* db_scratch,
@@ -923,14 +991,15 @@ extern "C" int pcgmix_logmel_recordings_f32(
       hop < 1 || n_mels < 1 || W < 1 || !(std != 0.f) ||
       (pad_mode != kPadConstant && pad_mode != kPadReflect))
     return hipErrorInvalidValue;
+  if (!mel_shape_small(kTileFrames, n_fft, hop, n_mels, W, false)) return hipErrorInvalidValue;
   const MelLayout L = mel_layout(kTileFrames, n_fft, hop, n_mels, W, false);
-  if (L.total > 158 * 1024) return hipErrorInvalidValue;
+  if (L.total > kMelLdsLimit) return hipErrorInvalidValue;
   static unsigned long long lds_ok = 0, lds_ok17 = 0;
   const bool ks17 = mel_tables(n_fft, n_mels).ksteps == 9;
   if (hipError_t e = ks17 ? allow_large_lds(reinterpret_cast<const void*>(logmel_kernel<true, 9>),
-                                            &lds_ok17, 158 * 1024)
+                                            &lds_ok17, kMelLdsLimit)
                           : allow_large_lds(reinterpret_cast<const void*>(logmel_kernel<true, 0>),
-                                            &lds_ok, 158 * 1024))
+                                            &lds_ok, kMelLdsLimit))
     return (int)e;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, ref_pow, R);
