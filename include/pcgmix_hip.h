@@ -31,7 +31,7 @@ extern "C" {
  * language binding does not need the HIP headers). */
 typedef struct ihipStream_t* pcgmix_stream_t;
 
-#define PCGMIX_ABI_VERSION 23
+#define PCGMIX_ABI_VERSION 24
 
 /* ABI version of the loaded library (== PCGMIX_ABI_VERSION it was built with). */
 int pcgmix_abi_version(void);
@@ -437,6 +437,62 @@ int pcgmix_potes_stack_bwd_mask_f32(const float* x, const float* grad_h2, const 
 int pcgmix_potes_stack_input_grad_mask_f32(const float* grad_h2, const uint8_t* m2,
                                            const uint8_t* s1, const float* w1, const float* w2,
                                            float* grad_x, int N, int T, pcgmix_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Narrow Potes conv stacks (the reference's model-size ladder).                      [device]
+ *
+ * The same chain on the N = 4*B band rows x (N,T) for the two small models of models.py:352-356
+ * (CNN_potes_tenpercent_TS, layers [2,1]; CNN_potes_twopercent_TS, layers [1,1]) over
+ * models.py:359-381:
+ *     Conv1d(1->C1,k5,pad1) + ReLU + MaxPool1d(2) -> Conv1d(C1->C2,k5,pad1) + ReLU + MaxPool1d(2)
+ * (C1,C2) in {(1,1), (2,1)}; torch weight layouts w1 (C1,1,5), b1 (C1), w2 (C2,C1,5), b2 (C2);
+ * float32, T >= 14, P2 = pcgmix_potes_out_len(T).  Plain VALU kernels (csrc/pcgmix_potes_narrow.hip):
+ * every conv output is an in-order fmaf chain from the bias over (input channel, tap).
+ *
+ *   pcgmix_potes_narrow_supported(C1,C2)   1 for (1,1) and (2,1), else 0
+ *   pcgmix_potes_narrow_grad_len(C1,C2)    5*C1 + C1 + 5*C1*C2 + C2 (12, 23); 0 if unsupported
+ *   pcgmix_potes_narrow_bwd_blocks         G = partial rows the weight gradient needs
+ *   pcgmix_potes_narrow_mask_bytes         bytes of m2 (layer = 2) / s1 (layer = 1)
+ *                                          (both helpers: 0 for an unsupported (C1,C2), T < 14,
+ *                                          N <= 0 or N > 65535 — whatever the launching entry
+ *                                          points refuse)
+ *   pcgmix_potes_narrow_fwd_f32            ONE launch: h2 (N,C2,P2); m2 != NULL: + the second layer's
+ *                                          routing; s1 != NULL: + the first layer's (only the input
+ *                                          gradient reads it).  m2 and s1 are the 2-bit encodings
+ *                                          defined above with 8 -> C1 and 4 -> C2: m2 uint8
+ *                                          (N, C2, ceil(P2/4)), s1 uint8 (N, C1, P1/4 + 1).
+ *                                          m2 == s1 == rnd_out == NULL: the inference forward.
+ *                                          rnd_out, rnd_bytes, key_dev, key: exactly as in
+ *                                          pcgmix_potes_stack_fwd_save_f32 — the same hash, the
+ *                                          same checks, the same bytes for a key and a length.
+ *   pcgmix_potes_narrow_bwd_mask_f32       weight gradients: recomputes layer 1 from x, routes
+ *                                          through m2, writes `partial` (G, grad_len) and reduces
+ *                                          it in a fixed order (no float atomics) into grads =
+ *                                          [gw1 | gb1 | gw2 | gb2].  grads == NULL (the deferred
+ *                                          reduction of the [8,4] kernels) is NOT supported:
+ *                                          hipErrorInvalidValue.
+ *   pcgmix_potes_narrow_input_grad_mask_f32  dL/dx (N,T) from grad_h2, m2, s1 and the weights
+ *                                          alone; every element of grad_x is written.
+ * Every entry point returns hipErrorInvalidValue, launching nothing and leaving its outputs
+ * untouched, for an unsupported (C1,C2), T < 14, N < 0 (or > 65535), a NULL required pointer or a
+ * misaligned rnd_out; N == 0 succeeds without a launch.  All are legal on a capturing stream.
+ */
+int pcgmix_potes_narrow_supported(int C1, int C2);
+int pcgmix_potes_narrow_grad_len(int C1, int C2);
+int pcgmix_potes_narrow_bwd_blocks(int N, int T, int C1, int C2);
+long long pcgmix_potes_narrow_mask_bytes(int N, int T, int C1, int C2, int layer);
+int pcgmix_potes_narrow_fwd_f32(const float* x, const float* w1, const float* b1, const float* w2,
+                                const float* b2, float* h2, uint8_t* m2, uint8_t* s1, int N, int T,
+                                int C1, int C2, uint8_t* rnd_out, long long rnd_bytes,
+                                const uint32_t* key_dev, uint64_t key, pcgmix_stream_t stream);
+int pcgmix_potes_narrow_bwd_mask_f32(const float* x, const float* grad_h2, const uint8_t* m2,
+                                     const float* w1, const float* b1, const float* w2,
+                                     const float* b2, float* partial, float* grads, int N, int T,
+                                     int C1, int C2, pcgmix_stream_t stream);
+int pcgmix_potes_narrow_input_grad_mask_f32(const float* grad_h2, const uint8_t* m2,
+                                            const uint8_t* s1, const float* w1, const float* w2,
+                                            float* grad_x, int N, int T, int C1, int C2,
+                                            pcgmix_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Skinny linear layer forward (the Potes head's `dimreduc`, models.py:376, 430).    [device]

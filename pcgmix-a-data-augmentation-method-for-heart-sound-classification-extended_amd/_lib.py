@@ -12,7 +12,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpcgmix_hip.so")
-ABI_VERSION = 23
+ABI_VERSION = 24
 
 _c_int = ctypes.c_int
 _c_float = ctypes.c_float
@@ -75,6 +75,14 @@ SIGNATURES = {
                                                  _ptr, ctypes.c_uint64, _ptr]),
     "pcgmix_potes_stack_bwd_mask_f32": (_c_int, [_ptr] * 9 + [_c_int, _c_int, _ptr]),
     "pcgmix_potes_stack_input_grad_mask_f32": (_c_int, [_ptr] * 6 + [_c_int, _c_int, _ptr]),
+    "pcgmix_potes_narrow_supported": (_c_int, [_c_int, _c_int]),
+    "pcgmix_potes_narrow_grad_len": (_c_int, [_c_int, _c_int]),
+    "pcgmix_potes_narrow_bwd_blocks": (_c_int, [_c_int] * 4),
+    "pcgmix_potes_narrow_mask_bytes": (ctypes.c_longlong, [_c_int] * 5),
+    "pcgmix_potes_narrow_fwd_f32": (_c_int, [_ptr] * 8 + [_c_int] * 4 + [_ptr, ctypes.c_longlong, _ptr,
+                                                                     ctypes.c_uint64, _ptr]),
+    "pcgmix_potes_narrow_bwd_mask_f32": (_c_int, [_ptr] * 9 + [_c_int] * 4 + [_ptr]),
+    "pcgmix_potes_narrow_input_grad_mask_f32": (_c_int, [_ptr] * 6 + [_c_int] * 4 + [_ptr]),
     "pcgmix_skinny_linear_splits": (_c_int, [_c_int, _c_int]),
     "pcgmix_skinny_linear_fwd_f32": (_c_int, [_ptr] * 5 + [_c_int, _c_int, _c_int, _ptr]),
     "pcgmix_adam_clip_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, ctypes.c_longlong, _c_float, _c_float,

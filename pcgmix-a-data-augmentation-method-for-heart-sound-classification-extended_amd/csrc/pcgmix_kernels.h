@@ -318,5 +318,37 @@ int launch_salopt_search(const float* sal, const int32_t* frames, const int32_t*
                          int pay_n16 = 0, const int16_t* partners16 = nullptr,
                          const DispPlan* plan = nullptr);
 
+// The random bytes the Potes head's dropouts read (pcgmix_potes_stack_fwd_save_f32 and
+// pcgmix_potes_narrow_fwd_f32 fill them on the side of their forward launch): 32-bit word w =
+// counter_hash(w, key) — murmur3's 32-bit finaliser, keyed before and inside.
+__device__ __forceinline__ uint32_t counter_hash(uint32_t i, uint32_t k0, uint32_t k1) {
+  uint32_t h = i * 0x9E3779B1u + k0;
+  h ^= h >> 16;
+  h *= 0x85EBCA6Bu;
+  h ^= h >> 13;
+  h ^= k1;
+  h *= 0xC2B2AE35u;
+  h ^= h >> 16;
+  return h;
+}
+// rnd[0 .. rnd_n16) 16-byte words, by all threads of a launch: `first` is this thread's index in
+// the launch, `stride` the launch's thread count.  key != nullptr: the two key words are read from
+// device memory (a captured step changes them per replay), else they are (key_lo, key_hi).
+__device__ __forceinline__ void counter_hash_fill(uint4* __restrict__ rnd, long long rnd_n16,
+                                                  const uint32_t* __restrict__ key, uint32_t key_lo,
+                                                  uint32_t key_hi, long long first, long long stride) {
+  const uint32_t k0 = key ? key[0] : key_lo, k1 = key ? key[1] : key_hi;
+  for (long long i = first; i < rnd_n16; i += stride) {
+    const uint32_t c = (uint32_t)i * 4u;
+    rnd[i] = make_uint4(counter_hash(c, k0, k1), counter_hash(c + 1, k0, k1),
+                        counter_hash(c + 2, k0, k1), counter_hash(c + 3, k0, k1));
+  }
+}
+// Host-side check of the (rnd_out, rnd_bytes) pair of those entry points; rnd_out == NULL: no fill.
+inline bool dropout_fill_args_ok(const void* rnd_out, long long rnd_bytes, int N) {
+  return !rnd_out || !(rnd_bytes <= 0 || (rnd_bytes & 15) || rnd_bytes > (16ll << 30) ||
+                       (reinterpret_cast<uintptr_t>(rnd_out) & 15) || N == 0);
+}
+
 }  // namespace pcgmix
 #endif

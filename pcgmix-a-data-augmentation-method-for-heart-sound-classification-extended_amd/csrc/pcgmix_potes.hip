@@ -231,16 +231,8 @@ constexpr int kFwdNQ = 2 * kFwdTP + 4;          // 508
 // two kernel arguments).  In a captured training step this replaces an eager `random_()` launch
 // before every replay: the key changes per replay (it rides with the step payload), the graph
 // does not.
-__device__ __forceinline__ uint32_t counter_hash(uint32_t i, uint32_t k0, uint32_t k1) {
-  uint32_t h = i * 0x9E3779B1u + k0;      // murmur3's 32-bit finaliser, keyed before and inside
-  h ^= h >> 16;
-  h *= 0x85EBCA6Bu;
-  h ^= h >> 13;
-  h ^= k1;
-  h *= 0xC2B2AE35u;
-  h ^= h >> 16;
-  return h;
-}
+// counter_hash and the fill loop (counter_hash_fill) are in pcgmix_kernels.h: the narrow stacks
+// (pcgmix_potes_narrow.hip) fill the same bytes from the same key.
 
 // ---------------------------------------------------------------------------------- forward, MFMA
 // The same stack on the matrix cores (round 3).  A k5 convolution with 8 or 4 output channels is a
@@ -384,15 +376,10 @@ __global__ __launch_bounds__(kPotThreads, 4) void potes_fwd_mfma_kernel(
     const float* __restrict__ w2, const float* __restrict__ b2, float* __restrict__ h2,
     uint8_t* __restrict__ m2, uint8_t* __restrict__ s1, int N, int T, uint4* __restrict__ rnd,
     long long rnd_n16, const uint32_t* __restrict__ key, uint32_t key_lo, uint32_t key_hi) {
-  if (SAVE && rnd) {
-    const uint32_t k0 = key ? key[0] : key_lo, k1 = key ? key[1] : key_hi;
-    const long long stride = (long long)gridDim.x * kPotThreads;
-    for (long long i = (long long)blockIdx.x * kPotThreads + threadIdx.x; i < rnd_n16; i += stride) {
-      const uint32_t c = (uint32_t)i * 4u;
-      rnd[i] = make_uint4(counter_hash(c, k0, k1), counter_hash(c + 1, k0, k1),
-                          counter_hash(c + 2, k0, k1), counter_hash(c + 3, k0, k1));
-    }
-  }
+  if (SAVE && rnd)
+    counter_hash_fill(rnd, rnd_n16, key, key_lo, key_hi,
+                      (long long)blockIdx.x * kPotThreads + threadIdx.x,
+                      (long long)gridDim.x * kPotThreads);
   __shared__ __align__(16) float xs[kMfXFloats];
   __shared__ __align__(16) float a1s[kC1 * kMfAPitch];
   const PotesDims d = potes_dims(T);
@@ -1987,9 +1974,7 @@ extern "C" int pcgmix_potes_stack_fwd_save_f32(const float* x, const float* w1, 
   using namespace pcgmix;
   if (!x || !w1 || !b1 || !w2 || !b2 || !h2 || !m2 || N < 0 || T < 14 || N > 65535)
     return hipErrorInvalidValue;
-  if (rnd_out && (rnd_bytes <= 0 || (rnd_bytes & 15) || rnd_bytes > (16ll << 30) ||
-                  (reinterpret_cast<uintptr_t>(rnd_out) & 15) || N == 0))
-    return hipErrorInvalidValue;
+  if (!dropout_fill_args_ok(rnd_out, rnd_bytes, N)) return hipErrorInvalidValue;
   if (N == 0) return hipSuccess;
   const PotesDims d = potes_dims(T);
   hipLaunchKernelGGL(potes_fwd_mfma_kernel<true>, dim3(potes_fwd_mfma_blocks(N, d)),

@@ -1,7 +1,7 @@
 """1D models of the PCGmix hot path, re-declared on PyTorch-ROCm with the reference's
 ``state_dict`` layout so checkpoints are interchangeable.
 
-  CNN_potes     the "1D-CNN" (Potes et al.), reference models.py:367-465, factory :345-350
+  CNN_potes     the "1D-CNN" (Potes et al.), reference models.py:367-465, factories :339-356
   ResNet9       Myrtle ResNet9 with 1D convolutions, reference models.py:520-589
 
 Both keep the reference's ``forward(x, depth=None, pass_part=None)`` signature; the training
@@ -34,7 +34,9 @@ def _warn_once(msg: str) -> None:
 
 class PotesStackFunction(torch.autograd.Function):
     """conv(1->8,k5,p1)+ReLU+pool2 -> conv(8->4,k5,p1)+ReLU+pool2 on (N,T) rows as ONE HIP kernel
-    forward and one (+ a 212-block reduction) backward (csrc/pcgmix_potes.hip).
+    forward and one (+ a 212-block reduction) backward (csrc/pcgmix_potes.hip).  Dispatches on the
+    weight shapes: layers [1,1] and [2,1] (the small models of the reference's size ladder) run
+    the same chain through their own kernels (csrc/pcgmix_potes_narrow.hip, mask-based only).
 
     ``use_masks`` (default): when a gradient will be needed the forward also stores where its
     ReLUs were alive and which element won each max-pool (2 bits per second-layer output; a byte
@@ -62,28 +64,52 @@ class PotesStackFunction(torch.autograd.Function):
         N, T = x.shape
         lib = _lib.load()
         P2 = lib.pcgmix_potes_out_len(T)
+        C1, C2 = int(w1.shape[0]), int(w2.shape[0])
+        narrow = (C1, C2) != (8, 4)                     # the small models' own kernels
+        if narrow and not lib.pcgmix_potes_narrow_supported(C1, C2):
+            raise RuntimeError(f"PotesStackFunction: no HIP conv stack for layers [{C1},{C2}]")
         w1c, b1c, w2c, b2c = (t.detach().contiguous() for t in (w1, b1, w2, b2))
-        h2 = torch.empty((N, 4, P2), dtype=torch.float32, device=x.device)
+        h2 = torch.empty((N, C2, P2), dtype=torch.float32, device=x.device)
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         need_x = ctx.needs_input_grad[0]
         m2 = s1 = None
+        opt = lambda t: t.data_ptr() if t is not None else None      # noqa: E731
+        rnd_args = (opt(rnd), rnd.numel() if rnd is not None else 0,
+                    key.data_ptr() if torch.is_tensor(key) else None,
+                    0 if (key is None or torch.is_tensor(key)) else int(key), stream)
         # rnd without any gradient (frozen conv stack, head-only fine-tuning in train mode): the
         # mask-saving forward still runs, for the dropout bytes it fills on the side
-        if PotesStackFunction.use_masks and N > 0 and (any(ctx.needs_input_grad) or rnd is not None):
+        save = PotesStackFunction.use_masks and N > 0 and (any(ctx.needs_input_grad) or rnd is not None)
+        if narrow and not PotesStackFunction.use_masks and any(ctx.needs_input_grad):
+            raise RuntimeError("PotesStackFunction: the narrow conv stacks have no recomputing "
+                               "backward (needs use_masks)")
+        if save and narrow:
+            m2 = torch.empty(lib.pcgmix_potes_narrow_mask_bytes(N, T, C1, C2, 2), dtype=torch.uint8,
+                             device=x.device)
+            if need_x:
+                s1 = torch.empty(lib.pcgmix_potes_narrow_mask_bytes(N, T, C1, C2, 1),
+                                 dtype=torch.uint8, device=x.device)
+            _lib.check(lib.pcgmix_potes_narrow_fwd_f32(
+                x.data_ptr(), w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(),
+                h2.data_ptr(), m2.data_ptr(), opt(s1), N, T, C1, C2, *rnd_args),
+                "pcgmix_potes_narrow_fwd_f32")
+        elif save:
             m2 = torch.empty(lib.pcgmix_potes_mask_bytes(N, T, 2), dtype=torch.uint8, device=x.device)
             if need_x:
                 s1 = torch.empty(lib.pcgmix_potes_mask_bytes(N, T, 1), dtype=torch.uint8,
                                  device=x.device)
             _lib.check(lib.pcgmix_potes_stack_fwd_save_f32(
                 x.data_ptr(), w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(),
-                h2.data_ptr(), m2.data_ptr(), s1.data_ptr() if s1 is not None else None, N, T,
-                rnd.data_ptr() if rnd is not None else None, rnd.numel() if rnd is not None else 0,
-                key.data_ptr() if torch.is_tensor(key) else None,
-                0 if (key is None or torch.is_tensor(key)) else int(key), stream),
+                h2.data_ptr(), m2.data_ptr(), opt(s1), N, T, *rnd_args),
                 "pcgmix_potes_stack_fwd_save_f32")
         elif rnd is not None:
             raise RuntimeError("PotesStackFunction: dropout bytes are filled by the mask-saving "
                                "forward (needs use_masks)")
+        elif narrow:
+            _lib.check(lib.pcgmix_potes_narrow_fwd_f32(
+                x.data_ptr(), w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(),
+                h2.data_ptr(), None, None, N, T, C1, C2, None, 0, None, 0, stream),
+                "pcgmix_potes_narrow_fwd_f32")
         else:
             _lib.check(lib.pcgmix_potes_stack_fwd_f32(x.data_ptr(), w1c.data_ptr(), b1c.data_ptr(),
                                                       w2c.data_ptr(), b2c.data_ptr(), h2.data_ptr(),
@@ -98,6 +124,9 @@ class PotesStackFunction(torch.autograd.Function):
         lib = _lib.load()
         g = grad_h2.contiguous()
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        C1, C2 = int(w1.shape[0]), int(w2.shape[0])
+        if (C1, C2) != (8, 4):
+            return PotesStackFunction._backward_narrow(ctx, g, lib, stream)
         gx = gw1 = gb1 = gw2 = gb2 = None
         if ctx.needs_input_grad[0]:                    # saliency: d score / d input
             gx = torch.empty_like(x)
@@ -131,6 +160,39 @@ class PotesStackFunction(torch.autograd.Function):
                     "pcgmix_potes_stack_bwd_f32")
             gw1, gb1 = grads[0:40].view(8, 1, 5), grads[40:48]
             gw2, gb2 = grads[48:208].view(4, 8, 5), grads[208:212]
+        return gx, gw1, gb1, gw2, gb2, None, None
+
+    @staticmethod
+    def _backward_narrow(ctx, g, lib, stream):
+        """The small models' backward (csrc/pcgmix_potes_narrow.hip): always from the saved routing,
+        and the weight gradient always reduced in its own call — ``defer_reduce`` is not consulted,
+        so the optimiser's fold finds nothing deferred."""
+        x, w1, b1, w2, b2, m2, s1 = ctx.saved_tensors
+        N, T = x.shape
+        C1, C2 = int(w1.shape[0]), int(w2.shape[0])
+        gx = gw1 = gb1 = gw2 = gb2 = None
+        if N == 0:
+            if ctx.needs_input_grad[0]:
+                gx = torch.zeros_like(x)
+            if any(ctx.needs_input_grad[1:]):
+                gw1, gb1, gw2, gb2 = (torch.zeros_like(t) for t in (w1, b1, w2, b2))
+            return gx, gw1, gb1, gw2, gb2, None, None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty_like(x)
+            _lib.check(lib.pcgmix_potes_narrow_input_grad_mask_f32(
+                g.data_ptr(), m2.data_ptr(), s1.data_ptr(), w1.data_ptr(), w2.data_ptr(),
+                gx.data_ptr(), N, T, C1, C2, stream), "pcgmix_potes_narrow_input_grad_mask_f32")
+        if any(ctx.needs_input_grad[1:]):
+            G, L = lib.pcgmix_potes_narrow_bwd_blocks(N, T, C1, C2), lib.pcgmix_potes_narrow_grad_len(C1, C2)
+            partial = torch.empty((G, L), dtype=torch.float32, device=x.device)
+            grads = torch.empty(L, dtype=torch.float32, device=x.device)
+            _lib.check(lib.pcgmix_potes_narrow_bwd_mask_f32(
+                x.data_ptr(), g.data_ptr(), m2.data_ptr(), w1.data_ptr(), b1.data_ptr(),
+                w2.data_ptr(), b2.data_ptr(), partial.data_ptr(), grads.data_ptr(), N, T, C1, C2,
+                stream), "pcgmix_potes_narrow_bwd_mask_f32")
+            o1, o2, o3 = 5 * C1, 6 * C1, 6 * C1 + 5 * C1 * C2
+            gw1, gb1 = grads[0:o1].view(C1, 1, 5), grads[o1:o2]
+            gw2, gb2 = grads[o2:o3].view(C2, C1, 5), grads[o3:o3 + C2]
         return gx, gw1, gb1, gw2, gb2, None, None
 
 
@@ -452,19 +514,26 @@ class CNN_potes(nn.Module):
         self.dropout_key = None     # the device key they come from (see _static_dropout)
 
     def _fused(self, x: torch.Tensor) -> bool:
-        """The hand-written HIP stack applies to the reference configuration (layers [8,4], float32)
-        on a HIP device.  Host tensors (CPU-side tests, gloo rehearsals) and an explicit
-        ``self.fused = False`` take torch's ops; a DEVICE tensor that cannot take the HIP kernels
-        does so too, but says so — a GPU run must not lose its kernels without a word."""
+        """The hand-written HIP stacks apply to float32 input on a HIP device for the reference
+        configuration (layers [8,4]) and for the narrow widths the library reports as supported
+        ([1,1], [2,1]: ``pcgmix_potes_narrow_supported``; those only with
+        ``PotesStackFunction.use_masks``, they have no recomputing backward).  Host tensors (CPU-side
+        tests, gloo rehearsals) and an explicit ``self.fused = False`` take torch's ops; a DEVICE
+        tensor that cannot take the HIP kernels does so too, but says so — a GPU run must not lose
+        its kernels without a word."""
         if not (self.fused and x.is_cuda):
             return False
         c1, c2 = self.cnn1[0][0], self.cnn1[1][0]
-        ok = (x.dtype == torch.float32 and c1.out_channels == 8 and c2.out_channels == 4
-              and x.shape[-1] >= 14)
+        widths = (c1.out_channels, c2.out_channels)
+        ok = widths == (8, 4) or bool(
+            PotesStackFunction.use_masks
+            and _lib.load().pcgmix_potes_narrow_supported(widths[0], widths[1]))
+        ok = ok and x.dtype == torch.float32 and x.shape[-1] >= 14
         if not ok:
             _warn_once(f"CNN_potes: input {tuple(x.shape)} {x.dtype} / layers "
                        f"[{c1.out_channels},{c2.out_channels}] cannot use the fused HIP conv stack "
-                       "(needs float32, layers [8,4], T >= 14): running torch/MIOpen ops instead")
+                       "(needs float32, T >= 14 and layers [8,4], or [1,1] / [2,1] with "
+                       "PotesStackFunction.use_masks): running torch/MIOpen ops instead")
         return ok
 
     def _fused_head(self, x: torch.Tensor) -> bool:
@@ -580,6 +649,40 @@ def CNN_potes_TS(num_channels: int = 4, num_classes: int = 2, dataset: str = "Ph
         raise ValueError(dataset)
     return CNN_potes(c_in=num_channels, c_out=num_classes, layers=[8, 4], linear=linear,
                      dropout=dropout)
+
+
+def _potes_linear(sig_len, width: int, default: int) -> int:
+    return default if sig_len is None else potes_flat_features(sig_len, width=width)
+
+
+def CNN_potes_tenpercent_TS(num_channels: int = 4, num_classes: int = 2,
+                            sig_len: int | None = None) -> CNN_potes:
+    """Reference factory (models.py:352-353): layers [2,1], linear = 2492 (T = 2500)."""
+    return CNN_potes(c_in=num_channels, c_out=num_classes, layers=[2, 1],
+                     linear=_potes_linear(sig_len, 1, 2492))
+
+
+def CNN_potes_twopercent_TS(num_channels: int = 4, num_classes: int = 2,
+                            sig_len: int | None = None) -> CNN_potes:
+    """Reference factory (models.py:355-356): layers [1,1], linear = 2492 (T = 2500)."""
+    return CNN_potes(c_in=num_channels, c_out=num_classes, layers=[1, 1],
+                     linear=_potes_linear(sig_len, 1, 2492))
+
+
+def CNN_potes_big64and32_TS(num_channels: int = 4, num_classes: int = 2, dataset: str = "PhysioNet",
+                            dropout: float = 0.25, sig_len: int | None = None) -> CNN_potes:
+    """Reference factory (models.py:342-343): layers [64,32], linear = 79744 (T = 2500).  No
+    hand-written stack at this width: the conv branch runs through torch/MIOpen (``_fused``)."""
+    return CNN_potes(c_in=num_channels, c_out=num_classes, layers=[64, 32],
+                     linear=_potes_linear(sig_len, 32, 79744), dropout=dropout)
+
+
+def CNN_potes_big128and64_TS(num_channels: int = 4, num_classes: int = 2, dataset: str = "PhysioNet",
+                             dropout: float = 0.25, sig_len: int | None = None) -> CNN_potes:
+    """Reference factory (models.py:339-340): layers [128,64], linear = 159488 (T = 2500).  As
+    ``CNN_potes_big64and32_TS``: torch/MIOpen conv branch."""
+    return CNN_potes(c_in=num_channels, c_out=num_classes, layers=[128, 64],
+                     linear=_potes_linear(sig_len, 64, 159488), dropout=dropout)
 
 
 def _res_block(c_in: int, c_out: int, pool: bool = False) -> nn.Sequential:

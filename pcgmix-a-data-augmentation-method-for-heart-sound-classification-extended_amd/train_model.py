@@ -280,17 +280,41 @@ def selc_turning_point(args) -> int:
     return args.num_epochs + 1
 
 
+# train_model.py:341-358: the ResNet9-1D size ladder, args.model -> filters
+RESNET9_LADDER = {
+    "resnet9-5k": (2, 4, 8, 16), "resnet9-15k": (4, 8, 16, 32), "resnet9-50k": (8, 16, 32, 64),
+    "resnet9-150k": (16, 32, 64, 128), "resnet9-600k": (32, 64, 128, 256),
+    "resnet9-1.4m": (64, 128, 192, 384), "resnet9-2.3m": (64, 128, 256, 512),
+    "resnet9-5m": (96, 192, 384, 768), "resnet9-9m": (128, 256, 512, 1024),
+}
+# train_model.py:359-370: the Potes size ladder, args.model -> (factory, takes dataset, extra kwargs)
+POTES_LADDER = {
+    "Potes": ("CNN_potes_TS", True, {}),
+    "Potes(noDropout)": ("CNN_potes_TS", True, {"dropout": 0.0}),
+    "PotesBig64and32": ("CNN_potes_big64and32_TS", True, {}),
+    "PotesBig128and64": ("CNN_potes_big128and64_TS", True, {}),
+    "Potes0.1": ("CNN_potes_tenpercent_TS", False, {}),
+    "Potes0.02": ("CNN_potes_twopercent_TS", False, {}),
+}
+
+
 def build_model(args) -> nn.Module:
-    """The three models of the hot path (train_model.py:296, 338, 360), head sized for
-    ``args.sig_len`` (the reference hard-codes T = 2500)."""
+    """The models of the hot path (train_model.py:296, 337-370: 'Potes', 'resnet9' and the two
+    model-size ladders around them), head sized for ``args.sig_len`` (the reference hard-codes
+    T = 2500).  'Potes', 'Potes(noDropout)', 'Potes0.1' and 'Potes0.02' run their conv branch on the
+    hand-written HIP stacks; the two 'PotesBig*' models and the ResNet9 widths the BatchNorm kernels
+    do not take run through torch/MIOpen, with the warnings those paths already give."""
     sig_len = getattr(args, "sig_len", 2500)
     if args.dataset in SPECTROGRAM_DATASETS:
         if args.model != "resnet9":
             raise NotImplementedError(args.model)
         return models2d.ResNet9(num_classes=args.num_classes)
-    if args.model == "Potes":
-        m = models.CNN_potes_TS(num_channels=args.num_channels, num_classes=args.num_classes,
-                                dataset=args.dataset, sig_len=None if sig_len == 2500 else sig_len)
+    if args.model in POTES_LADDER:
+        factory, takes_dataset, kw = POTES_LADDER[args.model]
+        kw = dict(kw, sig_len=None if sig_len == 2500 else sig_len)
+        if takes_dataset:
+            kw["dataset"] = args.dataset
+        m = getattr(models, factory)(num_channels=args.num_channels, num_classes=args.num_classes, **kw)
         # cnn2..cnn4 are never called (reference models.py:444-455): their grads stay None in
         # the reference, so Adam and the clipper skip them; freezing them is equivalent and
         # keeps them out of the DDP reducer
@@ -301,6 +325,11 @@ def build_model(args) -> nn.Module:
     if args.model == "resnet9":
         return models.ResNet9(in_channels=args.num_channels, num_classes=args.num_classes,
                               linear=models.resnet9_flat_features(sig_len))
+    if args.model in RESNET9_LADDER:
+        filters = RESNET9_LADDER[args.model]
+        return models.ResNet9(in_channels=args.num_channels, num_classes=args.num_classes,
+                              filters=filters,
+                              linear=models.resnet9_flat_features(sig_len, filters[-1]))
     raise NotImplementedError(f"model {args.model!r} is outside the PCGmix hot path")
 
 
