@@ -864,11 +864,12 @@ int pcgmix_mix_kernel_name(int B, int C, int T, int n_knots, int zero_rect, int 
                            int buf_len);
 
 /* ------------------------------------------------------------------------------------------
- * BatchNorm (training mode) + ReLU + MaxPool of a ResNet9 block, channels innermost.  [device]
+ * BatchNorm + ReLU + MaxPool of a ResNet9 block, channels innermost.               [device]
  *
  * Replaces nn.BatchNorm1d/2d -> nn.ReLU -> nn.MaxPool1d/2d of conv_block (models.py:468-473,
  * models2d.py:13-19) and their autograd.  y is the convolution output stored NHWC: (B, H, W, C)
- * row-major (H = 1 for the 1D network), C % 4 == 0 and 256 % (C / 4) == 0 (64 ... 1024).
+ * row-major (H = 1 for the 1D network); C is 2 or a multiple of 4 up to 1024
+ * (pcgmix_bnrp_supported), which covers every width of the reference's ResNet9 size ladder.
  *   forward : batch mean / biased variance per channel -> z (B, H/ph, W/pw, C) =
  *             maxpool_{ph x pw}(relu(gamma * (y - mean) / sqrt(var + eps) + beta)) [+ skip];
  *             ph = pw = 1: no pooling.  skip (shape of z, or NULL): the residual connection of
@@ -877,9 +878,12 @@ int pcgmix_mix_kernel_name(int B, int C, int T, int n_knots, int zero_rect, int 
  *             running_var (may be NULL) are updated in place with `momentum` (unbiased variance).
  *   backward: dz (shape of z) -> dx (shape of y), dgamma, dbeta (C each).  The ReLU mask and the
  *             pooling arg-max (first maximum) are recomputed from y.
- * workspace: pcgmix_bnrp_workspace_floats(B, H, W, C) floats.  All pointers 16-byte aligned.
+ * workspace: pcgmix_bnrp_workspace_floats(B, H, W, C) floats.  All pointers 16-byte aligned
+ * (8-byte for C = 2).
  * Each direction reads y twice and writes its output once; reductions are fixed-order.
  */
+/* 1 for the channel counts the kernels take, else 0.  Host only: no device is touched. */
+int pcgmix_bnrp_supported(int C);
 long long pcgmix_bnrp_workspace_floats(int B, int H, int W, int C);
 /* mean_shift (C, may be NULL): a per-channel constant left out of y — the convolution's bias, which
  * the normalisation cancels — added to the batch mean in the running-mean update only;
@@ -895,6 +899,27 @@ int pcgmix_bnrp_bwd_f32(const float* y, const float* dz, const float* gamma, con
                         const float* mean, const float* invstd, float* dx, float* dgamma,
                         float* dbeta, float* dzero, float* workspace, int B, int H, int W, int C,
                         int ph, int pw, pcgmix_stream_t stream);
+/* Eval mode: the same block with BatchNorm on its running statistics, as the reference's model runs
+ * in test_data_accuracy (train_model.py:591-670) and in the frozen saliency pass
+ * (saliency.py:26-61) after model.eval(): nn.BatchNorm1d/2d (eval) -> nn.ReLU -> nn.MaxPool1d/2d
+ * of conv_block (models.py:468-473, models2d.py:13-19).
+ *   z = maxpool_{ph x pw}(relu(gamma * (y - (running_mean - conv_bias)) / sqrt(running_var + eps)
+ *       + beta)) [+ skip]
+ * conv_bias (C, may be NULL): the convolution's bias when it was left out of y.  One launch, no
+ * workspace; the running statistics are read only.  Shapes, channel counts and alignment as above;
+ * conv_bias and skip may be NULL.                                                              */
+int pcgmix_bnrp_eval_fwd_f32(const float* y, const float* gamma, const float* beta,
+                             const float* running_mean, const float* running_var, float eps,
+                             const float* conv_bias, const float* skip, float* z, int B, int H,
+                             int W, int C, int ph, int pw, pcgmix_stream_t stream);
+/* The input gradient of the above (replaces the autograd of the same three modules in the frozen
+ * pass, saliency.py:26-61): dx (shape of y) = gamma / sqrt(running_var + eps) * dz at the FIRST
+ * maximum of each window where the activation is > 0, exact zeros everywhere else, the positions
+ * no window covers included.  One launch, no reduction.  The gradient of skip is dz itself.     */
+int pcgmix_bnrp_eval_bwd_f32(const float* y, const float* dz, const float* gamma, const float* beta,
+                             const float* running_mean, const float* running_var, float eps,
+                             const float* conv_bias, float* dx, int B, int H, int W, int C, int ph,
+                             int pw, pcgmix_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * The paper's 1D comparison augmentations.                                        [device]

@@ -167,6 +167,11 @@ SIGNATURES = {
                                      _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr]),
     "pcgmix_bnrp_bwd_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int,
                                      _c_int, _c_int, _c_int, _c_int, _c_int, _ptr]),
+    "pcgmix_bnrp_supported": (_c_int, [_c_int]),
+    "pcgmix_bnrp_eval_fwd_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _c_float, _ptr, _ptr, _ptr, _c_int,
+                                          _c_int, _c_int, _c_int, _c_int, _c_int, _ptr]),
+    "pcgmix_bnrp_eval_bwd_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_float, _ptr, _ptr, _c_int,
+                                          _c_int, _c_int, _c_int, _c_int, _c_int, _ptr]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
-// pcgmix_bnrp.hip — BatchNorm (training) + ReLU + MaxPool of the ResNet9 blocks as fused NHWC
-// kernels (gfx950).
+// pcgmix_bnrp.hip — BatchNorm + ReLU + MaxPool of the ResNet9 blocks as fused NHWC kernels
+// (gfx950): training mode (forward + backward) and eval mode (forward + input gradient).
 //
 // Reference: models.py:468-473 / models2d.py:13-19 (conv_block: Conv + BatchNorm + ReLU [+ MaxPool]).
 // The convolutions run at ~130 TFLOP/s fp32 through MIOpen's implicit-GEMM kernels (84 % of the
@@ -14,74 +14,110 @@
 //   backward  bnrp_bwd_reduce_kernel one read of y, dz -> sums of dy and dy * xhat per channel
 //             bn_bwd_finalize_kernel dgamma, dbeta, the two means BatchNorm's dx needs
 //             bnrp_bwd_apply_kernel  one read of y, dz -> dx (one write)
+//   eval      bnrp_eval_fwd_kernel   one read of y  -> z, scale and shift from the running statistics
+//             bnrp_eval_bwd_kernel   one read of y, dz -> dx = scale * dz at the arg-max (one write)
 //
 // The ReLU mask and the pooling arg-max are recomputed from y (first maximum wins, as in torch's
 // max_pool), so nothing but y, mean and 1/std is kept for backward.  Five passes instead of ten.
 // All reductions are fixed-order (deterministic).  HBM-bound: 4 bytes per element per pass.
+//
+// Channel counts: a thread owns one vector of a row's channels (V = float4: Q = C / 4 vectors per
+// row; V = float2 for C = 2: Q = 1) and keeps it across the grid stride, so every stride must be a
+// multiple of Q.  A block therefore has A = (256 / Q) * Q threads: 256 where Q divides 256, the
+// largest multiple of Q below it otherwise (C = 96: 240, C = 768: 192), and all strides and the
+// LDS reduction run over A.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include <cmath>
+#include <initializer_list>
 
 #include "pcgmix_kernels.h"
 
 namespace pcgmix {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
-constexpr int kBnThreads = 256;
+typedef float f2 __attribute__((ext_vector_type(2)));
+constexpr int kBnThreads = 256;       // most threads of a block (LDS is sized for it)
 constexpr int kBnMaxBlocks = 1024;
+constexpr int kBnMaxC = 1024;         // widest row: 256 float4
 constexpr int kFinCh = 16;            // channels per finalize block (x 16 partial-row lanes)
 
 struct BnShape {
-  int B, H, W, C, ph, pw, Ho, Wo, Q;   // Q = C / 4 float4 per row; kBnThreads % Q == 0
+  int B, H, W, C, ph, pw, Ho, Wo;
+  int Q;   // vectors per row (C / 4; 1 for C = 2)
+  int A;   // threads per block: (kBnThreads / Q) * Q
 };
 
-__device__ __forceinline__ f4 f4_fma(f4 a, f4 b, f4 c) {
-  return f4{fmaf(a.x, b.x, c.x), fmaf(a.y, b.y, c.y), fmaf(a.z, b.z, c.z), fmaf(a.w, b.w, c.w)};
+template <typename V>
+constexpr int kLanes = (int)(sizeof(V) / sizeof(float));
+
+template <typename V>
+__device__ __forceinline__ V vsplat(float x) {
+  V v;
+#pragma unroll
+  for (int e = 0; e < kLanes<V>; ++e) v[e] = x;
+  return v;
 }
 
-// Sum the per-thread float4 values of the threads that share a channel quad (tid % Q) in a fixed
-// order and let thread q < Q write the result for quad q.
-__device__ __forceinline__ void quad_reduce_store(f4 a, f4 b, int Q, f4* lds, float* out0,
+template <typename V>
+__device__ __forceinline__ V vfma(V a, V b, V c) {
+  V r;
+#pragma unroll
+  for (int e = 0; e < kLanes<V>; ++e) r[e] = fmaf(a[e], b[e], c[e]);
+  return r;
+}
+
+// the vector of channel group q of a per-channel array
+template <typename V>
+__device__ __forceinline__ V vchan(const float* __restrict__ p, int q) {
+  return *reinterpret_cast<const V*>(p + kLanes<V> * q);
+}
+
+// Sum the per-thread vectors of the threads that share a channel group (tid % Q) in a fixed
+// order and let thread q < Q write the result for group q.
+template <typename V>
+__device__ __forceinline__ void quad_reduce_store(V a, V b, int Q, int A, V* lds, float* out0,
                                                   float* out1) {
   const int tid = threadIdx.x;
   lds[tid] = a;
   lds[kBnThreads + tid] = b;
   __syncthreads();
   if (tid < Q) {
-    f4 sa = lds[tid], sb = lds[kBnThreads + tid];
-    for (int j = tid + Q; j < kBnThreads; j += Q) {
+    V sa = lds[tid], sb = lds[kBnThreads + tid];
+    for (int j = tid + Q; j < A; j += Q) {
       sa += lds[j];
       sb += lds[kBnThreads + j];
     }
-    *reinterpret_cast<f4*>(out0 + 4 * tid) = sa;
-    *reinterpret_cast<f4*>(out1 + 4 * tid) = sb;
+    *reinterpret_cast<V*>(out0 + kLanes<V> * tid) = sa;
+    *reinterpret_cast<V*>(out1 + kLanes<V> * tid) = sb;
   }
 }
 
 // ------------------------------------------------------------------------------------ forward
-__global__ __launch_bounds__(kBnThreads) void bn_stats_kernel(const f4* __restrict__ y,
-                                                              long long n4, int Q,
+template <typename V>
+__global__ __launch_bounds__(kBnThreads) void bn_stats_kernel(const V* __restrict__ y,
+                                                              long long n4, int Q, int A,
                                                               float* __restrict__ partial, int C) {
-  __shared__ f4 lds[2 * kBnThreads];
-  f4 s = {0.f, 0.f, 0.f, 0.f}, ss = {0.f, 0.f, 0.f, 0.f};
-  const long long stride = (long long)gridDim.x * kBnThreads;     // multiple of Q
-  long long i = (long long)blockIdx.x * kBnThreads + threadIdx.x;
+  __shared__ V lds[2 * kBnThreads];
+  V s = vsplat<V>(0.f), ss = vsplat<V>(0.f);
+  const long long stride = (long long)gridDim.x * A;              // multiple of Q
+  long long i = (long long)blockIdx.x * A + threadIdx.x;
   for (; i + 3 * stride < n4; i += 4 * stride) {   // four loads in flight per lane (a pure reader
-    const f4 v0 = y[i], v1 = y[i + stride], v2 = y[i + 2 * stride], v3 = y[i + 3 * stride];
-    s += v0; ss = f4_fma(v0, v0, ss);               // has no store to hide a load-wait-load chain behind)
-    s += v1; ss = f4_fma(v1, v1, ss);
-    s += v2; ss = f4_fma(v2, v2, ss);
-    s += v3; ss = f4_fma(v3, v3, ss);
+    const V v0 = y[i], v1 = y[i + stride], v2 = y[i + 2 * stride], v3 = y[i + 3 * stride];
+    s += v0; ss = vfma(v0, v0, ss);                 // has no store to hide a load-wait-load chain behind)
+    s += v1; ss = vfma(v1, v1, ss);
+    s += v2; ss = vfma(v2, v2, ss);
+    s += v3; ss = vfma(v3, v3, ss);
   }
   for (; i < n4; i += stride) {
-    const f4 v = y[i];
+    const V v = y[i];
     s += v;
-    ss = f4_fma(v, v, ss);
+    ss = vfma(v, v, ss);
   }
   float* p = partial + (size_t)blockIdx.x * 2 * C;
-  quad_reduce_store(s, ss, Q, lds, p, p + C);
+  quad_reduce_store(s, ss, Q, A, lds, p, p + C);
 }
 
 // Sum of the per-block partials of 16 channels: 16 lanes per channel stride over the blocks in
@@ -153,23 +189,78 @@ __global__ __launch_bounds__(kFinCh * 16) void bn_finalize_kernel(
   }
 }
 
-// relu(scale * y + shift) at the ph x pw window of pooled position (b, ho, wo), channel quad q;
+// The affine map in front of the ReLU for channel group q.  Training: from the batch statistics
+// the finalize kernel left.
+template <typename V>
+struct BnAffine {
+  V scale, shift, mu, is;
+};
+
+template <typename V>
+__device__ __forceinline__ BnAffine<V> train_affine(const float* __restrict__ gamma,
+                                                    const float* __restrict__ beta,
+                                                    const float* __restrict__ mean,
+                                                    const float* __restrict__ invstd, int q) {
+  BnAffine<V> a;
+  const V g = vchan<V>(gamma, q), bt = vchan<V>(beta, q);
+  a.mu = vchan<V>(mean, q);
+  a.is = vchan<V>(invstd, q);
+  a.scale = g * a.is;
+  a.shift = bt - a.mu * a.scale;
+  return a;
+}
+
+// Eval: from the running statistics; `bias` (optional) is the convolution's bias that was left out
+// of y, i.e. BN(y + bias) with the running mean == BN(y) with (running mean - bias).
+template <typename V>
+__device__ __forceinline__ BnAffine<V> eval_affine(const float* __restrict__ gamma,
+                                                   const float* __restrict__ beta,
+                                                   const float* __restrict__ running_mean,
+                                                   const float* __restrict__ running_var,
+                                                   const float* __restrict__ bias, float eps, int q) {
+  BnAffine<V> a;
+  const V g = vchan<V>(gamma, q), bt = vchan<V>(beta, q), rv = vchan<V>(running_var, q);
+  a.mu = vchan<V>(running_mean, q);
+  if (bias) a.mu -= vchan<V>(bias, q);
+#pragma unroll
+  for (int e = 0; e < kLanes<V>; ++e) a.is[e] = 1.f / sqrtf(rv[e] + eps);
+  a.scale = g * a.is;
+  a.shift = bt - a.mu * a.scale;
+  return a;
+}
+
+// row of pooled outputs -> (b, ho, wo)
+struct PoolPos {
+  long long b;
+  int ho, wo;
+};
+__device__ __forceinline__ PoolPos pool_pos(const BnShape& s, long long orow) {
+  PoolPos p;
+  p.wo = (int)(orow % s.Wo);
+  const long long t = orow / s.Wo;
+  p.ho = (int)(t % s.Ho);
+  p.b = t / s.Ho;
+  return p;
+}
+
+// relu(scale * y + shift) at the ph x pw window of pooled position (b, ho, wo), channel group q;
 // returns the maximum and (through *arg) the index i * pw + j of its FIRST occurrence.
 // If `raw` is given it receives y itself at that first maximum (what the backward's xhat needs:
 // re-reading it by index is a dependent scalar gather per channel).
-__device__ __forceinline__ f4 window_max(const f4* __restrict__ y, const BnShape& s, long long b,
-                                         int ho, int wo, int q, f4 scale, f4 shift, int arg[4],
-                                         f4* raw = nullptr) {
-  f4 best = {-1.f, -1.f, -1.f, -1.f};                 // relu output is >= 0: any value beats this
-  f4 vb = {0.f, 0.f, 0.f, 0.f};
+template <typename V>
+__device__ __forceinline__ V window_max(const V* __restrict__ y, const BnShape& s, long long b,
+                                        int ho, int wo, int q, V scale, V shift,
+                                        int (&arg)[kLanes<V>], V* raw = nullptr) {
+  V best = vsplat<V>(-1.f);                           // relu output is >= 0: any value beats this
+  V vb = vsplat<V>(0.f);
   for (int i = 0; i < s.ph; ++i)
     for (int j = 0; j < s.pw; ++j) {
       const long long row = (b * s.H + (ho * s.ph + i)) * s.W + (wo * s.pw + j);
-      const f4 v = y[row * s.Q + q];
-      f4 a = f4_fma(v, scale, shift);
+      const V v = y[row * s.Q + q];
+      V a = vfma(v, scale, shift);
       const int idx = i * s.pw + j;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
+      for (int e = 0; e < kLanes<V>; ++e) {
         const float r = a[e] > 0.f ? a[e] : 0.f;
         if (r > best[e]) {
           best[e] = r;
@@ -182,63 +273,72 @@ __device__ __forceinline__ f4 window_max(const f4* __restrict__ y, const BnShape
   return best;
 }
 
-__global__ __launch_bounds__(kBnThreads) void bnrp_apply_kernel(
-    const f4* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ mean, const float* __restrict__ invstd, const f4* __restrict__ skip,
-    f4* __restrict__ z, BnShape s) {
-  const int q = threadIdx.x % s.Q;                    // fixed per thread: strides are multiples of Q
-  const f4 g = *reinterpret_cast<const f4*>(gamma + 4 * q), bt = *reinterpret_cast<const f4*>(beta + 4 * q);
-  const f4 mu = *reinterpret_cast<const f4*>(mean + 4 * q), is = *reinterpret_cast<const f4*>(invstd + 4 * q);
-  const f4 scale = g * is, shift = bt - mu * scale;
+// z = maxpool(relu(scale * y + shift)) [+ skip], any window
+template <typename V>
+__device__ __forceinline__ void apply_rows(const V* __restrict__ y, const V* __restrict__ skip,
+                                           V* __restrict__ z, const BnShape& s, int q, V scale,
+                                           V shift) {
   const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
-  const long long stride = (long long)gridDim.x * kBnThreads;
-  for (long long o = (long long)blockIdx.x * kBnThreads + threadIdx.x; o < n_out; o += stride) {
-    const long long orow = o / s.Q;
-    const int wo = (int)(orow % s.Wo);
-    const long long t = orow / s.Wo;
-    const int ho = (int)(t % s.Ho);
-    const long long b = t / s.Ho;
-    int arg[4];
-    f4 v = window_max(y, s, b, ho, wo, q, scale, shift, arg);
+  const long long stride = (long long)gridDim.x * s.A;
+  for (long long o = (long long)blockIdx.x * s.A + threadIdx.x; o < n_out; o += stride) {
+    const PoolPos p = pool_pos(s, o / s.Q);
+    int arg[kLanes<V>];
+    V v = window_max(y, s, p.b, p.ho, p.wo, q, scale, shift, arg);
     if (skip) v += skip[o];                           // residual connection (models.py:577, 581)
     z[o] = v;
   }
 }
 
+template <typename V>
+__global__ __launch_bounds__(kBnThreads) void bnrp_apply_kernel(
+    const V* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ mean, const float* __restrict__ invstd, const V* __restrict__ skip,
+    V* __restrict__ z, BnShape s) {
+  const int q = threadIdx.x % s.Q;                    // fixed per thread: strides are multiples of Q
+  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
+  apply_rows(y, skip, z, s, q, a.scale, a.shift);
+}
+
+template <typename V>
+__global__ __launch_bounds__(kBnThreads) void bnrp_eval_fwd_kernel(
+    const V* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ running_mean, const float* __restrict__ running_var,
+    const float* __restrict__ bias, float eps, const V* __restrict__ skip, V* __restrict__ z,
+    BnShape s) {
+  const int q = threadIdx.x % s.Q;
+  const BnAffine<V> a = eval_affine<V>(gamma, beta, running_mean, running_var, bias, eps, q);
+  apply_rows(y, skip, z, s, q, a.scale, a.shift);
+}
+
 // ------------------------------------------------------------------------------------ backward
+template <typename V>
 __global__ __launch_bounds__(kBnThreads) void bnrp_bwd_reduce_kernel(
-    const f4* __restrict__ y, const f4* __restrict__ dz, const float* __restrict__ gamma,
+    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ mean,
     const float* __restrict__ invstd, float* __restrict__ partial, BnShape s) {
-  __shared__ f4 lds[2 * kBnThreads];
+  __shared__ V lds[2 * kBnThreads];
   const int q = threadIdx.x % s.Q;
-  const f4 g = *reinterpret_cast<const f4*>(gamma + 4 * q), bt = *reinterpret_cast<const f4*>(beta + 4 * q);
-  const f4 mu = *reinterpret_cast<const f4*>(mean + 4 * q), is = *reinterpret_cast<const f4*>(invstd + 4 * q);
-  const f4 scale = g * is, shift = bt - mu * scale;
-  f4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
+  V s1 = vsplat<V>(0.f), s2 = vsplat<V>(0.f);
   const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
-  const long long stride = (long long)gridDim.x * kBnThreads;
-  for (long long o = (long long)blockIdx.x * kBnThreads + threadIdx.x; o < n_out; o += stride) {
-    const long long orow = o / s.Q;
-    const int wo = (int)(orow % s.Wo);
-    const long long t = orow / s.Wo;
-    const int ho = (int)(t % s.Ho);
-    const long long b = t / s.Ho;
-    int arg[4];
-    f4 vraw;
-    const f4 best = window_max(y, s, b, ho, wo, q, scale, shift, arg, &vraw);
-    const f4 d = dz[o];
+  const long long stride = (long long)gridDim.x * s.A;
+  for (long long o = (long long)blockIdx.x * s.A + threadIdx.x; o < n_out; o += stride) {
+    const PoolPos p = pool_pos(s, o / s.Q);
+    int arg[kLanes<V>];
+    V vraw;
+    const V best = window_max(y, s, p.b, p.ho, p.wo, q, a.scale, a.shift, arg, &vraw);
+    const V d = dz[o];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
+    for (int e = 0; e < kLanes<V>; ++e) {
       if (best[e] > 0.f) {                            // ReLU passes the gradient at the arg-max
-        const float xh = (vraw[e] - mu[e]) * is[e];   // xhat at the arg-max
+        const float xh = (vraw[e] - a.mu[e]) * a.is[e];   // xhat at the arg-max
         s1[e] += d[e];
         s2[e] = fmaf(d[e], xh, s2[e]);
       }
     }
   }
   float* p = partial + (size_t)blockIdx.x * 2 * s.C;
-  quad_reduce_store(s1, s2, s.Q, lds, p, p + s.C);
+  quad_reduce_store(s1, s2, s.Q, s.A, lds, p, p + s.C);
 }
 
 __global__ __launch_bounds__(kFinCh * 16) void bn_bwd_finalize_kernel(
@@ -256,84 +356,104 @@ __global__ __launch_bounds__(kFinCh * 16) void bn_bwd_finalize_kernel(
   coef[C + c] = (float)(s2 / n_rows);      // mean of dy * xhat
 }
 
-// dx = gamma * invstd * (dy - mean(dy) - xhat * mean(dy * xhat)), dy = dz at the window's arg-max
-// where the activation is positive, 0 elsewhere.  One thread per (window, channel quad): every y
-// of the window is read once and every dx written once.  Positions that no window covers (odd
-// lengths: H % ph rows, W % pw columns) have dy = 0 and are written by the tail loop.
-__global__ __launch_bounds__(kBnThreads) void bnrp_bwd_apply_kernel(
-    const f4* __restrict__ y, const f4* __restrict__ dz, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ mean,
-    const float* __restrict__ invstd, const float* __restrict__ coef, f4* __restrict__ dx,
-    BnShape s) {
-  const int q = threadIdx.x % s.Q;
-  const f4 g = *reinterpret_cast<const f4*>(gamma + 4 * q), bt = *reinterpret_cast<const f4*>(beta + 4 * q);
-  const f4 mu = *reinterpret_cast<const f4*>(mean + 4 * q), is = *reinterpret_cast<const f4*>(invstd + 4 * q);
-  const f4 c1 = *reinterpret_cast<const f4*>(coef + 4 * q), c2 = *reinterpret_cast<const f4*>(coef + s.C + 4 * q);
-  const f4 scale = g * is, shift = bt - mu * scale;
-  const long long stride = (long long)gridDim.x * kBnThreads;
-  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
-  for (long long o = (long long)blockIdx.x * kBnThreads + threadIdx.x; o < n_out; o += stride) {
-    const long long orow = o / s.Q;
-    const int wo = (int)(orow % s.Wo);
-    const long long t = orow / s.Wo;
-    const int ho = (int)(t % s.Ho);
-    const long long b = t / s.Ho;
-    // pass 1 over the window: arg-max of relu(a) (first maximum)
-    f4 best = {-1.f, -1.f, -1.f, -1.f};
-    int arg[4] = {0, 0, 0, 0};
-    for (int i = 0; i < s.ph; ++i)
-      for (int j = 0; j < s.pw; ++j) {
-        const long long row = (b * s.H + (ho * s.ph + i)) * s.W + (wo * s.pw + j);
-        const f4 a = f4_fma(y[row * s.Q + q], scale, shift);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float r = a[e] > 0.f ? a[e] : 0.f;
-          if (r > best[e]) {
-            best[e] = r;
-            arg[e] = i * s.pw + j;
-          }
-        }
-      }
-    const f4 d = dz[o];
-    // pass 2 (the window is in cache): dx for every position
-    for (int i = 0; i < s.ph; ++i)
-      for (int j = 0; j < s.pw; ++j) {
-        const long long row = (b * s.H + (ho * s.ph + i)) * s.W + (wo * s.pw + j);
-        const f4 v = y[row * s.Q + q];
-        f4 dy = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-          if (best[e] > 0.f && arg[e] == i * s.pw + j) dy[e] = d[e];
-        const f4 xh = (v - mu) * is;
-        dx[row * s.Q + q] = scale * (dy - c1 - xh * c2);
-      }
-  }
-  // uncovered positions: columns w >= Wo*pw of every row, then rows h >= Ho*ph of the covered columns
+// Calls f(e) once for the vector index e of every position that no window covers (odd lengths):
+// columns w >= Wo*pw of every row, then rows h >= Ho*ph of the covered columns.
+template <typename F>
+__device__ __forceinline__ void for_uncovered(const BnShape& s, int q, F f) {
+  const long long stride = (long long)gridDim.x * s.A;
   const int wc = s.Wo * s.pw, hc = s.Ho * s.ph;
   const long long n_col = (long long)s.B * s.H * (s.W - wc) * s.Q;
-  for (long long i = (long long)blockIdx.x * kBnThreads + threadIdx.x; i < n_col; i += stride) {
+  for (long long i = (long long)blockIdx.x * s.A + threadIdx.x; i < n_col; i += stride) {
     const long long r = i / s.Q;
     const int w = wc + (int)(r % (s.W - wc));
     const long long bh = r / (s.W - wc);                           // b * H + h
-    const long long e = (bh * s.W + w) * s.Q + q;
-    const f4 xh = (y[e] - mu) * is;
-    dx[e] = scale * (-c1 - xh * c2);
+    f((bh * s.W + w) * s.Q + q);
   }
   const long long n_row = (long long)s.B * (s.H - hc) * wc * s.Q;
-  for (long long i = (long long)blockIdx.x * kBnThreads + threadIdx.x; i < n_row; i += stride) {
+  for (long long i = (long long)blockIdx.x * s.A + threadIdx.x; i < n_row; i += stride) {
     const long long r = i / s.Q;
     const int w = (int)(r % wc);
     const long long t = r / wc;
     const int h = hc + (int)(t % (s.H - hc));
     const long long b = t / (s.H - hc);
-    const long long e = ((b * s.H + h) * s.W + w) * s.Q + q;
-    const f4 xh = (y[e] - mu) * is;
-    dx[e] = scale * (-c1 - xh * c2);
+    f(((b * s.H + h) * s.W + w) * s.Q + q);
   }
 }
 
+// dx = gamma * invstd * (dy - mean(dy) - xhat * mean(dy * xhat)), dy = dz at the window's arg-max
+// where the activation is positive, 0 elsewhere.  One thread per (window, channel group): every y
+// of the window is read once and every dx written once.  Positions that no window covers have
+// dy = 0 and are written by the tail loops.
+template <typename V>
+__global__ __launch_bounds__(kBnThreads) void bnrp_bwd_apply_kernel(
+    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ mean,
+    const float* __restrict__ invstd, const float* __restrict__ coef, V* __restrict__ dx,
+    BnShape s) {
+  const int q = threadIdx.x % s.Q;
+  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
+  const V mu = a.mu, is = a.is, scale = a.scale, shift = a.shift;
+  const V c1 = vchan<V>(coef, q), c2 = vchan<V>(coef + s.C, q);
+  const long long stride = (long long)gridDim.x * s.A;
+  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
+  for (long long o = (long long)blockIdx.x * s.A + threadIdx.x; o < n_out; o += stride) {
+    const PoolPos p = pool_pos(s, o / s.Q);
+    // pass 1 over the window: arg-max of relu(a) (first maximum)
+    int arg[kLanes<V>] = {};
+    const V best = window_max(y, s, p.b, p.ho, p.wo, q, scale, shift, arg);
+    const V d = dz[o];
+    // pass 2 (the window is in cache): dx for every position
+    for (int i = 0; i < s.ph; ++i)
+      for (int j = 0; j < s.pw; ++j) {
+        const long long row = (p.b * s.H + (p.ho * s.ph + i)) * s.W + (p.wo * s.pw + j);
+        const V v = y[row * s.Q + q];
+        V dy = vsplat<V>(0.f);
+#pragma unroll
+        for (int e = 0; e < kLanes<V>; ++e)
+          if (best[e] > 0.f && arg[e] == i * s.pw + j) dy[e] = d[e];
+        const V xh = (v - mu) * is;
+        dx[row * s.Q + q] = scale * (dy - c1 - xh * c2);
+      }
+  }
+  for_uncovered(s, q, [&](long long e) {
+    const V xh = (y[e] - mu) * is;
+    dx[e] = scale * (-c1 - xh * c2);
+  });
+}
+
+// Eval-mode input gradient: the statistics are constants, so dx = scale * dz at the window's first
+// maximum where the activation is positive and an exact 0 everywhere else (uncovered positions
+// included).  No reduction: one read of y and dz, one write of dx.
+template <typename V>
+__global__ __launch_bounds__(kBnThreads) void bnrp_eval_bwd_kernel(
+    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ running_mean,
+    const float* __restrict__ running_var, const float* __restrict__ bias, float eps,
+    V* __restrict__ dx, BnShape s) {
+  const int q = threadIdx.x % s.Q;
+  const BnAffine<V> a = eval_affine<V>(gamma, beta, running_mean, running_var, bias, eps, q);
+  const long long stride = (long long)gridDim.x * s.A;
+  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
+  for (long long o = (long long)blockIdx.x * s.A + threadIdx.x; o < n_out; o += stride) {
+    const PoolPos p = pool_pos(s, o / s.Q);
+    int arg[kLanes<V>] = {};
+    const V best = window_max(y, s, p.b, p.ho, p.wo, q, a.scale, a.shift, arg);
+    const V d = dz[o];
+    for (int i = 0; i < s.ph; ++i)
+      for (int j = 0; j < s.pw; ++j) {
+        const long long row = (p.b * s.H + (p.ho * s.ph + i)) * s.W + (p.wo * s.pw + j);
+        V g = vsplat<V>(0.f);
+#pragma unroll
+        for (int e = 0; e < kLanes<V>; ++e)
+          if (best[e] > 0.f && arg[e] == i * s.pw + j) g[e] = a.scale[e] * d[e];
+        dx[row * s.Q + q] = g;
+      }
+  }
+  for_uncovered(s, q, [&](long long e) { dx[e] = vsplat<V>(0.f); });
+}
+
 // ------------------------------------------------------------------------------------ fast paths
-// The three streaming kernels above, specialised for the window shapes ResNet9 uses ((1,1), (1,2),
+// The streaming kernels above, specialised for the window shapes ResNet9 uses ((1,1), (1,2),
 // (2,2)) and index ranges that fit 32 bits.  The generic versions walk the window in a loop with
 // runtime bounds: one global load, one s_waitcnt vmcnt(0), the next load — and the backward
 // reduction then waits once more for dz.  A forward pass hides that behind its store (fire and
@@ -341,7 +461,7 @@ __global__ __launch_bounds__(kBnThreads) void bnrp_bwd_apply_kernel(
 // apply reaches 6.0 (profiles/r2_resnet1d_step_kernels.csv).  Here every thread handles TWO pooled
 // rows per iteration and issues all of their loads (2 x PH x PW of y, 2 of dz) before the first
 // use; row -> (b, ho, wo) is 32-bit arithmetic (the generic 64-bit divisions are ~100 instructions
-// each).
+// each).  A block covers R = A / Q pooled rows per step.
 template <int PH, int PW>
 __device__ __forceinline__ unsigned window_row(const BnShape& s, unsigned r) {
   const unsigned wo = r % (unsigned)s.Wo, t = r / (unsigned)s.Wo;
@@ -349,9 +469,9 @@ __device__ __forceinline__ unsigned window_row(const BnShape& s, unsigned r) {
   return (b * (unsigned)s.H + ho * PH) * (unsigned)s.W + wo * PW;      // first input row of the window
 }
 
-template <int PH, int PW>
-__device__ __forceinline__ void window_load(const f4* __restrict__ y, const BnShape& s, unsigned row0,
-                                            int q, f4 (&v)[PH * PW]) {
+template <int PH, int PW, typename V>
+__device__ __forceinline__ void window_load(const V* __restrict__ y, const BnShape& s, unsigned row0,
+                                            int q, V (&v)[PH * PW]) {
 #pragma unroll
   for (int i = 0; i < PH; ++i)
 #pragma unroll
@@ -361,14 +481,15 @@ __device__ __forceinline__ void window_load(const f4* __restrict__ y, const BnSh
 
 // window_max on registers: maximum of relu(scale * y + shift), index of its FIRST occurrence, and
 // y itself there.
-template <int N>
-__device__ __forceinline__ f4 window_best(const f4 (&v)[N], f4 scale, f4 shift, int (&arg)[4], f4* raw) {
-  f4 best = {-1.f, -1.f, -1.f, -1.f}, vb = {0.f, 0.f, 0.f, 0.f};
+template <int N, typename V>
+__device__ __forceinline__ V window_best(const V (&v)[N], V scale, V shift, int (&arg)[kLanes<V>],
+                                         V* raw) {
+  V best = vsplat<V>(-1.f), vb = vsplat<V>(0.f);
 #pragma unroll
   for (int k = 0; k < N; ++k) {
-    const f4 a = f4_fma(v[k], scale, shift);
+    const V a = vfma(v[k], scale, shift);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
+    for (int e = 0; e < kLanes<V>; ++e) {
       const float r = a[e] > 0.f ? a[e] : 0.f;
       if (r > best[e]) {
         best[e] = r;
@@ -381,104 +502,118 @@ __device__ __forceinline__ f4 window_best(const f4 (&v)[N], f4 scale, f4 shift, 
   return best;
 }
 
-template <int PH, int PW>
-__global__ __launch_bounds__(kBnThreads) void bnrp_apply_win_kernel(
-    const f4* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ mean, const float* __restrict__ invstd, const f4* __restrict__ skip,
-    f4* __restrict__ z, BnShape s) {
-  const int q = threadIdx.x % s.Q;
-  const unsigned R = kBnThreads / s.Q, rloc = threadIdx.x / s.Q;
-  const f4 g = *reinterpret_cast<const f4*>(gamma + 4 * q), bt = *reinterpret_cast<const f4*>(beta + 4 * q);
-  const f4 mu = *reinterpret_cast<const f4*>(mean + 4 * q), is = *reinterpret_cast<const f4*>(invstd + 4 * q);
-  const f4 scale = g * is, shift = bt - mu * scale;
+template <int PH, int PW, typename V>
+__device__ __forceinline__ void apply_win_rows(const V* __restrict__ y, const V* __restrict__ skip,
+                                               V* __restrict__ z, const BnShape& s, int q, V scale,
+                                               V shift) {
+  const unsigned R = s.A / s.Q, rloc = threadIdx.x / s.Q;
   const unsigned n_rows = (unsigned)s.B * s.Ho * s.Wo, stride = gridDim.x * R;
   for (unsigned r = blockIdx.x * R + rloc; r < n_rows; r += 2 * stride) {
     const bool two = r + stride < n_rows;
     const unsigned r2 = two ? r + stride : r;
-    f4 va[PH * PW], vb[PH * PW];
+    V va[PH * PW], vb[PH * PW];
     window_load<PH, PW>(y, s, window_row<PH, PW>(s, r), q, va);
     window_load<PH, PW>(y, s, window_row<PH, PW>(s, r2), q, vb);
-    f4 ka = {0.f, 0.f, 0.f, 0.f}, kb = ka;
+    V ka = vsplat<V>(0.f), kb = ka;
     if (skip) {
       ka = skip[(size_t)r * s.Q + q];
       kb = skip[(size_t)r2 * s.Q + q];
     }
-    int arg[4];
-    f4 raw;
+    int arg[kLanes<V>];
+    V raw;
     z[(size_t)r * s.Q + q] = window_best<PH * PW>(va, scale, shift, arg, &raw) + ka;
     if (two) z[(size_t)r2 * s.Q + q] = window_best<PH * PW>(vb, scale, shift, arg, &raw) + kb;
   }
 }
 
-template <int PH, int PW>
+template <int PH, int PW, typename V>
+__global__ __launch_bounds__(kBnThreads) void bnrp_apply_win_kernel(
+    const V* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ mean, const float* __restrict__ invstd, const V* __restrict__ skip,
+    V* __restrict__ z, BnShape s) {
+  const int q = threadIdx.x % s.Q;
+  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
+  apply_win_rows<PH, PW>(y, skip, z, s, q, a.scale, a.shift);
+}
+
+template <int PH, int PW, typename V>
+__global__ __launch_bounds__(kBnThreads) void bnrp_eval_fwd_win_kernel(
+    const V* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
+    const float* __restrict__ running_mean, const float* __restrict__ running_var,
+    const float* __restrict__ bias, float eps, const V* __restrict__ skip, V* __restrict__ z,
+    BnShape s) {
+  const int q = threadIdx.x % s.Q;
+  const BnAffine<V> a = eval_affine<V>(gamma, beta, running_mean, running_var, bias, eps, q);
+  apply_win_rows<PH, PW>(y, skip, z, s, q, a.scale, a.shift);
+}
+
+template <int PH, int PW, typename V>
 __global__ __launch_bounds__(kBnThreads) void bnrp_bwd_reduce_win_kernel(
-    const f4* __restrict__ y, const f4* __restrict__ dz, const float* __restrict__ gamma,
+    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ mean,
     const float* __restrict__ invstd, float* __restrict__ partial, BnShape s) {
-  __shared__ f4 lds[2 * kBnThreads];
+  __shared__ V lds[2 * kBnThreads];
   const int q = threadIdx.x % s.Q;
-  const unsigned R = kBnThreads / s.Q, rloc = threadIdx.x / s.Q;
-  const f4 g = *reinterpret_cast<const f4*>(gamma + 4 * q), bt = *reinterpret_cast<const f4*>(beta + 4 * q);
-  const f4 mu = *reinterpret_cast<const f4*>(mean + 4 * q), is = *reinterpret_cast<const f4*>(invstd + 4 * q);
-  const f4 scale = g * is, shift = bt - mu * scale;
-  f4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
+  const unsigned R = s.A / s.Q, rloc = threadIdx.x / s.Q;
+  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
+  const V mu = a.mu, is = a.is, scale = a.scale, shift = a.shift;
+  V s1 = vsplat<V>(0.f), s2 = vsplat<V>(0.f);
   const unsigned n_rows = (unsigned)s.B * s.Ho * s.Wo, stride = gridDim.x * R;
   for (unsigned r = blockIdx.x * R + rloc; r < n_rows; r += 2 * stride) {
     const bool two = r + stride < n_rows;
     const unsigned r2 = two ? r + stride : r;
-    f4 va[PH * PW], vb[PH * PW];
+    V va[PH * PW], vb[PH * PW];
     window_load<PH, PW>(y, s, window_row<PH, PW>(s, r), q, va);
     window_load<PH, PW>(y, s, window_row<PH, PW>(s, r2), q, vb);
-    const f4 da = dz[(size_t)r * s.Q + q];
-    f4 db = dz[(size_t)r2 * s.Q + q];
-    if (!two) db = f4{0.f, 0.f, 0.f, 0.f};
-    int arg[4];
-    f4 raw;
-    f4 best = window_best<PH * PW>(va, scale, shift, arg, &raw);
+    const V da = dz[(size_t)r * s.Q + q];
+    V db = dz[(size_t)r2 * s.Q + q];
+    if (!two) db = vsplat<V>(0.f);
+    int arg[kLanes<V>];
+    V raw;
+    V best = window_best<PH * PW>(va, scale, shift, arg, &raw);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
+    for (int e = 0; e < kLanes<V>; ++e) {
       const float d = best[e] > 0.f ? da[e] : 0.f;    // ReLU passes the gradient at the arg-max
       s1[e] += d;
       s2[e] = fmaf(d, (raw[e] - mu[e]) * is[e], s2[e]);
     }
     best = window_best<PH * PW>(vb, scale, shift, arg, &raw);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
+    for (int e = 0; e < kLanes<V>; ++e) {
       const float d = best[e] > 0.f ? db[e] : 0.f;
       s1[e] += d;
       s2[e] = fmaf(d, (raw[e] - mu[e]) * is[e], s2[e]);
     }
   }
   float* p = partial + (size_t)blockIdx.x * 2 * s.C;
-  quad_reduce_store(s1, s2, s.Q, lds, p, p + s.C);
+  quad_reduce_store(s1, s2, s.Q, s.A, lds, p, p + s.C);
 }
 
-template <int PH, int PW>
+template <int PH, int PW, typename V>
 __global__ __launch_bounds__(kBnThreads) void bnrp_bwd_apply_win_kernel(
-    const f4* __restrict__ y, const f4* __restrict__ dz, const float* __restrict__ gamma,
+    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ mean,
-    const float* __restrict__ invstd, const float* __restrict__ coef, f4* __restrict__ dx,
+    const float* __restrict__ invstd, const float* __restrict__ coef, V* __restrict__ dx,
     BnShape s) {
   const int q = threadIdx.x % s.Q;
-  const unsigned R = kBnThreads / s.Q, rloc = threadIdx.x / s.Q;
-  const f4 g = *reinterpret_cast<const f4*>(gamma + 4 * q), bt = *reinterpret_cast<const f4*>(beta + 4 * q);
-  const f4 mu = *reinterpret_cast<const f4*>(mean + 4 * q), is = *reinterpret_cast<const f4*>(invstd + 4 * q);
-  const f4 c1 = *reinterpret_cast<const f4*>(coef + 4 * q), c2 = *reinterpret_cast<const f4*>(coef + s.C + 4 * q);
-  const f4 scale = g * is, shift = bt - mu * scale;
+  const unsigned R = s.A / s.Q, rloc = threadIdx.x / s.Q;
+  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
+  const V mu = a.mu, is = a.is, scale = a.scale, shift = a.shift;
+  const V c1 = vchan<V>(coef, q), c2 = vchan<V>(coef + s.C, q);
   const unsigned n_rows = (unsigned)s.B * s.Ho * s.Wo, stride = gridDim.x * R;
-  auto emit = [&](const f4 (&v)[PH * PW], f4 d, unsigned row0) {
-    int arg[4] = {0, 0, 0, 0};
-    f4 raw;
-    const f4 best = window_best<PH * PW>(v, scale, shift, arg, &raw);
+  auto emit = [&](const V (&v)[PH * PW], V d, unsigned row0) {
+    int arg[kLanes<V>] = {};
+    V raw;
+    const V best = window_best<PH * PW>(v, scale, shift, arg, &raw);
 #pragma unroll
     for (int i = 0; i < PH; ++i)
 #pragma unroll
       for (int j = 0; j < PW; ++j) {
-        f4 dy = {0.f, 0.f, 0.f, 0.f};
+        V dy = vsplat<V>(0.f);
 #pragma unroll
-        for (int e = 0; e < 4; ++e)
+        for (int e = 0; e < kLanes<V>; ++e)
           if (best[e] > 0.f && arg[e] == i * PW + j) dy[e] = d[e];
-        const f4 xh = (v[i * PW + j] - mu) * is;
+        const V xh = (v[i * PW + j] - mu) * is;
         dx[(size_t)(row0 + (unsigned)i * (unsigned)s.W + (unsigned)j) * s.Q + q] = scale * (dy - c1 - xh * c2);
       }
   };
@@ -486,36 +621,58 @@ __global__ __launch_bounds__(kBnThreads) void bnrp_bwd_apply_win_kernel(
     const bool two = r + stride < n_rows;
     const unsigned r2 = two ? r + stride : r;
     const unsigned rowa = window_row<PH, PW>(s, r), rowb = window_row<PH, PW>(s, r2);
-    f4 va[PH * PW], vb[PH * PW];
+    V va[PH * PW], vb[PH * PW];
     window_load<PH, PW>(y, s, rowa, q, va);
     window_load<PH, PW>(y, s, rowb, q, vb);
-    const f4 da = dz[(size_t)r * s.Q + q], db = dz[(size_t)r2 * s.Q + q];
+    const V da = dz[(size_t)r * s.Q + q], db = dz[(size_t)r2 * s.Q + q];
     emit(va, da, rowa);
     if (two) emit(vb, db, rowb);
   }
   // uncovered positions (odd lengths), as in the generic kernel
-  const long long stride4 = (long long)gridDim.x * kBnThreads;
-  const int wc = s.Wo * s.pw, hc = s.Ho * s.ph;
-  const long long n_col = (long long)s.B * s.H * (s.W - wc) * s.Q;
-  for (long long i = (long long)blockIdx.x * kBnThreads + threadIdx.x; i < n_col; i += stride4) {
-    const long long r = i / s.Q;
-    const int w = wc + (int)(r % (s.W - wc));
-    const long long bh = r / (s.W - wc);
-    const long long e = (bh * s.W + w) * s.Q + q;
-    const f4 xh = (y[e] - mu) * is;
+  for_uncovered(s, q, [&](long long e) {
+    const V xh = (y[e] - mu) * is;
     dx[e] = scale * (-c1 - xh * c2);
+  });
+}
+
+template <int PH, int PW, typename V>
+__global__ __launch_bounds__(kBnThreads) void bnrp_eval_bwd_win_kernel(
+    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ running_mean,
+    const float* __restrict__ running_var, const float* __restrict__ bias, float eps,
+    V* __restrict__ dx, BnShape s) {
+  const int q = threadIdx.x % s.Q;
+  const unsigned R = s.A / s.Q, rloc = threadIdx.x / s.Q;
+  const BnAffine<V> a = eval_affine<V>(gamma, beta, running_mean, running_var, bias, eps, q);
+  const V scale = a.scale, shift = a.shift;
+  const unsigned n_rows = (unsigned)s.B * s.Ho * s.Wo, stride = gridDim.x * R;
+  auto emit = [&](const V (&v)[PH * PW], V d, unsigned row0) {
+    int arg[kLanes<V>] = {};
+    V raw;
+    const V best = window_best<PH * PW>(v, scale, shift, arg, &raw);
+#pragma unroll
+    for (int i = 0; i < PH; ++i)
+#pragma unroll
+      for (int j = 0; j < PW; ++j) {
+        V g = vsplat<V>(0.f);
+#pragma unroll
+        for (int e = 0; e < kLanes<V>; ++e)
+          if (best[e] > 0.f && arg[e] == i * PW + j) g[e] = scale[e] * d[e];
+        dx[(size_t)(row0 + (unsigned)i * (unsigned)s.W + (unsigned)j) * s.Q + q] = g;
+      }
+  };
+  for (unsigned r = blockIdx.x * R + rloc; r < n_rows; r += 2 * stride) {
+    const bool two = r + stride < n_rows;
+    const unsigned r2 = two ? r + stride : r;
+    const unsigned rowa = window_row<PH, PW>(s, r), rowb = window_row<PH, PW>(s, r2);
+    V va[PH * PW], vb[PH * PW];
+    window_load<PH, PW>(y, s, rowa, q, va);
+    window_load<PH, PW>(y, s, rowb, q, vb);
+    const V da = dz[(size_t)r * s.Q + q], db = dz[(size_t)r2 * s.Q + q];
+    emit(va, da, rowa);
+    if (two) emit(vb, db, rowb);
   }
-  const long long n_row = (long long)s.B * (s.H - hc) * wc * s.Q;
-  for (long long i = (long long)blockIdx.x * kBnThreads + threadIdx.x; i < n_row; i += stride4) {
-    const long long r = i / s.Q;
-    const int w = (int)(r % wc);
-    const long long t = r / wc;
-    const int h = hc + (int)(t % (s.H - hc));
-    const long long b = t / (s.H - hc);
-    const long long e = ((b * s.H + h) * s.W + w) * s.Q + q;
-    const f4 xh = (y[e] - mu) * is;
-    dx[e] = scale * (-c1 - xh * c2);
-  }
+  for_uncovered(s, q, [&](long long e) { dx[e] = vsplat<V>(0.f); });
 }
 
 // 0: generic kernels; 1: (1,1), 2: (1,2), 3: (2,2) windows with 32-bit indexing
@@ -533,15 +690,119 @@ inline int bn_blocks(long long n4) {
   return (int)(b > kBnMaxBlocks ? kBnMaxBlocks : b);
 }
 
+// Vectors per row of a supported channel count, 0 for every other: C = 2 (one float2), or a
+// multiple of 4 up to kBnMaxC (C / 4 float4).
+inline int bn_width(int C) {
+  if (C == 2) return 1;
+  if (C <= 0 || (C & 3) || C > kBnMaxC) return 0;
+  return C / 4;
+}
+
 inline bool bn_shape(BnShape* s, int B, int H, int W, int C, int ph, int pw) {
-  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || ph <= 0 || pw <= 0 || (C & 3)) return false;
-  const int Q = C / 4;
-  if (Q > kBnThreads || kBnThreads % Q) return false;
-  *s = BnShape{B, H, W, C, ph, pw, H / ph, W / pw, Q};
+  const int Q = bn_width(C);
+  if (B <= 0 || H <= 0 || W <= 0 || ph <= 0 || pw <= 0 || Q == 0) return false;
+  *s = BnShape{B, H, W, C, ph, pw, H / ph, W / pw, Q, (kBnThreads / Q) * Q};
   return s->Ho > 0 && s->Wo > 0;
 }
 
+inline bool bn_aligned(int C, std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & (C == 2 ? sizeof(f2) - 1 : sizeof(f4) - 1)) == 0;
+}
+
+template <typename V>
+void bnrp_fwd(const float* y, const float* gamma, const float* beta, float* running_mean,
+              float* running_var, float momentum, float eps, const float* mean_shift,
+              long long* batches_tracked, const float* skip, float* z, float* mean, float* invstd,
+              float* workspace, const BnShape& s, hipStream_t st) {
+  const int C = s.C;
+  const long long rows = (long long)s.B * s.H * s.W, n4 = rows * s.Q;
+  const int nblk = bn_blocks(n4);
+  const V* y4 = reinterpret_cast<const V*>(y);
+  const V* k4 = reinterpret_cast<const V*>(skip);
+  V* z4 = reinterpret_cast<V*>(z);
+  hipLaunchKernelGGL(bn_stats_kernel<V>, dim3(nblk), dim3(s.A), 0, st, y4, n4, s.Q, s.A, workspace, C);
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * 16), 0, st, workspace, nblk, C,
+                     (double)rows, eps, momentum, mean, invstd, running_mean, running_var, mean_shift,
+                     batches_tracked);
+  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
+  const dim3 ag(bn_blocks(n_out * 2)), ab(s.A);
+  switch (bn_fast_kind(s)) {
+    case 1: hipLaunchKernelGGL((bnrp_apply_win_kernel<1, 1, V>), ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s); break;
+    case 2: hipLaunchKernelGGL((bnrp_apply_win_kernel<1, 2, V>), ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s); break;
+    case 3: hipLaunchKernelGGL((bnrp_apply_win_kernel<2, 2, V>), ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s); break;
+    default: hipLaunchKernelGGL(bnrp_apply_kernel<V>, ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s);
+  }
+}
+
+template <typename V>
+void bnrp_bwd(const float* y, const float* dz, const float* gamma, const float* beta,
+              const float* mean, const float* invstd, float* dx, float* dgamma, float* dbeta,
+              float* dzero, float* workspace, const BnShape& s, hipStream_t st) {
+  const int C = s.C;
+  const long long rows = (long long)s.B * s.H * s.W;
+  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
+  const int nblk = bn_blocks(n_out * 2);
+  float* coef = workspace + (size_t)kBnMaxBlocks * 2 * C;
+  const dim3 rg(nblk), rb(s.A);
+  const V* y4 = reinterpret_cast<const V*>(y);
+  const V* dz4 = reinterpret_cast<const V*>(dz);
+  V* dx4 = reinterpret_cast<V*>(dx);
+  const int kind = bn_fast_kind(s);
+  switch (kind) {
+    case 1: hipLaunchKernelGGL((bnrp_bwd_reduce_win_kernel<1, 1, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s); break;
+    case 2: hipLaunchKernelGGL((bnrp_bwd_reduce_win_kernel<1, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s); break;
+    case 3: hipLaunchKernelGGL((bnrp_bwd_reduce_win_kernel<2, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s); break;
+    default: hipLaunchKernelGGL(bnrp_bwd_reduce_kernel<V>, rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s);
+  }
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * 16), 0, st, workspace, nblk,
+                     C, (double)rows, dgamma, dbeta, coef, dzero);
+  switch (kind) {
+    case 1: hipLaunchKernelGGL((bnrp_bwd_apply_win_kernel<1, 1, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s); break;
+    case 2: hipLaunchKernelGGL((bnrp_bwd_apply_win_kernel<1, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s); break;
+    case 3: hipLaunchKernelGGL((bnrp_bwd_apply_win_kernel<2, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s); break;
+    default: hipLaunchKernelGGL(bnrp_bwd_apply_kernel<V>, rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s);
+  }
+}
+
+template <typename V>
+void bnrp_eval_fwd(const float* y, const float* gamma, const float* beta, const float* rm,
+                   const float* rv, const float* bias, float eps, const float* skip, float* z,
+                   const BnShape& s, hipStream_t st) {
+  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
+  const dim3 ag(bn_blocks(n_out * 2)), ab(s.A);
+  const V* y4 = reinterpret_cast<const V*>(y);
+  const V* k4 = reinterpret_cast<const V*>(skip);
+  V* z4 = reinterpret_cast<V*>(z);
+  switch (bn_fast_kind(s)) {
+    case 1: hipLaunchKernelGGL((bnrp_eval_fwd_win_kernel<1, 1, V>), ag, ab, 0, st, y4, gamma, beta, rm, rv, bias, eps, k4, z4, s); break;
+    case 2: hipLaunchKernelGGL((bnrp_eval_fwd_win_kernel<1, 2, V>), ag, ab, 0, st, y4, gamma, beta, rm, rv, bias, eps, k4, z4, s); break;
+    case 3: hipLaunchKernelGGL((bnrp_eval_fwd_win_kernel<2, 2, V>), ag, ab, 0, st, y4, gamma, beta, rm, rv, bias, eps, k4, z4, s); break;
+    default: hipLaunchKernelGGL(bnrp_eval_fwd_kernel<V>, ag, ab, 0, st, y4, gamma, beta, rm, rv, bias, eps, k4, z4, s);
+  }
+}
+
+template <typename V>
+void bnrp_eval_bwd(const float* y, const float* dz, const float* gamma, const float* beta,
+                   const float* rm, const float* rv, const float* bias, float eps, float* dx,
+                   const BnShape& s, hipStream_t st) {
+  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
+  const dim3 rg(bn_blocks(n_out * 2)), rb(s.A);
+  const V* y4 = reinterpret_cast<const V*>(y);
+  const V* dz4 = reinterpret_cast<const V*>(dz);
+  V* dx4 = reinterpret_cast<V*>(dx);
+  switch (bn_fast_kind(s)) {
+    case 1: hipLaunchKernelGGL((bnrp_eval_bwd_win_kernel<1, 1, V>), rg, rb, 0, st, y4, dz4, gamma, beta, rm, rv, bias, eps, dx4, s); break;
+    case 2: hipLaunchKernelGGL((bnrp_eval_bwd_win_kernel<1, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, rm, rv, bias, eps, dx4, s); break;
+    case 3: hipLaunchKernelGGL((bnrp_eval_bwd_win_kernel<2, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, rm, rv, bias, eps, dx4, s); break;
+    default: hipLaunchKernelGGL(bnrp_eval_bwd_kernel<V>, rg, rb, 0, st, y4, dz4, gamma, beta, rm, rv, bias, eps, dx4, s);
+  }
+}
+
 }  // namespace pcgmix
+
+extern "C" int pcgmix_bnrp_supported(int C) { return pcgmix::bn_width(C) != 0; }
 
 extern "C" long long pcgmix_bnrp_workspace_floats(int B, int H, int W, int C) {
   if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return 0;
@@ -558,29 +819,14 @@ extern "C" int pcgmix_bnrp_fwd_f32(const float* y, const float* gamma, const flo
   BnShape s;
   if (!y || !gamma || !beta || !z || !mean || !invstd || !workspace || !bn_shape(&s, B, H, W, C, ph, pw))
     return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(skip) |
-       reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) |
-       reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(invstd)) & 15)
-    return hipErrorInvalidValue;
+  if (!bn_aligned(C, {y, z, skip, gamma, beta, mean, invstd})) return hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const long long rows = (long long)B * H * W, n4 = rows * s.Q;
-  const int nblk = bn_blocks(n4);
-  hipLaunchKernelGGL(bn_stats_kernel, dim3(nblk), dim3(kBnThreads), 0, st,
-                     reinterpret_cast<const f4*>(y), n4, s.Q, workspace, C);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * 16), 0, st, workspace, nblk, C,
-                     (double)rows, eps, momentum, mean, invstd, running_mean, running_var, mean_shift,
-                     batches_tracked);
-  const long long n_out = (long long)B * s.Ho * s.Wo * s.Q;
-  const dim3 ag(bn_blocks(n_out * 2)), ab(kBnThreads);
-  const f4* y4 = reinterpret_cast<const f4*>(y);
-  const f4* k4 = reinterpret_cast<const f4*>(skip);
-  f4* z4 = reinterpret_cast<f4*>(z);
-  switch (bn_fast_kind(s)) {
-    case 1: hipLaunchKernelGGL((bnrp_apply_win_kernel<1, 1>), ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s); break;
-    case 2: hipLaunchKernelGGL((bnrp_apply_win_kernel<1, 2>), ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s); break;
-    case 3: hipLaunchKernelGGL((bnrp_apply_win_kernel<2, 2>), ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s); break;
-    default: hipLaunchKernelGGL(bnrp_apply_kernel, ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s);
-  }
+  if (C == 2)
+    bnrp_fwd<f2>(y, gamma, beta, running_mean, running_var, momentum, eps, mean_shift, batches_tracked,
+                 skip, z, mean, invstd, workspace, s, st);
+  else
+    bnrp_fwd<f4>(y, gamma, beta, running_mean, running_var, momentum, eps, mean_shift, batches_tracked,
+                 skip, z, mean, invstd, workspace, s, st);
   return (int)hipGetLastError();
 }
 
@@ -594,34 +840,50 @@ extern "C" int pcgmix_bnrp_bwd_f32(const float* y, const float* dz, const float*
   if (!y || !dz || !gamma || !beta || !mean || !invstd || !dx || !dgamma || !dbeta || !workspace ||
       !bn_shape(&s, B, H, W, C, ph, pw))
     return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dz) |
-       reinterpret_cast<uintptr_t>(dx) | reinterpret_cast<uintptr_t>(workspace) |
-       reinterpret_cast<uintptr_t>(gamma) | reinterpret_cast<uintptr_t>(beta) |
-       reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(invstd)) & 15)
+  if (!bn_aligned(C, {y, dz, dx, workspace, gamma, beta, mean, invstd})) return hipErrorInvalidValue;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (C == 2)
+    bnrp_bwd<f2>(y, dz, gamma, beta, mean, invstd, dx, dgamma, dbeta, dzero, workspace, s, st);
+  else
+    bnrp_bwd<f4>(y, dz, gamma, beta, mean, invstd, dx, dgamma, dbeta, dzero, workspace, s, st);
+  return (int)hipGetLastError();
+}
+
+extern "C" int pcgmix_bnrp_eval_fwd_f32(const float* y, const float* gamma, const float* beta,
+                                        const float* running_mean, const float* running_var,
+                                        float eps, const float* conv_bias, const float* skip,
+                                        float* z, int B, int H, int W, int C, int ph, int pw,
+                                        pcgmix_stream_t stream) {
+  using namespace pcgmix;
+  BnShape s;
+  if (!y || !gamma || !beta || !running_mean || !running_var || !z || !bn_shape(&s, B, H, W, C, ph, pw))
+    return hipErrorInvalidValue;
+  if (!bn_aligned(C, {y, z, skip, gamma, beta, running_mean, running_var, conv_bias}))
     return hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const long long rows = (long long)B * H * W;
-  const long long n_out = (long long)B * s.Ho * s.Wo * s.Q;
-  const int nblk = bn_blocks(n_out * 2);
-  float* coef = workspace + (size_t)kBnMaxBlocks * 2 * C;
-  const dim3 rg(nblk), rb(kBnThreads);
-  const f4* y4 = reinterpret_cast<const f4*>(y);
-  const f4* dz4 = reinterpret_cast<const f4*>(dz);
-  f4* dx4 = reinterpret_cast<f4*>(dx);
-  const int kind = bn_fast_kind(s);
-  switch (kind) {
-    case 1: hipLaunchKernelGGL((bnrp_bwd_reduce_win_kernel<1, 1>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s); break;
-    case 2: hipLaunchKernelGGL((bnrp_bwd_reduce_win_kernel<1, 2>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s); break;
-    case 3: hipLaunchKernelGGL((bnrp_bwd_reduce_win_kernel<2, 2>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s); break;
-    default: hipLaunchKernelGGL(bnrp_bwd_reduce_kernel, rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s);
-  }
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * 16), 0, st, workspace, nblk,
-                     C, (double)rows, dgamma, dbeta, coef, dzero);
-  switch (kind) {
-    case 1: hipLaunchKernelGGL((bnrp_bwd_apply_win_kernel<1, 1>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s); break;
-    case 2: hipLaunchKernelGGL((bnrp_bwd_apply_win_kernel<1, 2>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s); break;
-    case 3: hipLaunchKernelGGL((bnrp_bwd_apply_win_kernel<2, 2>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s); break;
-    default: hipLaunchKernelGGL(bnrp_bwd_apply_kernel, rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s);
-  }
+  if (C == 2)
+    bnrp_eval_fwd<f2>(y, gamma, beta, running_mean, running_var, conv_bias, eps, skip, z, s, st);
+  else
+    bnrp_eval_fwd<f4>(y, gamma, beta, running_mean, running_var, conv_bias, eps, skip, z, s, st);
+  return (int)hipGetLastError();
+}
+
+extern "C" int pcgmix_bnrp_eval_bwd_f32(const float* y, const float* dz, const float* gamma,
+                                        const float* beta, const float* running_mean,
+                                        const float* running_var, float eps, const float* conv_bias,
+                                        float* dx, int B, int H, int W, int C, int ph, int pw,
+                                        pcgmix_stream_t stream) {
+  using namespace pcgmix;
+  BnShape s;
+  if (!y || !dz || !gamma || !beta || !running_mean || !running_var || !dx ||
+      !bn_shape(&s, B, H, W, C, ph, pw))
+    return hipErrorInvalidValue;
+  if (!bn_aligned(C, {y, dz, dx, gamma, beta, running_mean, running_var, conv_bias}))
+    return hipErrorInvalidValue;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (C == 2)
+    bnrp_eval_bwd<f2>(y, dz, gamma, beta, running_mean, running_var, conv_bias, eps, dx, s, st);
+  else
+    bnrp_eval_bwd<f4>(y, dz, gamma, beta, running_mean, running_var, conv_bias, eps, dx, s, st);
   return (int)hipGetLastError();
 }

@@ -705,10 +705,10 @@ class BNReLUPoolFunction(torch.autograd.Function):
 
     @staticmethod
     def supported(y: torch.Tensor) -> bool:
-        C = y.shape[1] if y.dim() == 4 else 0
-        return (y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and C % 4 == 0
-                and C // 4 <= 256 and 256 % (C // 4) == 0 and y.numel() > 0
-                and y.is_contiguous(memory_format=torch.channels_last))
+        # the channel rule is the kernels' own (C = 2 or a multiple of 4 up to 1024)
+        return (y.is_cuda and y.dtype == torch.float32 and y.dim() == 4 and y.numel() > 0
+                and y.is_contiguous(memory_format=torch.channels_last)
+                and bool(_lib.load().pcgmix_bnrp_supported(int(y.shape[1]))))
 
     @staticmethod
     def forward(ctx, y, gamma, beta, running_mean, running_var, momentum, eps, ph, pw, skip=None,
@@ -768,6 +768,56 @@ class BNReLUPoolFunction(torch.autograd.Function):
                 (dz if ctx.has_skip else None), dbias, None)
 
 
+class BNReLUPoolEvalFunction(torch.autograd.Function):
+    """Eval-mode BatchNorm (running statistics) + ReLU + MaxPool [+ skip] on a channels_last
+    activation as one kernel (``pcgmix_bnrp_eval_fwd_f32``), and its input gradient as one more
+    (``pcgmix_bnrp_eval_bwd_f32``: no reduction, the statistics are constants).  For frozen
+    parameters only: the backward returns a gradient for ``y`` (and ``dz`` itself for ``skip``),
+    none for gamma, beta or the bias.  ``conv_bias`` is the bias that was left out of ``y``.
+    Nothing here synchronises or allocates other than through ``torch.empty``, so the frozen
+    saliency pass can be captured into a graph."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, running_mean, running_var, eps, ph, pw, skip=None, conv_bias=None):
+        B, C, H, W = y.shape
+        if skip is not None and (skip.shape != (B, C, H // ph, W // pw) or skip.dtype != torch.float32
+                                 or not skip.is_contiguous(memory_format=torch.channels_last)):
+            raise ValueError("skip must be a float32 channels_last tensor shaped like the output")
+        lib = _lib.load()
+        z = torch.empty((B, C, H // ph, W // pw), dtype=torch.float32, device=y.device,
+                        memory_format=torch.channels_last)
+        vecs = [t.detach().contiguous() for t in (gamma, beta, running_mean, running_var)]
+        bias = conv_bias.detach().contiguous() if conv_bias is not None else None
+        stream = ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
+        _lib.check(lib.pcgmix_bnrp_eval_fwd_f32(
+            y.data_ptr(), *(t.data_ptr() for t in vecs), ctypes.c_float(eps),
+            bias.data_ptr() if bias is not None else None,
+            skip.data_ptr() if skip is not None else None, z.data_ptr(), B, H, W, C, ph, pw, stream),
+            "pcgmix_bnrp_eval_fwd_f32")
+        ctx.save_for_backward(y, *vecs, *(() if bias is None else (bias,)))
+        ctx.args = (float(eps), ph, pw, skip is not None)
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        y, *vecs = ctx.saved_tensors
+        bias = vecs.pop() if len(vecs) == 5 else None
+        eps, ph, pw, has_skip = ctx.args
+        B, C, H, W = y.shape
+        dz = dz.contiguous(memory_format=torch.channels_last)
+        dx = torch.empty_like(y)                             # preserves channels_last
+        stream = ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
+        _lib.check(_lib.load().pcgmix_bnrp_eval_bwd_f32(
+            y.data_ptr(), dz.data_ptr(), *(t.data_ptr() for t in vecs), ctypes.c_float(eps),
+            bias.data_ptr() if bias is not None else None, dx.data_ptr(), B, H, W, C, ph, pw, stream),
+            "pcgmix_bnrp_eval_bwd_f32")
+        return (dx, None, None, None, None, None, None, None, (dz if has_skip else None), None)
+
+
+def _pool_window(pool):
+    return (1, 1) if pool is None else ((pool, pool) if isinstance(pool, int) else tuple(pool))
+
+
 def conv_bn_relu_pool(h, weight4, conv_bias, padding, bn, training: bool, pool, skip=None):
     """Conv -> BatchNorm -> ReLU [-> MaxPool] on a 4-D (channels_last) activation with the
     convolution's bias folded into the BatchNorm instead of added by a separate pass.
@@ -796,7 +846,7 @@ def conv_bn_relu_pool(h, weight4, conv_bias, padding, bn, training: bool, pool, 
                 and conv_bias.is_contiguous() and conv_bias.dtype == torch.float32:
             # counter, running-mean shift (new = (1-m) * old + m * (mean(conv) + b)) and the bias'
             # exact zero gradient all happen inside the BatchNorm kernels: no launch of their own
-            ph, pw = (1, 1) if pool is None else ((pool, pool) if isinstance(pool, int) else pool)
+            ph, pw = _pool_window(pool)
             if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
                 skip = skip.contiguous(memory_format=torch.channels_last)
             return BNReLUPoolFunction.apply(h, bn.weight, bn.bias, bn.running_mean, bn.running_var,
@@ -812,11 +862,20 @@ def conv_bn_relu_pool(h, weight4, conv_bias, padding, bn, training: bool, pool, 
                 bn.running_mean.add_(conv_bias, alpha=bn.momentum / (1.0 - bn.momentum))
         if FUSED_BN and training and h.is_cuda:
             _warn_once(f"conv_bn_relu_pool: activation {tuple(h.shape)} {h.dtype} cannot use the HIP "
-                       "BatchNorm+ReLU+pool kernels (needs float32 channels_last, C % 4 == 0, "
-                       "256 % (C/4) == 0): running torch ops instead")
+                       "BatchNorm+ReLU+pool kernels (needs float32 channels_last, C == 2 or "
+                       "C % 4 == 0 with C <= 1024): running torch ops instead")
         h = F.batch_norm(h, bn.running_mean, bn.running_var, bn.weight, beta, True, bn.momentum,
                          bn.eps)
     else:
+        frozen = bn.weight is not None and (not torch.is_grad_enabled() or not (
+            bn.weight.requires_grad or bn.bias.requires_grad or conv_bias.requires_grad))
+        if FUSED_BN and frozen and BNReLUPoolFunction.supported(h) and conv_bias.dtype == torch.float32:
+            # running statistics, frozen parameters: one kernel forward, one for the input gradient
+            ph, pw = _pool_window(pool)
+            if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
+                skip = skip.contiguous(memory_format=torch.channels_last)
+            return BNReLUPoolEvalFunction.apply(h, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                                float(bn.eps), int(ph), int(pw), skip, conv_bias)
         h = F.batch_norm(h, bn.running_mean - conv_bias.detach(), bn.running_var, bn.weight,
                          bn.bias, False, 0.0, bn.eps)
     h = F.relu(h, inplace=True)

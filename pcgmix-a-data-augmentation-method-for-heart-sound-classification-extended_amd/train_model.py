@@ -302,8 +302,10 @@ def build_model(args) -> nn.Module:
     """The models of the hot path (train_model.py:296, 337-370: 'Potes', 'resnet9' and the two
     model-size ladders around them), head sized for ``args.sig_len`` (the reference hard-codes
     T = 2500).  'Potes', 'Potes(noDropout)', 'Potes0.1' and 'Potes0.02' run their conv branch on the
-    hand-written HIP stacks; the two 'PotesBig*' models and the ResNet9 widths the BatchNorm kernels
-    do not take run through torch/MIOpen, with the warnings those paths already give."""
+    hand-written HIP stacks; the two 'PotesBig*' models run through torch/MIOpen, with the warning
+    that path already gives.  Every ResNet9 width of the ladder (2 ... 1024) runs its BatchNorm +
+    ReLU + pool through the HIP kernels, in training and in eval mode: they take C = 2 and every
+    multiple of 4 up to 1024 (``pcgmix_bnrp_supported``), so no ResNet9 name warns."""
     sig_len = getattr(args, "sig_len", 2500)
     if args.dataset in SPECTROGRAM_DATASETS:
         if args.model != "resnet9":
