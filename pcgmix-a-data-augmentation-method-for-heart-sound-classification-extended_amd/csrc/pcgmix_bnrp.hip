@@ -10,12 +10,17 @@
 //
 //   forward   bn_stats_kernel        one read of y  -> per-block (sum, sum of squares) per channel
 //             bn_finalize_kernel     mean, 1/std, running-stat update (float64 combination)
-//             bnrp_apply_kernel      one read of y  -> z = maxpool(relu(gamma * xhat + beta))
+//             bnrp_fwd_kernel        one read of y  -> z = maxpool(relu(gamma * xhat + beta)) [+ skip]
 //   backward  bnrp_bwd_reduce_kernel one read of y, dz -> sums of dy and dy * xhat per channel
 //             bn_bwd_finalize_kernel dgamma, dbeta, the two means BatchNorm's dx needs
-//             bnrp_bwd_apply_kernel  one read of y, dz -> dx (one write)
-//   eval      bnrp_eval_fwd_kernel   one read of y  -> z, scale and shift from the running statistics
-//             bnrp_eval_bwd_kernel   one read of y, dz -> dx = scale * dz at the arg-max (one write)
+//             bnrp_dx_kernel         one read of y, dz -> dx (one write)
+//   eval      bnrp_fwd_kernel        the same kernel, scale and shift from the running statistics
+//             bnrp_dx_kernel         the same kernel, dx = scale * dz at the arg-max, 0 elsewhere
+//
+// bnrp_fwd_kernel and bnrp_dx_kernel are templates over <Window, Stats, V>: Stats (TrainStats or
+// EvalStats) says where scale and shift come from and which rule gives dx; Window (FixedWindow<PH,
+// PW> or AnyWindow) picks the loop: loads-before-first-use with 32-bit indices for the window
+// shapes ResNet9 uses, a runtime window with 64-bit indices for everything else (with_window).
 //
 // The ReLU mask and the pooling arg-max are recomputed from y (first maximum wins, as in torch's
 // max_pool), so nothing but y, mean and 1/std is kept for backward.  Five passes instead of ten.
@@ -229,6 +234,39 @@ __device__ __forceinline__ BnAffine<V> eval_affine(const float* __restrict__ gam
   return a;
 }
 
+// The per-channel arrays of a launch, passed to the kernels by value.  kBatch: the statistics are
+// the batch's own, so the input gradient carries BatchNorm's two mean terms.
+struct TrainStats {
+  static constexpr bool kBatch = true;
+  const float *__restrict__ gamma, *__restrict__ beta, *__restrict__ mean, *__restrict__ invstd;
+  template <typename V>
+  __device__ __forceinline__ BnAffine<V> affine(int q) const {
+    return train_affine<V>(gamma, beta, mean, invstd, q);
+  }
+};
+
+struct EvalStats {
+  static constexpr bool kBatch = false;
+  const float *__restrict__ gamma, *__restrict__ beta, *__restrict__ running_mean,
+      *__restrict__ running_var, *__restrict__ bias;
+  float eps;
+  template <typename V>
+  __device__ __forceinline__ BnAffine<V> affine(int q) const {
+    return eval_affine<V>(gamma, beta, running_mean, running_var, bias, eps, q);
+  }
+};
+
+// The pooling window as a kernel template argument: known at compile time (with 32-bit indexing),
+// or read from the BnShape (with 64-bit indexing).  with_window() maps a shape to its tag.
+template <int PH_, int PW_>
+struct FixedWindow {
+  static constexpr bool kFixed = true;
+  static constexpr int PH = PH_, PW = PW_;
+};
+struct AnyWindow {
+  static constexpr bool kFixed = false;
+};
+
 // row of pooled outputs -> (b, ho, wo)
 struct PoolPos {
   long long b;
@@ -289,179 +327,16 @@ __device__ __forceinline__ void apply_rows(const V* __restrict__ y, const V* __r
   }
 }
 
-template <typename V>
-__global__ __launch_bounds__(kBnThreads) void bnrp_apply_kernel(
-    const V* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ mean, const float* __restrict__ invstd, const V* __restrict__ skip,
-    V* __restrict__ z, BnShape s) {
-  const int q = threadIdx.x % s.Q;                    // fixed per thread: strides are multiples of Q
-  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
-  apply_rows(y, skip, z, s, q, a.scale, a.shift);
-}
-
-template <typename V>
-__global__ __launch_bounds__(kBnThreads) void bnrp_eval_fwd_kernel(
-    const V* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ running_mean, const float* __restrict__ running_var,
-    const float* __restrict__ bias, float eps, const V* __restrict__ skip, V* __restrict__ z,
-    BnShape s) {
-  const int q = threadIdx.x % s.Q;
-  const BnAffine<V> a = eval_affine<V>(gamma, beta, running_mean, running_var, bias, eps, q);
-  apply_rows(y, skip, z, s, q, a.scale, a.shift);
-}
-
-// ------------------------------------------------------------------------------------ backward
-template <typename V>
-__global__ __launch_bounds__(kBnThreads) void bnrp_bwd_reduce_kernel(
-    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ mean,
-    const float* __restrict__ invstd, float* __restrict__ partial, BnShape s) {
-  __shared__ V lds[2 * kBnThreads];
-  const int q = threadIdx.x % s.Q;
-  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
-  V s1 = vsplat<V>(0.f), s2 = vsplat<V>(0.f);
-  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
-  const long long stride = (long long)gridDim.x * s.A;
-  for (long long o = (long long)blockIdx.x * s.A + threadIdx.x; o < n_out; o += stride) {
-    const PoolPos p = pool_pos(s, o / s.Q);
-    int arg[kLanes<V>];
-    V vraw;
-    const V best = window_max(y, s, p.b, p.ho, p.wo, q, a.scale, a.shift, arg, &vraw);
-    const V d = dz[o];
-#pragma unroll
-    for (int e = 0; e < kLanes<V>; ++e) {
-      if (best[e] > 0.f) {                            // ReLU passes the gradient at the arg-max
-        const float xh = (vraw[e] - a.mu[e]) * a.is[e];   // xhat at the arg-max
-        s1[e] += d[e];
-        s2[e] = fmaf(d[e], xh, s2[e]);
-      }
-    }
-  }
-  float* p = partial + (size_t)blockIdx.x * 2 * s.C;
-  quad_reduce_store(s1, s2, s.Q, s.A, lds, p, p + s.C);
-}
-
-__global__ __launch_bounds__(kFinCh * 16) void bn_bwd_finalize_kernel(
-    const float* __restrict__ partial, int nblk, int C, double n_rows, float* __restrict__ dgamma,
-    float* __restrict__ dbeta, float* __restrict__ coef, float* __restrict__ dzero) {
-  __shared__ double lds[2][kFinCh][16];
-  const int c = blockIdx.x * kFinCh + threadIdx.x % kFinCh, lane = threadIdx.x / kFinCh;
-  double s1, s2;
-  partial_sums(partial, nblk, C, c, lane, lds, &s1, &s2);
-  if (c >= C || lane != 0) return;
-  dbeta[c] = (float)s1;
-  dgamma[c] = (float)s2;
-  if (dzero) dzero[c] = 0.f;               // the exact zero gradient of a constant the norm cancels
-  coef[c] = (float)(s1 / n_rows);          // mean of dy
-  coef[C + c] = (float)(s2 / n_rows);      // mean of dy * xhat
-}
-
-// Calls f(e) once for the vector index e of every position that no window covers (odd lengths):
-// columns w >= Wo*pw of every row, then rows h >= Ho*ph of the covered columns.
-template <typename F>
-__device__ __forceinline__ void for_uncovered(const BnShape& s, int q, F f) {
-  const long long stride = (long long)gridDim.x * s.A;
-  const int wc = s.Wo * s.pw, hc = s.Ho * s.ph;
-  const long long n_col = (long long)s.B * s.H * (s.W - wc) * s.Q;
-  for (long long i = (long long)blockIdx.x * s.A + threadIdx.x; i < n_col; i += stride) {
-    const long long r = i / s.Q;
-    const int w = wc + (int)(r % (s.W - wc));
-    const long long bh = r / (s.W - wc);                           // b * H + h
-    f((bh * s.W + w) * s.Q + q);
-  }
-  const long long n_row = (long long)s.B * (s.H - hc) * wc * s.Q;
-  for (long long i = (long long)blockIdx.x * s.A + threadIdx.x; i < n_row; i += stride) {
-    const long long r = i / s.Q;
-    const int w = (int)(r % wc);
-    const long long t = r / wc;
-    const int h = hc + (int)(t % (s.H - hc));
-    const long long b = t / (s.H - hc);
-    f(((b * s.H + h) * s.W + w) * s.Q + q);
-  }
-}
-
-// dx = gamma * invstd * (dy - mean(dy) - xhat * mean(dy * xhat)), dy = dz at the window's arg-max
-// where the activation is positive, 0 elsewhere.  One thread per (window, channel group): every y
-// of the window is read once and every dx written once.  Positions that no window covers have
-// dy = 0 and are written by the tail loops.
-template <typename V>
-__global__ __launch_bounds__(kBnThreads) void bnrp_bwd_apply_kernel(
-    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ mean,
-    const float* __restrict__ invstd, const float* __restrict__ coef, V* __restrict__ dx,
-    BnShape s) {
-  const int q = threadIdx.x % s.Q;
-  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
-  const V mu = a.mu, is = a.is, scale = a.scale, shift = a.shift;
-  const V c1 = vchan<V>(coef, q), c2 = vchan<V>(coef + s.C, q);
-  const long long stride = (long long)gridDim.x * s.A;
-  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
-  for (long long o = (long long)blockIdx.x * s.A + threadIdx.x; o < n_out; o += stride) {
-    const PoolPos p = pool_pos(s, o / s.Q);
-    // pass 1 over the window: arg-max of relu(a) (first maximum)
-    int arg[kLanes<V>] = {};
-    const V best = window_max(y, s, p.b, p.ho, p.wo, q, scale, shift, arg);
-    const V d = dz[o];
-    // pass 2 (the window is in cache): dx for every position
-    for (int i = 0; i < s.ph; ++i)
-      for (int j = 0; j < s.pw; ++j) {
-        const long long row = (p.b * s.H + (p.ho * s.ph + i)) * s.W + (p.wo * s.pw + j);
-        const V v = y[row * s.Q + q];
-        V dy = vsplat<V>(0.f);
-#pragma unroll
-        for (int e = 0; e < kLanes<V>; ++e)
-          if (best[e] > 0.f && arg[e] == i * s.pw + j) dy[e] = d[e];
-        const V xh = (v - mu) * is;
-        dx[row * s.Q + q] = scale * (dy - c1 - xh * c2);
-      }
-  }
-  for_uncovered(s, q, [&](long long e) {
-    const V xh = (y[e] - mu) * is;
-    dx[e] = scale * (-c1 - xh * c2);
-  });
-}
-
-// Eval-mode input gradient: the statistics are constants, so dx = scale * dz at the window's first
-// maximum where the activation is positive and an exact 0 everywhere else (uncovered positions
-// included).  No reduction: one read of y and dz, one write of dx.
-template <typename V>
-__global__ __launch_bounds__(kBnThreads) void bnrp_eval_bwd_kernel(
-    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ running_mean,
-    const float* __restrict__ running_var, const float* __restrict__ bias, float eps,
-    V* __restrict__ dx, BnShape s) {
-  const int q = threadIdx.x % s.Q;
-  const BnAffine<V> a = eval_affine<V>(gamma, beta, running_mean, running_var, bias, eps, q);
-  const long long stride = (long long)gridDim.x * s.A;
-  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
-  for (long long o = (long long)blockIdx.x * s.A + threadIdx.x; o < n_out; o += stride) {
-    const PoolPos p = pool_pos(s, o / s.Q);
-    int arg[kLanes<V>] = {};
-    const V best = window_max(y, s, p.b, p.ho, p.wo, q, a.scale, a.shift, arg);
-    const V d = dz[o];
-    for (int i = 0; i < s.ph; ++i)
-      for (int j = 0; j < s.pw; ++j) {
-        const long long row = (p.b * s.H + (p.ho * s.ph + i)) * s.W + (p.wo * s.pw + j);
-        V g = vsplat<V>(0.f);
-#pragma unroll
-        for (int e = 0; e < kLanes<V>; ++e)
-          if (best[e] > 0.f && arg[e] == i * s.pw + j) g[e] = a.scale[e] * d[e];
-        dx[row * s.Q + q] = g;
-      }
-  }
-  for_uncovered(s, q, [&](long long e) { dx[e] = vsplat<V>(0.f); });
-}
-
-// ------------------------------------------------------------------------------------ fast paths
-// The streaming kernels above, specialised for the window shapes ResNet9 uses ((1,1), (1,2),
-// (2,2)) and index ranges that fit 32 bits.  The generic versions walk the window in a loop with
-// runtime bounds: one global load, one s_waitcnt vmcnt(0), the next load — and the backward
-// reduction then waits once more for dz.  A forward pass hides that behind its store (fire and
-// forget), a pure reader does not: bnrp_bwd_reduce_kernel ran at 2.4-2.8 TB/s where the forward
-// apply reaches 6.0 (profiles/r2_resnet1d_step_kernels.csv).  Here every thread handles TWO pooled
-// rows per iteration and issues all of their loads (2 x PH x PW of y, 2 of dz) before the first
-// use; row -> (b, ho, wo) is 32-bit arithmetic (the generic 64-bit divisions are ~100 instructions
-// each).  A block covers R = A / Q pooled rows per step.
+// ------------------------------------------------------------------------------------ fixed windows
+// The window shapes ResNet9 uses ((1,1), (1,2), (2,2)) with index ranges that fit 32 bits.  The
+// generic loops walk the window with runtime bounds: one global load, one s_waitcnt vmcnt(0), the
+// next load — and the backward reduction then waits once more for dz.  A forward pass hides that
+// behind its store (fire and forget), a pure reader does not: the generic backward reduction ran
+// at 2.4-2.8 TB/s where the forward reaches 6.0 (profiles/r2_resnet1d_step_kernels.csv).  With a
+// FixedWindow every thread handles TWO pooled rows per iteration and issues all of their loads
+// (2 x PH x PW of y, 2 of dz) before the first use; row -> (b, ho, wo) is 32-bit arithmetic (the
+// generic 64-bit divisions are ~100 instructions each).  A block covers R = A / Q pooled rows per
+// step.
 template <int PH, int PW>
 __device__ __forceinline__ unsigned window_row(const BnShape& s, unsigned r) {
   const unsigned wo = r % (unsigned)s.Wo, t = r / (unsigned)s.Wo;
@@ -526,162 +401,239 @@ __device__ __forceinline__ void apply_win_rows(const V* __restrict__ y, const V*
   }
 }
 
-template <int PH, int PW, typename V>
-__global__ __launch_bounds__(kBnThreads) void bnrp_apply_win_kernel(
-    const V* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ mean, const float* __restrict__ invstd, const V* __restrict__ skip,
-    V* __restrict__ z, BnShape s) {
-  const int q = threadIdx.x % s.Q;
-  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
-  apply_win_rows<PH, PW>(y, skip, z, s, q, a.scale, a.shift);
+template <typename Win, typename Stats, typename V>
+__global__ __launch_bounds__(kBnThreads) void bnrp_fwd_kernel(const V* __restrict__ y, Stats st,
+                                                              const V* __restrict__ skip,
+                                                              V* __restrict__ z, BnShape s) {
+  const int q = threadIdx.x % s.Q;                    // fixed per thread: strides are multiples of Q
+  const BnAffine<V> a = st.template affine<V>(q);
+  if constexpr (Win::kFixed)
+    apply_win_rows<Win::PH, Win::PW>(y, skip, z, s, q, a.scale, a.shift);
+  else
+    apply_rows(y, skip, z, s, q, a.scale, a.shift);
 }
 
-template <int PH, int PW, typename V>
-__global__ __launch_bounds__(kBnThreads) void bnrp_eval_fwd_win_kernel(
-    const V* __restrict__ y, const float* __restrict__ gamma, const float* __restrict__ beta,
-    const float* __restrict__ running_mean, const float* __restrict__ running_var,
-    const float* __restrict__ bias, float eps, const V* __restrict__ skip, V* __restrict__ z,
+// ------------------------------------------------------------------------------------ backward
+template <typename Win, typename V>
+__global__ __launch_bounds__(kBnThreads) void bnrp_bwd_reduce_kernel(
+    const V* __restrict__ y, const V* __restrict__ dz, TrainStats st, float* __restrict__ partial,
     BnShape s) {
-  const int q = threadIdx.x % s.Q;
-  const BnAffine<V> a = eval_affine<V>(gamma, beta, running_mean, running_var, bias, eps, q);
-  apply_win_rows<PH, PW>(y, skip, z, s, q, a.scale, a.shift);
-}
-
-template <int PH, int PW, typename V>
-__global__ __launch_bounds__(kBnThreads) void bnrp_bwd_reduce_win_kernel(
-    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ mean,
-    const float* __restrict__ invstd, float* __restrict__ partial, BnShape s) {
   __shared__ V lds[2 * kBnThreads];
   const int q = threadIdx.x % s.Q;
-  const unsigned R = s.A / s.Q, rloc = threadIdx.x / s.Q;
-  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
+  const BnAffine<V> a = st.affine<V>(q);
   const V mu = a.mu, is = a.is, scale = a.scale, shift = a.shift;
   V s1 = vsplat<V>(0.f), s2 = vsplat<V>(0.f);
-  const unsigned n_rows = (unsigned)s.B * s.Ho * s.Wo, stride = gridDim.x * R;
-  for (unsigned r = blockIdx.x * R + rloc; r < n_rows; r += 2 * stride) {
-    const bool two = r + stride < n_rows;
-    const unsigned r2 = two ? r + stride : r;
-    V va[PH * PW], vb[PH * PW];
-    window_load<PH, PW>(y, s, window_row<PH, PW>(s, r), q, va);
-    window_load<PH, PW>(y, s, window_row<PH, PW>(s, r2), q, vb);
-    const V da = dz[(size_t)r * s.Q + q];
-    V db = dz[(size_t)r2 * s.Q + q];
-    if (!two) db = vsplat<V>(0.f);
-    int arg[kLanes<V>];
-    V raw;
-    V best = window_best<PH * PW>(va, scale, shift, arg, &raw);
+  if constexpr (Win::kFixed) {
+    constexpr int PH = Win::PH, PW = Win::PW;
+    const unsigned R = s.A / s.Q, rloc = threadIdx.x / s.Q;
+    const unsigned n_rows = (unsigned)s.B * s.Ho * s.Wo, stride = gridDim.x * R;
+    for (unsigned r = blockIdx.x * R + rloc; r < n_rows; r += 2 * stride) {
+      const bool two = r + stride < n_rows;
+      const unsigned r2 = two ? r + stride : r;
+      V va[PH * PW], vb[PH * PW];
+      window_load<PH, PW>(y, s, window_row<PH, PW>(s, r), q, va);
+      window_load<PH, PW>(y, s, window_row<PH, PW>(s, r2), q, vb);
+      const V da = dz[(size_t)r * s.Q + q];
+      V db = dz[(size_t)r2 * s.Q + q];
+      if (!two) db = vsplat<V>(0.f);
+      int arg[kLanes<V>];
+      V raw;
+      V best = window_best<PH * PW>(va, scale, shift, arg, &raw);
 #pragma unroll
-    for (int e = 0; e < kLanes<V>; ++e) {
-      const float d = best[e] > 0.f ? da[e] : 0.f;    // ReLU passes the gradient at the arg-max
-      s1[e] += d;
-      s2[e] = fmaf(d, (raw[e] - mu[e]) * is[e], s2[e]);
+      for (int e = 0; e < kLanes<V>; ++e) {
+        const float d = best[e] > 0.f ? da[e] : 0.f;  // ReLU passes the gradient at the arg-max
+        s1[e] += d;
+        s2[e] = fmaf(d, (raw[e] - mu[e]) * is[e], s2[e]);
+      }
+      best = window_best<PH * PW>(vb, scale, shift, arg, &raw);
+#pragma unroll
+      for (int e = 0; e < kLanes<V>; ++e) {
+        const float d = best[e] > 0.f ? db[e] : 0.f;
+        s1[e] += d;
+        s2[e] = fmaf(d, (raw[e] - mu[e]) * is[e], s2[e]);
+      }
     }
-    best = window_best<PH * PW>(vb, scale, shift, arg, &raw);
+  } else {
+    const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
+    const long long stride = (long long)gridDim.x * s.A;
+    for (long long o = (long long)blockIdx.x * s.A + threadIdx.x; o < n_out; o += stride) {
+      const PoolPos p = pool_pos(s, o / s.Q);
+      int arg[kLanes<V>];
+      V vraw;
+      const V best = window_max(y, s, p.b, p.ho, p.wo, q, scale, shift, arg, &vraw);
+      const V d = dz[o];
 #pragma unroll
-    for (int e = 0; e < kLanes<V>; ++e) {
-      const float d = best[e] > 0.f ? db[e] : 0.f;
-      s1[e] += d;
-      s2[e] = fmaf(d, (raw[e] - mu[e]) * is[e], s2[e]);
+      for (int e = 0; e < kLanes<V>; ++e) {
+        if (best[e] > 0.f) {                          // ReLU passes the gradient at the arg-max
+          const float xh = (vraw[e] - mu[e]) * is[e];     // xhat at the arg-max
+          s1[e] += d[e];
+          s2[e] = fmaf(d[e], xh, s2[e]);
+        }
+      }
     }
   }
   float* p = partial + (size_t)blockIdx.x * 2 * s.C;
   quad_reduce_store(s1, s2, s.Q, s.A, lds, p, p + s.C);
 }
 
-template <int PH, int PW, typename V>
-__global__ __launch_bounds__(kBnThreads) void bnrp_bwd_apply_win_kernel(
-    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ mean,
-    const float* __restrict__ invstd, const float* __restrict__ coef, V* __restrict__ dx,
-    BnShape s) {
-  const int q = threadIdx.x % s.Q;
-  const unsigned R = s.A / s.Q, rloc = threadIdx.x / s.Q;
-  const BnAffine<V> a = train_affine<V>(gamma, beta, mean, invstd, q);
-  const V mu = a.mu, is = a.is, scale = a.scale, shift = a.shift;
-  const V c1 = vchan<V>(coef, q), c2 = vchan<V>(coef + s.C, q);
-  const unsigned n_rows = (unsigned)s.B * s.Ho * s.Wo, stride = gridDim.x * R;
-  auto emit = [&](const V (&v)[PH * PW], V d, unsigned row0) {
-    int arg[kLanes<V>] = {};
-    V raw;
-    const V best = window_best<PH * PW>(v, scale, shift, arg, &raw);
-#pragma unroll
-    for (int i = 0; i < PH; ++i)
-#pragma unroll
-      for (int j = 0; j < PW; ++j) {
-        V dy = vsplat<V>(0.f);
-#pragma unroll
-        for (int e = 0; e < kLanes<V>; ++e)
-          if (best[e] > 0.f && arg[e] == i * PW + j) dy[e] = d[e];
-        const V xh = (v[i * PW + j] - mu) * is;
-        dx[(size_t)(row0 + (unsigned)i * (unsigned)s.W + (unsigned)j) * s.Q + q] = scale * (dy - c1 - xh * c2);
-      }
-  };
-  for (unsigned r = blockIdx.x * R + rloc; r < n_rows; r += 2 * stride) {
-    const bool two = r + stride < n_rows;
-    const unsigned r2 = two ? r + stride : r;
-    const unsigned rowa = window_row<PH, PW>(s, r), rowb = window_row<PH, PW>(s, r2);
-    V va[PH * PW], vb[PH * PW];
-    window_load<PH, PW>(y, s, rowa, q, va);
-    window_load<PH, PW>(y, s, rowb, q, vb);
-    const V da = dz[(size_t)r * s.Q + q], db = dz[(size_t)r2 * s.Q + q];
-    emit(va, da, rowa);
-    if (two) emit(vb, db, rowb);
-  }
-  // uncovered positions (odd lengths), as in the generic kernel
-  for_uncovered(s, q, [&](long long e) {
-    const V xh = (y[e] - mu) * is;
-    dx[e] = scale * (-c1 - xh * c2);
-  });
+__global__ __launch_bounds__(kFinCh * 16) void bn_bwd_finalize_kernel(
+    const float* __restrict__ partial, int nblk, int C, double n_rows, float* __restrict__ dgamma,
+    float* __restrict__ dbeta, float* __restrict__ coef, float* __restrict__ dzero) {
+  __shared__ double lds[2][kFinCh][16];
+  const int c = blockIdx.x * kFinCh + threadIdx.x % kFinCh, lane = threadIdx.x / kFinCh;
+  double s1, s2;
+  partial_sums(partial, nblk, C, c, lane, lds, &s1, &s2);
+  if (c >= C || lane != 0) return;
+  dbeta[c] = (float)s1;
+  dgamma[c] = (float)s2;
+  if (dzero) dzero[c] = 0.f;               // the exact zero gradient of a constant the norm cancels
+  coef[c] = (float)(s1 / n_rows);          // mean of dy
+  coef[C + c] = (float)(s2 / n_rows);      // mean of dy * xhat
 }
 
-template <int PH, int PW, typename V>
-__global__ __launch_bounds__(kBnThreads) void bnrp_eval_bwd_win_kernel(
-    const V* __restrict__ y, const V* __restrict__ dz, const float* __restrict__ gamma,
-    const float* __restrict__ beta, const float* __restrict__ running_mean,
-    const float* __restrict__ running_var, const float* __restrict__ bias, float eps,
-    V* __restrict__ dx, BnShape s) {
+// Calls f(e) once for the vector index e of every position that no window covers (odd lengths):
+// columns w >= Wo*pw of every row, then rows h >= Ho*ph of the covered columns.
+template <typename F>
+__device__ __forceinline__ void for_uncovered(const BnShape& s, int q, F f) {
+  const long long stride = (long long)gridDim.x * s.A;
+  const int wc = s.Wo * s.pw, hc = s.Ho * s.ph;
+  const long long n_col = (long long)s.B * s.H * (s.W - wc) * s.Q;
+  for (long long i = (long long)blockIdx.x * s.A + threadIdx.x; i < n_col; i += stride) {
+    const long long r = i / s.Q;
+    const int w = wc + (int)(r % (s.W - wc));
+    const long long bh = r / (s.W - wc);                           // b * H + h
+    f((bh * s.W + w) * s.Q + q);
+  }
+  const long long n_row = (long long)s.B * (s.H - hc) * wc * s.Q;
+  for (long long i = (long long)blockIdx.x * s.A + threadIdx.x; i < n_row; i += stride) {
+    const long long r = i / s.Q;
+    const int w = (int)(r % wc);
+    const long long t = r / wc;
+    const int h = hc + (int)(t % (s.H - hc));
+    const long long b = t / (s.H - hc);
+    f(((b * s.H + h) * s.W + w) * s.Q + q);
+  }
+}
+
+// The input gradient of one position, given dy = dz at the window's first maximum where the
+// activation is positive and 0 everywhere else (positions that no window covers included).
+//   kBatch (training): dx = gamma * invstd * (dy - mean(dy) - xhat * mean(dy * xhat)); c1 and c2
+//     are the two means (bn_bwd_finalize_kernel).
+//   running statistics (eval): they are constants, so dx = scale * dy, written as a select so that
+//     every other position gets an exact +0 whatever the sign of gamma.
+// dx_at: position idx of a window whose maximum `best` sits at arg; v = y there, d = the window's dz.
+template <bool kBatch, typename V>
+__device__ __forceinline__ V dx_at(const BnAffine<V>& a, V c1, V c2, V v, V best,
+                                   const int (&arg)[kLanes<V>], int idx, V d) {
+  V dy = vsplat<V>(0.f);
+#pragma unroll
+  for (int e = 0; e < kLanes<V>; ++e)
+    if (best[e] > 0.f && arg[e] == idx) dy[e] = kBatch ? d[e] : a.scale[e] * d[e];
+  if constexpr (kBatch) {
+    const V xh = (v - a.mu) * a.is;
+    return a.scale * (dy - c1 - xh * c2);
+  } else {
+    return dy;
+  }
+}
+
+// a position that no window covers; v = y there
+template <bool kBatch, typename V>
+__device__ __forceinline__ V dx_uncovered(const BnAffine<V>& a, V c1, V c2, V v) {
+  if constexpr (kBatch) {
+    const V xh = (v - a.mu) * a.is;
+    return a.scale * (-c1 - xh * c2);
+  } else {
+    return vsplat<V>(0.f);
+  }
+}
+
+// One thread per (window, channel group): every y of the window is read once and every dx written
+// once; the tail loops write the positions that no window covers.  No reduction here: in eval
+// mode this kernel is the whole backward.
+template <typename Win, typename Stats, typename V>
+__global__ __launch_bounds__(kBnThreads) void bnrp_dx_kernel(const V* __restrict__ y,
+                                                             const V* __restrict__ dz, Stats st,
+                                                             const float* __restrict__ coef,
+                                                             V* __restrict__ dx, BnShape s) {
   const int q = threadIdx.x % s.Q;
-  const unsigned R = s.A / s.Q, rloc = threadIdx.x / s.Q;
-  const BnAffine<V> a = eval_affine<V>(gamma, beta, running_mean, running_var, bias, eps, q);
+  constexpr bool kBatch = Stats::kBatch;
+  const BnAffine<V> a = st.template affine<V>(q);
   const V scale = a.scale, shift = a.shift;
-  const unsigned n_rows = (unsigned)s.B * s.Ho * s.Wo, stride = gridDim.x * R;
-  auto emit = [&](const V (&v)[PH * PW], V d, unsigned row0) {
-    int arg[kLanes<V>] = {};
-    V raw;
-    const V best = window_best<PH * PW>(v, scale, shift, arg, &raw);
-#pragma unroll
-    for (int i = 0; i < PH; ++i)
-#pragma unroll
-      for (int j = 0; j < PW; ++j) {
-        V g = vsplat<V>(0.f);
-#pragma unroll
-        for (int e = 0; e < kLanes<V>; ++e)
-          if (best[e] > 0.f && arg[e] == i * PW + j) g[e] = scale[e] * d[e];
-        dx[(size_t)(row0 + (unsigned)i * (unsigned)s.W + (unsigned)j) * s.Q + q] = g;
-      }
-  };
-  for (unsigned r = blockIdx.x * R + rloc; r < n_rows; r += 2 * stride) {
-    const bool two = r + stride < n_rows;
-    const unsigned r2 = two ? r + stride : r;
-    const unsigned rowa = window_row<PH, PW>(s, r), rowb = window_row<PH, PW>(s, r2);
-    V va[PH * PW], vb[PH * PW];
-    window_load<PH, PW>(y, s, rowa, q, va);
-    window_load<PH, PW>(y, s, rowb, q, vb);
-    const V da = dz[(size_t)r * s.Q + q], db = dz[(size_t)r2 * s.Q + q];
-    emit(va, da, rowa);
-    if (two) emit(vb, db, rowb);
+  V c1 = vsplat<V>(0.f), c2 = c1;
+  if constexpr (kBatch) {
+    c1 = vchan<V>(coef, q);
+    c2 = vchan<V>(coef + s.C, q);
   }
-  for_uncovered(s, q, [&](long long e) { dx[e] = vsplat<V>(0.f); });
+  if constexpr (Win::kFixed) {
+    constexpr int PH = Win::PH, PW = Win::PW;
+    const unsigned R = s.A / s.Q, rloc = threadIdx.x / s.Q;
+    const unsigned n_rows = (unsigned)s.B * s.Ho * s.Wo, stride = gridDim.x * R;
+    auto emit = [&](const V (&v)[PH * PW], V d, unsigned row0) {
+      int arg[kLanes<V>] = {};
+      V raw;
+      const V best = window_best<PH * PW>(v, scale, shift, arg, &raw);
+#pragma unroll
+      for (int i = 0; i < PH; ++i)
+#pragma unroll
+        for (int j = 0; j < PW; ++j)
+          dx[(size_t)(row0 + (unsigned)i * (unsigned)s.W + (unsigned)j) * s.Q + q] =
+              dx_at<kBatch>(a, c1, c2, v[i * PW + j], best, arg, i * PW + j, d);
+    };
+    for (unsigned r = blockIdx.x * R + rloc; r < n_rows; r += 2 * stride) {
+      const bool two = r + stride < n_rows;
+      const unsigned r2 = two ? r + stride : r;
+      const unsigned rowa = window_row<PH, PW>(s, r), rowb = window_row<PH, PW>(s, r2);
+      V va[PH * PW], vb[PH * PW];
+      window_load<PH, PW>(y, s, rowa, q, va);
+      window_load<PH, PW>(y, s, rowb, q, vb);
+      const V da = dz[(size_t)r * s.Q + q], db = dz[(size_t)r2 * s.Q + q];
+      emit(va, da, rowa);
+      if (two) emit(vb, db, rowb);
+    }
+  } else {
+    const long long stride = (long long)gridDim.x * s.A;
+    const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
+    for (long long o = (long long)blockIdx.x * s.A + threadIdx.x; o < n_out; o += stride) {
+      const PoolPos p = pool_pos(s, o / s.Q);
+      // pass 1 over the window: arg-max of relu(a) (first maximum)
+      int arg[kLanes<V>] = {};
+      const V best = window_max(y, s, p.b, p.ho, p.wo, q, scale, shift, arg);
+      const V d = dz[o];
+      // pass 2 (the window is in cache): dx for every position
+      for (int i = 0; i < s.ph; ++i)
+        for (int j = 0; j < s.pw; ++j) {
+          const long long row = (p.b * s.H + (p.ho * s.ph + i)) * s.W + (p.wo * s.pw + j);
+          dx[row * s.Q + q] = dx_at<kBatch>(a, c1, c2, y[row * s.Q + q], best, arg, i * s.pw + j, d);
+        }
+    }
+  }
+  for_uncovered(s, q, [&](long long e) { dx[e] = dx_uncovered<kBatch>(a, c1, c2, y[e]); });
 }
 
-// 0: generic kernels; 1: (1,1), 2: (1,2), 3: (2,2) windows with 32-bit indexing
-inline int bn_fast_kind(const BnShape& s) {
-  if ((long long)s.B * s.H * s.W * s.Q >= (1ll << 31)) return 0;
-  if (s.ph == 1 && s.pw == 1) return 1;
-  if (s.ph == 1 && s.pw == 2) return 2;
-  if (s.ph == 2 && s.pw == 2) return 3;
-  return 0;
+// ------------------------------------------------------------------------------------ host
+// Calls f with the window tag of the shape: the windows ResNet9 uses where every index fits 32
+// bits, AnyWindow for every other shape.
+template <typename F>
+void with_window(const BnShape& s, F f) {
+  const bool fits = (long long)s.B * s.H * s.W * s.Q < (1ll << 31);
+  if (fits && s.ph == 1 && s.pw == 1) return f(FixedWindow<1, 1>{});
+  if (fits && s.ph == 1 && s.pw == 2) return f(FixedWindow<1, 2>{});
+  if (fits && s.ph == 2 && s.pw == 2) return f(FixedWindow<2, 2>{});
+  f(AnyWindow{});
+}
+
+// Calls f with a value of the vector type a thread owns: float2 for C = 2, float4 otherwise.
+template <typename F>
+void with_vector(int C, F f) {
+  if (C == 2) return f(f2{});
+  f(f4{});
+}
+
+// Both: f(window tag, vector value), the two template arguments a launch needs.
+template <typename F>
+void with_window_and_vector(const BnShape& s, F f) {
+  with_vector(s.C, [&](auto vec) { with_window(s, [&](auto win) { f(win, vec); }); });
 }
 
 inline int bn_blocks(long long n4) {
@@ -711,93 +663,31 @@ inline bool bn_aligned(int C, std::initializer_list<const void*> ptrs) {
   return (bits & (C == 2 ? sizeof(f2) - 1 : sizeof(f4) - 1)) == 0;
 }
 
-template <typename V>
-void bnrp_fwd(const float* y, const float* gamma, const float* beta, float* running_mean,
-              float* running_var, float momentum, float eps, const float* mean_shift,
-              long long* batches_tracked, const float* skip, float* z, float* mean, float* invstd,
-              float* workspace, const BnShape& s, hipStream_t st) {
-  const int C = s.C;
-  const long long rows = (long long)s.B * s.H * s.W, n4 = rows * s.Q;
-  const int nblk = bn_blocks(n4);
-  const V* y4 = reinterpret_cast<const V*>(y);
-  const V* k4 = reinterpret_cast<const V*>(skip);
-  V* z4 = reinterpret_cast<V*>(z);
-  hipLaunchKernelGGL(bn_stats_kernel<V>, dim3(nblk), dim3(s.A), 0, st, y4, n4, s.Q, s.A, workspace, C);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * 16), 0, st, workspace, nblk, C,
-                     (double)rows, eps, momentum, mean, invstd, running_mean, running_var, mean_shift,
-                     batches_tracked);
-  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
-  const dim3 ag(bn_blocks(n_out * 2)), ab(s.A);
-  switch (bn_fast_kind(s)) {
-    case 1: hipLaunchKernelGGL((bnrp_apply_win_kernel<1, 1, V>), ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s); break;
-    case 2: hipLaunchKernelGGL((bnrp_apply_win_kernel<1, 2, V>), ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s); break;
-    case 3: hipLaunchKernelGGL((bnrp_apply_win_kernel<2, 2, V>), ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s); break;
-    default: hipLaunchKernelGGL(bnrp_apply_kernel<V>, ag, ab, 0, st, y4, gamma, beta, mean, invstd, k4, z4, s);
-  }
+// grid of the passes over the pooled rows (two per thread and iteration)
+inline int pooled_blocks(const BnShape& s) {
+  return bn_blocks((long long)s.B * s.Ho * s.Wo * s.Q * 2);
 }
 
-template <typename V>
-void bnrp_bwd(const float* y, const float* dz, const float* gamma, const float* beta,
-              const float* mean, const float* invstd, float* dx, float* dgamma, float* dbeta,
-              float* dzero, float* workspace, const BnShape& s, hipStream_t st) {
-  const int C = s.C;
-  const long long rows = (long long)s.B * s.H * s.W;
-  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
-  const int nblk = bn_blocks(n_out * 2);
-  float* coef = workspace + (size_t)kBnMaxBlocks * 2 * C;
-  const dim3 rg(nblk), rb(s.A);
-  const V* y4 = reinterpret_cast<const V*>(y);
-  const V* dz4 = reinterpret_cast<const V*>(dz);
-  V* dx4 = reinterpret_cast<V*>(dx);
-  const int kind = bn_fast_kind(s);
-  switch (kind) {
-    case 1: hipLaunchKernelGGL((bnrp_bwd_reduce_win_kernel<1, 1, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s); break;
-    case 2: hipLaunchKernelGGL((bnrp_bwd_reduce_win_kernel<1, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s); break;
-    case 3: hipLaunchKernelGGL((bnrp_bwd_reduce_win_kernel<2, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s); break;
-    default: hipLaunchKernelGGL(bnrp_bwd_reduce_kernel<V>, rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, workspace, s);
-  }
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * 16), 0, st, workspace, nblk,
-                     C, (double)rows, dgamma, dbeta, coef, dzero);
-  switch (kind) {
-    case 1: hipLaunchKernelGGL((bnrp_bwd_apply_win_kernel<1, 1, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s); break;
-    case 2: hipLaunchKernelGGL((bnrp_bwd_apply_win_kernel<1, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s); break;
-    case 3: hipLaunchKernelGGL((bnrp_bwd_apply_win_kernel<2, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s); break;
-    default: hipLaunchKernelGGL(bnrp_bwd_apply_kernel<V>, rg, rb, 0, st, y4, dz4, gamma, beta, mean, invstd, coef, dx4, s);
-  }
+template <typename Stats>
+void launch_fwd(const float* y, const Stats& stats, const float* skip, float* z, const BnShape& s,
+                hipStream_t st) {
+  with_window_and_vector(s, [&](auto win, auto vec) {
+    using V = decltype(vec);
+    hipLaunchKernelGGL((bnrp_fwd_kernel<decltype(win), Stats, V>), dim3(pooled_blocks(s)), dim3(s.A), 0, st,
+                       reinterpret_cast<const V*>(y), stats, reinterpret_cast<const V*>(skip),
+                       reinterpret_cast<V*>(z), s);
+  });
 }
 
-template <typename V>
-void bnrp_eval_fwd(const float* y, const float* gamma, const float* beta, const float* rm,
-                   const float* rv, const float* bias, float eps, const float* skip, float* z,
-                   const BnShape& s, hipStream_t st) {
-  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
-  const dim3 ag(bn_blocks(n_out * 2)), ab(s.A);
-  const V* y4 = reinterpret_cast<const V*>(y);
-  const V* k4 = reinterpret_cast<const V*>(skip);
-  V* z4 = reinterpret_cast<V*>(z);
-  switch (bn_fast_kind(s)) {
-    case 1: hipLaunchKernelGGL((bnrp_eval_fwd_win_kernel<1, 1, V>), ag, ab, 0, st, y4, gamma, beta, rm, rv, bias, eps, k4, z4, s); break;
-    case 2: hipLaunchKernelGGL((bnrp_eval_fwd_win_kernel<1, 2, V>), ag, ab, 0, st, y4, gamma, beta, rm, rv, bias, eps, k4, z4, s); break;
-    case 3: hipLaunchKernelGGL((bnrp_eval_fwd_win_kernel<2, 2, V>), ag, ab, 0, st, y4, gamma, beta, rm, rv, bias, eps, k4, z4, s); break;
-    default: hipLaunchKernelGGL(bnrp_eval_fwd_kernel<V>, ag, ab, 0, st, y4, gamma, beta, rm, rv, bias, eps, k4, z4, s);
-  }
-}
-
-template <typename V>
-void bnrp_eval_bwd(const float* y, const float* dz, const float* gamma, const float* beta,
-                   const float* rm, const float* rv, const float* bias, float eps, float* dx,
-                   const BnShape& s, hipStream_t st) {
-  const long long n_out = (long long)s.B * s.Ho * s.Wo * s.Q;
-  const dim3 rg(bn_blocks(n_out * 2)), rb(s.A);
-  const V* y4 = reinterpret_cast<const V*>(y);
-  const V* dz4 = reinterpret_cast<const V*>(dz);
-  V* dx4 = reinterpret_cast<V*>(dx);
-  switch (bn_fast_kind(s)) {
-    case 1: hipLaunchKernelGGL((bnrp_eval_bwd_win_kernel<1, 1, V>), rg, rb, 0, st, y4, dz4, gamma, beta, rm, rv, bias, eps, dx4, s); break;
-    case 2: hipLaunchKernelGGL((bnrp_eval_bwd_win_kernel<1, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, rm, rv, bias, eps, dx4, s); break;
-    case 3: hipLaunchKernelGGL((bnrp_eval_bwd_win_kernel<2, 2, V>), rg, rb, 0, st, y4, dz4, gamma, beta, rm, rv, bias, eps, dx4, s); break;
-    default: hipLaunchKernelGGL(bnrp_eval_bwd_kernel<V>, rg, rb, 0, st, y4, dz4, gamma, beta, rm, rv, bias, eps, dx4, s);
-  }
+template <typename Stats>
+void launch_dx(const float* y, const float* dz, const Stats& stats, const float* coef, float* dx,
+               const BnShape& s, hipStream_t st) {
+  with_window_and_vector(s, [&](auto win, auto vec) {
+    using V = decltype(vec);
+    hipLaunchKernelGGL((bnrp_dx_kernel<decltype(win), Stats, V>), dim3(pooled_blocks(s)), dim3(s.A), 0, st,
+                       reinterpret_cast<const V*>(y), reinterpret_cast<const V*>(dz), stats, coef,
+                       reinterpret_cast<V*>(dx), s);
+  });
 }
 
 }  // namespace pcgmix
@@ -821,12 +711,17 @@ extern "C" int pcgmix_bnrp_fwd_f32(const float* y, const float* gamma, const flo
     return hipErrorInvalidValue;
   if (!bn_aligned(C, {y, z, skip, gamma, beta, mean, invstd})) return hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (C == 2)
-    bnrp_fwd<f2>(y, gamma, beta, running_mean, running_var, momentum, eps, mean_shift, batches_tracked,
-                 skip, z, mean, invstd, workspace, s, st);
-  else
-    bnrp_fwd<f4>(y, gamma, beta, running_mean, running_var, momentum, eps, mean_shift, batches_tracked,
-                 skip, z, mean, invstd, workspace, s, st);
+  const long long rows = (long long)B * H * W, n4 = rows * s.Q;
+  const int nblk = bn_blocks(n4);
+  with_vector(C, [&](auto vec) {
+    using V = decltype(vec);
+    hipLaunchKernelGGL(bn_stats_kernel<V>, dim3(nblk), dim3(s.A), 0, st, reinterpret_cast<const V*>(y), n4, s.Q, s.A,
+                       workspace, C);
+  });
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * 16), 0, st, workspace, nblk, C,
+                     (double)rows, eps, momentum, mean, invstd, running_mean, running_var, mean_shift,
+                     batches_tracked);
+  launch_fwd(y, TrainStats{gamma, beta, mean, invstd}, skip, z, s, st);
   return (int)hipGetLastError();
 }
 
@@ -842,10 +737,17 @@ extern "C" int pcgmix_bnrp_bwd_f32(const float* y, const float* dz, const float*
     return hipErrorInvalidValue;
   if (!bn_aligned(C, {y, dz, dx, workspace, gamma, beta, mean, invstd})) return hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (C == 2)
-    bnrp_bwd<f2>(y, dz, gamma, beta, mean, invstd, dx, dgamma, dbeta, dzero, workspace, s, st);
-  else
-    bnrp_bwd<f4>(y, dz, gamma, beta, mean, invstd, dx, dgamma, dbeta, dzero, workspace, s, st);
+  const TrainStats stats{gamma, beta, mean, invstd};
+  const int nblk = pooled_blocks(s);
+  float* coef = workspace + (size_t)kBnMaxBlocks * 2 * C;
+  with_window_and_vector(s, [&](auto win, auto vec) {
+    using V = decltype(vec);
+    hipLaunchKernelGGL((bnrp_bwd_reduce_kernel<decltype(win), V>), dim3(nblk), dim3(s.A), 0, st,
+                       reinterpret_cast<const V*>(y), reinterpret_cast<const V*>(dz), stats, workspace, s);
+  });
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * 16), 0, st, workspace, nblk,
+                     C, (double)((long long)B * H * W), dgamma, dbeta, coef, dzero);
+  launch_dx(y, dz, stats, coef, dx, s, st);
   return (int)hipGetLastError();
 }
 
@@ -860,11 +762,8 @@ extern "C" int pcgmix_bnrp_eval_fwd_f32(const float* y, const float* gamma, cons
     return hipErrorInvalidValue;
   if (!bn_aligned(C, {y, z, skip, gamma, beta, running_mean, running_var, conv_bias}))
     return hipErrorInvalidValue;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (C == 2)
-    bnrp_eval_fwd<f2>(y, gamma, beta, running_mean, running_var, conv_bias, eps, skip, z, s, st);
-  else
-    bnrp_eval_fwd<f4>(y, gamma, beta, running_mean, running_var, conv_bias, eps, skip, z, s, st);
+  launch_fwd(y, EvalStats{gamma, beta, running_mean, running_var, conv_bias, eps}, skip, z, s,
+             reinterpret_cast<hipStream_t>(stream));
   return (int)hipGetLastError();
 }
 
@@ -880,10 +779,7 @@ extern "C" int pcgmix_bnrp_eval_bwd_f32(const float* y, const float* dz, const f
     return hipErrorInvalidValue;
   if (!bn_aligned(C, {y, dz, dx, gamma, beta, running_mean, running_var, conv_bias}))
     return hipErrorInvalidValue;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (C == 2)
-    bnrp_eval_bwd<f2>(y, dz, gamma, beta, running_mean, running_var, conv_bias, eps, dx, s, st);
-  else
-    bnrp_eval_bwd<f4>(y, dz, gamma, beta, running_mean, running_var, conv_bias, eps, dx, s, st);
+  launch_dx(y, dz, EvalStats{gamma, beta, running_mean, running_var, conv_bias, eps}, nullptr, dx, s,
+            reinterpret_cast<hipStream_t>(stream));
   return (int)hipGetLastError();
 }

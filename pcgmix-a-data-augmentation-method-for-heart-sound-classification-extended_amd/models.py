@@ -697,6 +697,24 @@ def _res_block(c_in: int, c_out: int, pool: bool = False) -> nn.Sequential:
 FUSED_BN = True      # BatchNorm + ReLU + MaxPool through the HIP kernels (False: torch ops)
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
+def _stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def _pooled_output(y, ph, pw, skip):
+    """The empty channels_last output of the pooled block; ``skip`` (optional) must match it."""
+    B, C, H, W = y.shape
+    if skip is not None and (skip.shape != (B, C, H // ph, W // pw) or skip.dtype != torch.float32
+                             or not skip.is_contiguous(memory_format=torch.channels_last)):
+        raise ValueError("skip must be a float32 channels_last tensor shaped like the output")
+    return torch.empty((B, C, H // ph, W // pw), dtype=torch.float32, device=y.device,
+                       memory_format=torch.channels_last)
+
+
 class BNReLUPoolFunction(torch.autograd.Function):
     """Training-mode BatchNorm + ReLU + MaxPool on a channels_last activation through
     ``pcgmix_bnrp_{fwd,bwd}_f32``: five passes over the activation per block (forward + backward)
@@ -717,27 +735,18 @@ class BNReLUPoolFunction(torch.autograd.Function):
         # cancels it): it only shifts the running mean, and gets an exact zero gradient — both inside
         # the BatchNorm kernels.  batches_tracked: the module's counter, incremented there too.
         B, C, H, W = y.shape
-        if skip is not None and (skip.shape != (B, C, H // ph, W // pw) or skip.dtype != torch.float32
-                                 or not skip.is_contiguous(memory_format=torch.channels_last)):
-            raise ValueError("skip must be a float32 channels_last tensor shaped like the output")
+        z = _pooled_output(y, ph, pw, skip)
         lib = _lib.load()
         dev = y.device
-        z = torch.empty((B, C, H // ph, W // pw), dtype=torch.float32, device=dev,
-                        memory_format=torch.channels_last)
         mean = torch.empty(C, dtype=torch.float32, device=dev)
         invstd = torch.empty(C, dtype=torch.float32, device=dev)
         ws = torch.empty(lib.pcgmix_bnrp_workspace_floats(B, H, W, C), dtype=torch.float32, device=dev)
         g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(lib.pcgmix_bnrp_fwd_f32(
-            y.data_ptr(), g.data_ptr(), b.data_ptr(),
-            running_mean.data_ptr() if running_mean is not None else None,
-            running_var.data_ptr() if running_var is not None else None,
-            ctypes.c_float(momentum), ctypes.c_float(eps),
-            conv_bias.data_ptr() if conv_bias is not None else None,
-            batches_tracked.data_ptr() if batches_tracked is not None else None,
-            skip.data_ptr() if skip is not None else None, z.data_ptr(), mean.data_ptr(),
-            invstd.data_ptr(), ws.data_ptr(), B, H, W, C, ph, pw, stream), "pcgmix_bnrp_fwd_f32")
+            y.data_ptr(), g.data_ptr(), b.data_ptr(), _ptr(running_mean), _ptr(running_var),
+            ctypes.c_float(momentum), ctypes.c_float(eps), _ptr(conv_bias), _ptr(batches_tracked),
+            _ptr(skip), z.data_ptr(), mean.data_ptr(), invstd.data_ptr(), ws.data_ptr(),
+            B, H, W, C, ph, pw, _stream(dev)), "pcgmix_bnrp_fwd_f32")
         ctx.save_for_backward(y, g, b, mean, invstd)
         ctx.pool = (ph, pw)
         ctx.has_skip = skip is not None
@@ -757,12 +766,10 @@ class BNReLUPoolFunction(torch.autograd.Function):
         dbeta = torch.empty(C, dtype=torch.float32, device=dev)
         dbias = torch.empty(C, dtype=torch.float32, device=dev) if ctx.has_bias else None
         ws = torch.empty(lib.pcgmix_bnrp_workspace_floats(B, H, W, C), dtype=torch.float32, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _lib.check(lib.pcgmix_bnrp_bwd_f32(
             y.data_ptr(), dz.data_ptr(), g.data_ptr(), b.data_ptr(), mean.data_ptr(),
-            invstd.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(),
-            dbias.data_ptr() if dbias is not None else None, ws.data_ptr(),
-            B, H, W, C, ph, pw, stream), "pcgmix_bnrp_bwd_f32")
+            invstd.data_ptr(), dx.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), _ptr(dbias),
+            ws.data_ptr(), B, H, W, C, ph, pw, _stream(dev)), "pcgmix_bnrp_bwd_f32")
         # the residual input enters by a plain addition: its gradient is dz itself
         return (dx, dgamma, dbeta, None, None, None, None, None, None,
                 (dz if ctx.has_skip else None), dbias, None)
@@ -780,20 +787,12 @@ class BNReLUPoolEvalFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, y, gamma, beta, running_mean, running_var, eps, ph, pw, skip=None, conv_bias=None):
         B, C, H, W = y.shape
-        if skip is not None and (skip.shape != (B, C, H // ph, W // pw) or skip.dtype != torch.float32
-                                 or not skip.is_contiguous(memory_format=torch.channels_last)):
-            raise ValueError("skip must be a float32 channels_last tensor shaped like the output")
-        lib = _lib.load()
-        z = torch.empty((B, C, H // ph, W // pw), dtype=torch.float32, device=y.device,
-                        memory_format=torch.channels_last)
+        z = _pooled_output(y, ph, pw, skip)
         vecs = [t.detach().contiguous() for t in (gamma, beta, running_mean, running_var)]
         bias = conv_bias.detach().contiguous() if conv_bias is not None else None
-        stream = ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
-        _lib.check(lib.pcgmix_bnrp_eval_fwd_f32(
-            y.data_ptr(), *(t.data_ptr() for t in vecs), ctypes.c_float(eps),
-            bias.data_ptr() if bias is not None else None,
-            skip.data_ptr() if skip is not None else None, z.data_ptr(), B, H, W, C, ph, pw, stream),
-            "pcgmix_bnrp_eval_fwd_f32")
+        _lib.check(_lib.load().pcgmix_bnrp_eval_fwd_f32(
+            y.data_ptr(), *(t.data_ptr() for t in vecs), ctypes.c_float(eps), _ptr(bias), _ptr(skip),
+            z.data_ptr(), B, H, W, C, ph, pw, _stream(y.device)), "pcgmix_bnrp_eval_fwd_f32")
         ctx.save_for_backward(y, *vecs, *(() if bias is None else (bias,)))
         ctx.args = (float(eps), ph, pw, skip is not None)
         return z
@@ -806,16 +805,18 @@ class BNReLUPoolEvalFunction(torch.autograd.Function):
         B, C, H, W = y.shape
         dz = dz.contiguous(memory_format=torch.channels_last)
         dx = torch.empty_like(y)                             # preserves channels_last
-        stream = ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
         _lib.check(_lib.load().pcgmix_bnrp_eval_bwd_f32(
-            y.data_ptr(), dz.data_ptr(), *(t.data_ptr() for t in vecs), ctypes.c_float(eps),
-            bias.data_ptr() if bias is not None else None, dx.data_ptr(), B, H, W, C, ph, pw, stream),
-            "pcgmix_bnrp_eval_bwd_f32")
+            y.data_ptr(), dz.data_ptr(), *(t.data_ptr() for t in vecs), ctypes.c_float(eps), _ptr(bias),
+            dx.data_ptr(), B, H, W, C, ph, pw, _stream(y.device)), "pcgmix_bnrp_eval_bwd_f32")
         return (dx, None, None, None, None, None, None, None, (dz if has_skip else None), None)
 
 
-def _pool_window(pool):
-    return (1, 1) if pool is None else ((pool, pool) if isinstance(pool, int) else tuple(pool))
+def _window_and_skip(pool, skip):
+    """What the fused Functions take: the pooling window as two ints, ``skip`` channels_last."""
+    ph, pw = (1, 1) if pool is None else ((pool, pool) if isinstance(pool, int) else tuple(pool))
+    if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
+        skip = skip.contiguous(memory_format=torch.channels_last)
+    return int(ph), int(pw), skip
 
 
 def conv_bn_relu_pool(h, weight4, conv_bias, padding, bn, training: bool, pool, skip=None):
@@ -846,12 +847,10 @@ def conv_bn_relu_pool(h, weight4, conv_bias, padding, bn, training: bool, pool, 
                 and conv_bias.is_contiguous() and conv_bias.dtype == torch.float32:
             # counter, running-mean shift (new = (1-m) * old + m * (mean(conv) + b)) and the bias'
             # exact zero gradient all happen inside the BatchNorm kernels: no launch of their own
-            ph, pw = _pool_window(pool)
-            if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
-                skip = skip.contiguous(memory_format=torch.channels_last)
+            ph, pw, skip = _window_and_skip(pool, skip)
             return BNReLUPoolFunction.apply(h, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                            float(bn.momentum), float(bn.eps), int(ph), int(pw), skip,
-                                            conv_bias, bn.num_batches_tracked)
+                                            float(bn.momentum), float(bn.eps), ph, pw, skip, conv_bias,
+                                            bn.num_batches_tracked)
         if training and bn.track_running_stats:
             bn.num_batches_tracked.add_(1)                  # as nn.BatchNorm.forward does
         beta = bn.bias + 0.0 * conv_bias
@@ -871,11 +870,9 @@ def conv_bn_relu_pool(h, weight4, conv_bias, padding, bn, training: bool, pool, 
             bn.weight.requires_grad or bn.bias.requires_grad or conv_bias.requires_grad))
         if FUSED_BN and frozen and BNReLUPoolFunction.supported(h) and conv_bias.dtype == torch.float32:
             # running statistics, frozen parameters: one kernel forward, one for the input gradient
-            ph, pw = _pool_window(pool)
-            if skip is not None and not skip.is_contiguous(memory_format=torch.channels_last):
-                skip = skip.contiguous(memory_format=torch.channels_last)
+            ph, pw, skip = _window_and_skip(pool, skip)
             return BNReLUPoolEvalFunction.apply(h, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                                float(bn.eps), int(ph), int(pw), skip, conv_bias)
+                                                float(bn.eps), ph, pw, skip, conv_bias)
         h = F.batch_norm(h, bn.running_mean - conv_bias.detach(), bn.running_var, bn.weight,
                          bn.bias, False, 0.0, bn.eps)
     h = F.relu(h, inplace=True)

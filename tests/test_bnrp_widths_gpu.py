@@ -147,6 +147,26 @@ def test_flat_windows_route_to_the_first_maximum(B, C, H, W, ph, pw, device):
     assert not dx.any()
 
 
+# float4 with a fixed window; float2 with an uncovered last column; the generic window
+@pytest.mark.parametrize("B,C,H,W,ph,pw", [(2, 8, 4, 4, 2, 2), (2, 2, 1, 9, 1, 2), (1, 8, 1, 12, 1, 4)])
+def test_eval_dx_zeros_are_exact_for_either_sign_of_gamma(B, C, H, W, ph, pw, device):
+    """Off the arg-max, under a closed ReLU and at uncovered positions the eval input gradient is
+    +0.0, bit for bit, also in channels with gamma < 0 (a product scale * 0 would give -0.0 there)."""
+    y, gamma, beta, rm, rv, _, _, dz = _inputs(B, C, H, W, ph, pw, False, device)
+    gamma = gamma * (1 - 2 * (torch.arange(C, device=device) % 2))          # +, -, +, - ...
+    y.requires_grad_(True)
+    models.BNReLUPoolEvalFunction.apply(y, gamma, beta, rm, rv, 1e-5, ph, pw).backward(dz)
+    dx = y.grad
+    assert (dx == 0).any()
+    assert not dx.view(torch.int32)[dx == 0].any()
+
+    yd = y.detach().double().requires_grad_(True)
+    want = _pooled(F.relu(F.batch_norm(yd, rm.double(), rv.double(), gamma.double(), beta.double(),
+                                       False, 0.0, 1e-5)), ph, pw)
+    want.backward(dz.double())
+    _grad_ok(dx, yd.grad, "dx")
+
+
 def test_new_paths_are_deterministic(device):
     torch.manual_seed(0)
     outs = []
