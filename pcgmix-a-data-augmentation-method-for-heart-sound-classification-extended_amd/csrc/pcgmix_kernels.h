@@ -20,7 +20,7 @@ inline hipError_t allow_large_lds(const void* kernel, unsigned long long* done, 
   return e;
 }
 
-// pcgmix_potes.hip: split-K partial products of the skinny linear layer (see there).
+// pcgmix_skinny.hip: split-K partial products of the skinny linear layer (see there).
 // mask != nullptr: h holds the features before dropout; element e owns `bits` random bits of mask
 // (bit offset e*bits), kept iff their value >= thr, times scale.
 hipError_t launch_skinny_partial(const float* h, const float* W, float* partial, int B, int K,

@@ -17,43 +17,26 @@
 //                                 by a second tiny kernel or inside the optimiser launch
 //                                 (deterministic, no float atomics).
 //   potes_input_grad_pair_kernel  dL/dx from dL/dh2, m2 and s1 (saliency maps).
-//   potes_bwd_kernel<false>, potes_input_grad_kernel: the same two gradients for callers that kept
-//                                 no routing (they recompute the whole forward per tile).
-// The VALU forward and the earlier mask-based backward kernels (rounds 1-3: potes_fwd_kernel,
-// potes_bwd_kernel<true>, potes_bwd_fused_kernel, potes_input_grad_mask_kernel) were removed from
-// the product library in round 4; they are in the history at commit 2fa984b and their measurements
-// in profiles/r2_*, r3_*.
+//   potes_bwd_recompute_kernel, potes_input_grad_kernel: the same two gradients for callers that
+//                                 kept no routing (they recompute the whole forward per tile).
+// The entry points of these five kernels follow them.  The geometry and the ReLU/pool routing rules
+// shared with the narrow stacks are in pcgmix_potes_stack.h; the partials' reduce lives with the
+// optimiser that can fold it in (pcgmix_optim.hip), the classifier's skinny linear layer in
+// pcgmix_skinny.hip.  Earlier kernels (a VALU forward, mask-based backwards over positions) are in
+// the history at commit 2fa984b, their measurements in profiles/r2_*, r3_*.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
-#include <cmath>
-
 #include "pcgmix_kernels.h"
+#include "pcgmix_potes_stack.h"
 
 namespace pcgmix {
 
 constexpr int kC1 = 8, kC2 = 4, kK = 5;
 constexpr int kNW1 = kC1 * kK;        // 40
 constexpr int kNW2 = kC2 * kC1 * kK;  // 160
-constexpr int kNGrad = kNW1 + kC1 + kNW2 + kC2;  // 212: [gw1 | gb1 | gw2 | gb2]
-constexpr int kPotThreads = 256;
-
-struct PotesDims {
-  int T, L1, P1, L2, P2;
-};
-__host__ __device__ inline PotesDims potes_dims(int T) {
-  PotesDims d;
-  d.T = T;
-  d.L1 = T - 2;       // conv k5 pad1
-  d.P1 = d.L1 / 2;    // MaxPool1d(2), floor
-  d.L2 = d.P1 - 2;
-  d.P2 = d.L2 / 2;
-  return d;
-}
-
-// Bytes per (row, channel) of the packed first-layer selectors (see layer1_t, s1g).
-__host__ __device__ inline int potes_s1_row_bytes(const PotesDims& d) { return (d.P1 >> 2) + 1; }
+static_assert(kNGrad == kNW1 + kC1 + kNW2 + kC2, "[gw1 | gb1 | gw2 | gb2]");
 
 struct PotesWeights {  // LDS copy, broadcast-read
   float w1[kNW1], b1[kC1], w2[kNW2], b2[kC2];
@@ -90,22 +73,10 @@ __device__ __forceinline__ void lds_load8(const float* p, float (&v)[8]) {  // p
   v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
-// Layer 1 (conv 1->8 k5 + ReLU + pool 2) for pooled positions q = qlo + qq, qq in [0, nq),
-// nq % 4 == 0.  Work item = (channel, 4 consecutive qq): 12 staged inputs feed 8 conv outputs.
-// a1s[ci*nq + qq] is 0 outside [0,P1) — that IS conv2's zero padding.  If sel != nullptr it gets
-// which conv output won the pool and survived the ReLU: 0 none, 1 first (i = 2q), 2 second.
-// SWZ (forward kernel): xs and a1s are stored as two planes of float4 — even-indexed float4 in
-// plane E, odd-indexed in plane O (plane strides xplane / aplane floats) — so that the three
-// 16-byte reads of a 12-float window starting at float4 index 2g become E[g], O[g], E[g+1]:
-// consecutive lanes read consecutive 16 bytes.  With the plain layout the windows start 32 bytes
-// apart and every ds_read_b128 is a 2-way bank conflict (64 banks x 4 B, 16 lanes per group).
-// s1g (forward kernel only, may be nullptr): global plane (8, own_hi bytes) of this row that
-// receives the same pool/ReLU selectors, four per byte (own_lo unused) — what the mask-based
-// backward kernels read instead of recomputing this layer.
-// c[m] = bias + sum_k w[k] * xw[m + k], m < 8, as float2 pairs (see potes_fwd_kernel): the ONE
-// place where the first layer's arithmetic order is written down — forward and every backward
-// recompute it through this function, so they agree on which ReLUs are alive and which element
-// wins each max-pool.
+// c[m] = bias + sum_k w[k] * xw[m + k], m < 8, as float2 pairs (even and odd taps accumulate apart):
+// the ONE place where the recomputing kernels' first-layer arithmetic order is written down, so the
+// weight gradient and the input gradient agree on which ReLUs are alive and which element wins each
+// max-pool.
 __device__ __forceinline__ void conv1_window(const float (&xw)[12], const float (&w)[kK], float bias,
                                              float (&c)[8]) {
   f2 ce[4], co_[3];
@@ -139,40 +110,17 @@ __device__ __forceinline__ void conv1_window(const float (&xw)[12], const float 
   }
 }
 
-// ReLU + MaxPool(2) of one pair of conv outputs, branch-free: value, and which of the two won and
-// survived (0 none, 1 first, 2 second — torch's max-pool keeps the FIRST maximum: strict '>').
-// Written as selects: the nested-if form compiled to an exec-mask branch per position
-// (s_and_saveexec / s_cbranch_execz / s_or exec plus hazard nops, ~10 scalar instructions around
-// three vector ones).
-__device__ __forceinline__ void relu_pool2(float za, float zb, bool valid, float& a, uint32_t& sc) {
-  const float ra = fmaxf(za, 0.f), rb = fmaxf(zb, 0.f);
-  const bool second = rb > ra;
-  const float best = second ? rb : ra;
-  const uint32_t code = second ? 2u : (ra > 0.f ? 1u : 0u);
-  a = valid ? best : 0.f;
-  sc = valid ? code : 0u;
-}
-
-template <bool SWZ>
-__device__ __forceinline__ void layer1_t(const PotesWeights& W, const float* xs, float* a1s,
-                                         uint8_t* sel, int qlo, int nq, int P1, int xplane,
-                                         int aplane, uint8_t* __restrict__ s1g = nullptr,
-                                         int own_lo = 0, int own_hi = 0, int g_first = 0) {
-  // groups g_first .. nq/4-1 of every channel (g_first > 0: the caller never reads the first
-  // 4*g_first positions and the remaining items fill whole rounds of the block)
-  const int groups = nq / 4 - g_first;
+// Layer 1 (conv 1->8 k5 + ReLU + pool 2) for pooled positions q = qlo + qq, qq in [0, nq),
+// nq % 4 == 0.  Work item = (channel, 4 consecutive qq): 12 staged inputs feed 8 conv outputs.
+// a1s[ci*nq + qq] is 0 outside [0,P1) — that IS conv2's zero padding.  If sel != nullptr it gets
+// which conv output won the pool and survived the ReLU: 0 none, 1 first (i = 2q), 2 second.
+__device__ __forceinline__ void layer1(const PotesWeights& W, const float* xs, float* a1s,
+                                       uint8_t* sel, int qlo, int nq, int P1) {
+  const int groups = nq / 4;
   for (int item = threadIdx.x; item < kC1 * groups; item += kPotThreads) {
-    const int ci = item / groups, g = g_first + item - ci * groups;
+    const int ci = item / groups, g = item - ci * groups;
     float xw[12], w[kK];
-    if (SWZ) {
-      const f4 a = *reinterpret_cast<const f4*>(xs + 4 * g),
-               b = *reinterpret_cast<const f4*>(xs + xplane + 4 * g),
-               c = *reinterpret_cast<const f4*>(xs + 4 * g + 4);
-      xw[0] = a.x; xw[1] = a.y; xw[2] = a.z; xw[3] = a.w; xw[4] = b.x; xw[5] = b.y; xw[6] = b.z;
-      xw[7] = b.w; xw[8] = c.x; xw[9] = c.y; xw[10] = c.z; xw[11] = c.w;
-    } else {
-      lds_load12(xs + 8 * g, xw);
-    }
+    lds_load12(xs + 8 * g, xw);
 #pragma unroll
     for (int k = 0; k < kK; ++k) w[k] = W.w1[ci * kK + k];
     const float bias = W.b1[ci];
@@ -189,50 +137,10 @@ __device__ __forceinline__ void layer1_t(const PotesWeights& W, const float* xs,
       out[u] = a;
       sels |= sc << (8 * u);
     }
-    if (SWZ) {
-      *reinterpret_cast<f4*>(a1s + ci * 2 * aplane + (g & 1) * aplane + 4 * (g >> 1)) = out;
-      if (s1g) {
-        // Packed: selector of position q in bits 2*((q+1)&3) of byte (q+1)>>2 of the channel's
-        // row (stride own_hi = P1/4 + 1 bytes).  qlo + 1 is a multiple of 4, so a work item's four
-        // positions are exactly one byte; the one group that two neighbouring tiles both compute
-        // (the halo) gets the same byte from both — same inputs, same arithmetic.
-        const int bi = ((qlo + 1) >> 2) + g;
-        if (bi >= 0 && bi < own_hi)
-          s1g[(size_t)ci * own_hi + bi] = (uint8_t)((sels & 3u) | ((sels >> 6) & 0xcu) |
-                                                    ((sels >> 12) & 0x30u) | ((sels >> 18) & 0xc0u));
-      }
-    } else {
-      *reinterpret_cast<f4*>(a1s + ci * nq + 4 * g) = out;
-      if (sel) *reinterpret_cast<uint32_t*>(sel + ci * nq + 4 * g) = sels;
-    }
+    *reinterpret_cast<f4*>(a1s + ci * nq + 4 * g) = out;
+    if (sel) *reinterpret_cast<uint32_t*>(sel + ci * nq + 4 * g) = sels;
   }
 }
-
-__device__ __forceinline__ void layer1(const PotesWeights& W, const float* xs, float* a1s,
-                                       uint8_t* sel, int qlo, int nq, int P1, int g_first = 0) {
-  layer1_t<false>(W, xs, a1s, sel, qlo, nq, P1, 0, 0, nullptr, 0, 0, g_first);
-}
-
-// ---------------------------------------------------------------------------------- forward
-constexpr int kFwdTP = 252;                     // pooled outputs per block (4 per lane, wave = co):
-                                                // 2*252+4 = 508 layer-1 positions = 127 groups x 8
-                                                // channels = 1016 work items = 4 rounds of 256 threads
-                                                // (256 outputs would need a 5th round for 8 items)
-constexpr int kFwdNQ = 2 * kFwdTP + 4;          // 508
-
-// SAVE: also write what the mask-based backward kernels need so that they do not recompute the
-// forward: m2 (N, 4, ceil(P2/4)) — per pooled output 2 bits (0 = ReLU-dead, 1 = first conv output
-// of the pooled pair won, 2 = second), four outputs per byte — and, if s1 != nullptr, s1
-// (N, 8, P1) — the same selector for the first layer, one byte per pooled position.
-//
-// rnd != nullptr (SAVE only): the launch also fills rnd[0 .. rnd_n16) (16-byte words) with the
-// uniformly random bytes the classifier head's dropouts read (pcgmix_head.hip) — word i =
-// counter_hash(key, 4i .. 4i+3), key = two 32-bit words in device memory (or, key == nullptr, the
-// two kernel arguments).  In a captured training step this replaces an eager `random_()` launch
-// before every replay: the key changes per replay (it rides with the step payload), the graph
-// does not.
-// counter_hash and the fill loop (counter_hash_fill) are in pcgmix_kernels.h: the narrow stacks
-// (pcgmix_potes_narrow.hip) fill the same bytes from the same key.
 
 // ---------------------------------------------------------------------------------- forward, MFMA
 // The same stack on the matrix cores (round 3).  A k5 convolution with 8 or 4 output channels is a
@@ -245,7 +153,7 @@ constexpr int kFwdNQ = 2 * kFwdTP + 4;          // 508
 // so with the lane's 12-float input window xw[0..11] in registers (three conflict-free
 // ds_read_b128 from the even/odd float4 planes) the update for tap k and position offset r is
 //     D[r] = mfma(xw[r + k], w[k], D[r])
-// — no operand assembly at all (the VALU kernel spends about one v_mov per packed multiply-add on
+// — no operand assembly at all (the earlier VALU kernel spent about one v_mov per packed multiply-add on
 // it), 64 distinct LDS words feed 40 instructions, and the K = 1 form makes every accumulator an
 // in-order fmaf chain from the bias (exact f32: what a scalar loop over (ci, k) would give).
 // D[r] register i' of lane 4b+j is position 32b + 8i' + r of channel j: a lane ends up with 32
@@ -254,7 +162,7 @@ constexpr int kFwdNQ = 2 * kFwdTP + 4;          // 508
 // i.e. 2/3 of the f32 peak when nothing else issues; VALU work between two of them costs ~7 cycles
 // extra on top of its own, so the matrix instructions are kept in runs of 40 or more.
 //
-// Block = 256 threads = one tile of kFwdTP = 252 pooled outputs of one row, as in the VALU kernel:
+// Block = 256 threads = one tile of kFwdTP = 252 pooled outputs of one row:
 // 504 conv2 positions fed by 508 a1 positions = 1016 conv1 positions.
 //   layer 1: wave w takes conv1 unit u = w >> 1 (512 positions, 8 per lane) and channel half
 //            h = w & 1: one run of 40 instructions on 8 independent accumulators; pooled values to
@@ -263,9 +171,11 @@ constexpr int kFwdNQ = 2 * kFwdTP + 4;          // 508
 //   layer 2: wave w takes conv2 positions 128w .. 128w+127, two per lane (window = 6 floats, three
 //            ds_read_b64, conflict-free), 8 x 5 x 2 = 80 instructions; even and odd input channels
 //            accumulate separately (four independent chains) and are added at the end.  A lane ends
-//            with 4 consecutive pooled outputs of channel j: stores and the m2 byte as in the VALU
-//            kernel.
+//            with 4 consecutive pooled outputs of channel j: one 16-byte store and one
+//            m2 byte.
 // 480 matrix instructions per tile, 120 per wave.
+constexpr int kFwdTP = 252;                     // pooled outputs per block = tile
+constexpr int kFwdNQ = 2 * kFwdTP + 4;          // 508 layer-1 positions feed them
 constexpr int kMfXE = 132 * 4;                  // x: even float4 plane (indices 0..128 used), floats
 constexpr int kMfXFloats = (132 + 128) * 4;     // + odd plane (0..127)
 constexpr int kMfXN = 1028;                     // generic path: staged samples (float4 index <= 256)
@@ -370,6 +280,18 @@ __device__ __forceinline__ float relu_max2(float a, float b) {
   return r;
 }
 
+// SAVE: also write what the mask-based backward kernels read instead of recomputing the forward:
+// m2 (N, 4, m2row) — per pooled output 2 bits (0 = ReLU-dead, 1 = first conv output of the pooled
+// pair won, 2 = second), output p in bits 2*(p&3) of byte p>>2 — and, if s1 != nullptr, s1
+// (N, 8, s1row) — the same code for the first layer, position q in bits 2*((q+1)&3) of byte
+// (q+1)>>2 (pcgmix_potes_stack.h has both row lengths).
+// rnd != nullptr (SAVE only): the launch also fills rnd[0 .. rnd_n16) (16-byte words) with the
+// uniformly random bytes the classifier head's dropouts read (pcgmix_head.hip) — word i =
+// counter_hash(key, 4i .. 4i+3), key = two 32-bit words in device memory (or, key == nullptr, the
+// two kernel arguments).  In a captured training step this replaces an eager `random_()` launch
+// before every replay: the key changes per replay (it rides with the step payload), the graph
+// does not.  counter_hash and the fill loop (counter_hash_fill) are in pcgmix_kernels.h: the narrow
+// stacks (pcgmix_potes_narrow.hip) fill the same bytes from the same key.
 template <bool SAVE>
 __global__ __launch_bounds__(kPotThreads, 4) void potes_fwd_mfma_kernel(
     const float* __restrict__ x, const float* __restrict__ w1, const float* __restrict__ b1,
@@ -400,7 +322,7 @@ __global__ __launch_bounds__(kPotThreads, 4) void potes_fwd_mfma_kernel(
   const f4 bias1q = {bias1, bias1, bias1, bias1}, bias2q = {bias2, bias2, bias2, bias2};
   // positions 512 .. 515 of every a1 row are read (by conv2 positions nobody keeps), never written
   if (threadIdx.x < kC1) *reinterpret_cast<f4*>(a1s + threadIdx.x * kMfAPitch + 512) = f4{0.f, 0.f, 0.f, 0.f};
-  const int s1row = potes_s1_row_bytes(d), m2row = (d.P2 + 3) / 4;
+  const int s1row = d.s1row(), m2row = d.m2row();
 
   int item = blockIdx.x;
   MfStage st;
@@ -448,7 +370,7 @@ __global__ __launch_bounds__(kPotThreads, 4) void potes_fwd_mfma_kernel(
         *reinterpret_cast<f4*>(arow + 4 * i) = out;
       }
       if (SAVE && s1) {
-        // packed selectors (layer1_t): position q in bits 2*((q+1)&3) of byte (q+1)>>2; q + 1 =
+        // packed selectors: position q in bits 2*((q+1)&3) of byte (q+1)>>2; q + 1 =
         // 2 p0 + 4 g + t with g = 64u + 4 blk + i, so a float4 group is exactly byte p0/2 + g and
         // the lane's four groups are four consecutive bytes: one (unaligned) 32-bit store.
         uint32_t sel4 = 0;
@@ -592,17 +514,38 @@ constexpr int kBwdNS = 2 * kBwdTP;              // 250 owned j / owned q
 constexpr int kBwdNIpad = 512;
 constexpr int kNAcc = 53;                       // private accumulators per lane (see below)
 
-__device__ __forceinline__ int potes_bwd_tiles(const PotesDims& d) {
+__host__ __device__ inline int potes_bwd_tiles(const PotesDims& d) {
   // +2: the a1 positions 2*P2 .. 2*P2+2 still receive gradient from the last pooled outputs
   return (d.P2 + 2 + kBwdTP - 1) / kBwdTP;
 }
 
-// MASK: the second layer's ReLU/pool routing comes from the forward's m2 bytes instead of being
-// recomputed (no conv2 pass, one barrier phase less): dz2 = route(gh2, m2).
-template <bool MASK>
-__global__ __launch_bounds__(kPotThreads) void potes_bwd_kernel(
-    const float* __restrict__ x, const float* __restrict__ gh2, const uint8_t* __restrict__ m2,
-    const float* __restrict__ w1,
+// The recomputing kernels' second layer before ReLU and pool: conv2 outputs za[u], zb[u] (the two
+// candidates of pooled output pe0 + 2*lane + u, u < 2; 128 pooled outputs per wave, wave = co)
+// from the a1 rows in LDS.  a1 index = conv2 output index + k (both count from the tile's extended
+// origin).  UNROLL: of the loop over input channels.
+template <int UNROLL>
+__device__ __forceinline__ void conv2_pairs(const float* a1s, const float* w2, const float* b2,
+                                            int co, int lane, float (&za)[2], float (&zb)[2]) {
+  float aw[8];
+  za[0] = za[1] = zb[0] = zb[1] = b2[co];
+#pragma unroll UNROLL
+  for (int ci = 0; ci < kC1; ++ci) {
+    float w[kK];
+    lds_load8(a1s + ci * kBwdNQ + 4 * lane, aw);
+#pragma unroll
+    for (int k = 0; k < kK; ++k) w[k] = w2[(co * kC1 + ci) * kK + k];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int k = 0; k < kK; ++k) {
+        za[u] = fmaf(w[k], aw[2 * u + k], za[u]);
+        zb[u] = fmaf(w[k], aw[2 * u + 1 + k], zb[u]);
+      }
+  }
+}
+
+__global__ __launch_bounds__(kPotThreads) void potes_bwd_recompute_kernel(
+    const float* __restrict__ x, const float* __restrict__ gh2, const float* __restrict__ w1,
     const float* __restrict__ b1, const float* __restrict__ w2, const float* __restrict__ b2,
     float* __restrict__ partial /* gridDim.x * 212 */, int N, int T) {
   __shared__ PotesWeights W;
@@ -638,8 +581,6 @@ __global__ __launch_bounds__(kPotThreads) void potes_bwd_kernel(
   // not paid twice per item with only two resident blocks per CU.
   constexpr int kXPer = (kBwdNX + 4 + kPotThreads - 1) / kPotThreads;   // 3
   float xr[kXPer], gr[2];
-  uint32_t mr[2] = {0u, 0u};
-  const int m2s = (d.P2 + 3) / 4;
   auto prefetch = [&](unsigned it) {
     const int n = (int)(it / (unsigned)tiles), p0 = (int)(it - (unsigned)n * (unsigned)tiles) * kBwdTP;
     const int xlo = 2 * (2 * p0 - 5) - 1;
@@ -653,10 +594,6 @@ __global__ __launch_bounds__(kPotThreads) void potes_bwd_kernel(
     for (int u = 0; u < 2; ++u) {
       const int pe = p0 - 2 + 2 * lane + u;
       gr[u] = (pe >= 0 && pe < d.P2) ? gh2[((size_t)n * kC2 + wave) * d.P2 + pe] : 0.f;
-      if (MASK)
-        mr[u] = (pe >= 0 && pe < d.P2)
-                    ? (m2[((size_t)n * kC2 + wave) * m2s + (pe >> 2)] >> (2 * (pe & 3))) & 3u
-                    : 0u;
     }
   };
   if (blockIdx.x < work) prefetch(blockIdx.x);
@@ -672,40 +609,14 @@ __global__ __launch_bounds__(kPotThreads) void potes_bwd_kernel(
       if (u < kBwdNX + 4) xs[u] = xr[j];
     }
     const float g_cur[2] = {gr[0], gr[1]};
-    if (MASK) {   // dz2 on the extended range straight from the saved routing (wave = co)
-      f4 dz;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        dz[2 * u] = mr[u] == 1u ? g_cur[u] : 0.f;
-        dz[2 * u + 1] = mr[u] == 2u ? g_cur[u] : 0.f;
-      }
-      *reinterpret_cast<f4*>(dz2s + wave * kDz2Row + 4 * lane) = dz;
-    }
     if (item + gridDim.x < work) prefetch(item + gridDim.x);
     __syncthreads();
-    // Without the conv2 recompute nothing reads a1s[0..3] / sel1[0..4] (the weight gradient reads
-    // a1 from index 4, the routing from index 5): 64 groups x 8 channels = exactly two rounds of
-    // the block instead of two and a 8-thread third.
-    layer1(W, xs, a1s, sel1, qlo, kBwdNQ, d.P1, MASK ? 1 : 0);
+    layer1(W, xs, a1s, sel1, qlo, kBwdNQ, d.P1);
     __syncthreads();
-    if (!MASK) {  // conv2 + ReLU + pool on the extended range -> dz2 = dL/dz2 (wave = co, 2 pooled per lane)
+    {  // conv2 + ReLU + pool on the extended range p0-2 .. -> dz2 (wave = co, 2 pooled per lane)
       const int co = __builtin_amdgcn_readfirstlane(wave);
-      float aw[8], za[2], zb[2];
-      za[0] = za[1] = zb[0] = zb[1] = b2[co];
-#pragma unroll 2
-      for (int ci = 0; ci < kC1; ++ci) {
-        float w[kK];
-        lds_load8(a1s + ci * kBwdNQ + 4 * lane, aw);
-#pragma unroll
-        for (int k = 0; k < kK; ++k) w[k] = w2[(co * kC1 + ci) * kK + k];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int k = 0; k < kK; ++k) {
-            za[u] = fmaf(w[k], aw[2 * u + k], za[u]);
-            zb[u] = fmaf(w[k], aw[2 * u + 1 + k], zb[u]);
-          }
-      }
+      float za[2], zb[2];
+      conv2_pairs<2>(a1s, w2, b2, co, lane, za, zb);
       f4 dz;
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -721,7 +632,7 @@ __global__ __launch_bounds__(kPotThreads) void potes_bwd_kernel(
       }
       *reinterpret_cast<f4*>(dz2s + co * kDz2Row + 4 * lane) = dz;
     }
-    if (!MASK) __syncthreads();
+    __syncthreads();
     {  // back through conv2 to the owned a1 positions q = 2p0+r, then pool1/ReLU1 -> dz1
        // wave w -> channels 2w, 2w+1; lane -> r0 = 4*lane .. +3
       const int r0 = 4 * lane;
@@ -1012,7 +923,7 @@ __global__ __launch_bounds__(kPotThreads, 4) void potes_bwd_pair_kernel(
   float xr[kXPer], gr[2];
   uint32_t mb[2] = {0u, 0u};           // raw routing bytes; decoded when they are used
   int p0_pref = 0;                     // the tile the registers belong to
-  const int m2s = (d.P2 + 3) / 4;
+  const int m2s = d.m2row();
   auto prefetch = [&](unsigned it) {
     const int n = (int)(it / (unsigned)tiles), p0 = (int)(it - (unsigned)n * (unsigned)tiles) * kBwdTP;
     p0_pref = p0;
@@ -1056,7 +967,7 @@ __global__ __launch_bounds__(kPotThreads, 4) void potes_bwd_pair_kernel(
       for (int u = 0; u < 2; ++u) {
         const int pe = p0_pref - 2 + 2 * lane + u;
         const bool in = pe >= 0 && pe < d.P2;
-        const uint32_t code = in ? (mb[u] >> (2 * (pe & 3))) & 3u : 0u;
+        const uint32_t code = in ? route2_of(mb[u], pe) : 0u;
         dz[2 * u] = code == 1u ? gr[u] : 0.f;
         dz[2 * u + 1] = code == 2u ? gr[u] : 0.f;
       }
@@ -1233,22 +1144,8 @@ __global__ __launch_bounds__(kPotThreads) void potes_input_grad_kernel(
   __syncthreads();
   {  // conv2 + ReLU + pool on pe = p0-3+pp, pp < 128 -> dz2 (wave = co, 2 pooled per lane)
     const int co = __builtin_amdgcn_readfirstlane(wave);
-    float aw[8], za[2], zb[2];
-    za[0] = za[1] = zb[0] = zb[1] = b2[co];
-#pragma unroll
-    for (int ci = 0; ci < kC1; ++ci) {
-      float w[kK];
-      lds_load8(a1s + ci * kBwdNQ + 4 * lane, aw);
-#pragma unroll
-      for (int k = 0; k < kK; ++k) w[k] = w2[(co * kC1 + ci) * kK + k];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int k = 0; k < kK; ++k) {
-          za[u] = fmaf(w[k], aw[2 * u + k], za[u]);
-          zb[u] = fmaf(w[k], aw[2 * u + 1 + k], zb[u]);
-        }
-    }
+    float za[2], zb[2];
+    conv2_pairs<kC1>(a1s, w2, b2, co, lane, za, zb);
     f4 dz;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -1359,7 +1256,7 @@ __global__ __launch_bounds__(kPotThreads) void potes_input_grad_pair_kernel(
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int tiles = (T + kInNU - 1) / kInNU;
   const unsigned work = (unsigned)N * (unsigned)tiles;
-  const int m2s = (d.P2 + 3) / 4, s1row = potes_s1_row_bytes(d);
+  const int m2s = d.m2row(), s1row = d.s1row();
   for (int i = threadIdx.x; i < 4 * kC2 * kK * 2; i += kPotThreads) {
     const int h = i & 1, k = (i >> 1) % kK, co = (i >> 1) / kK % kC2, wv = (i >> 1) / (kK * kC2);
     w2ps[i] = w2[(co * kC1 + 2 * wv + h) * kK + k];
@@ -1405,7 +1302,7 @@ __global__ __launch_bounds__(kPotThreads) void potes_input_grad_pair_kernel(
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int pe = p0 - 3 + 2 * lane + u;
-        const uint32_t code = (pe >= 0 && pe < d.P2) ? (mbyte[u] >> (2 * (pe & 3))) & 3u : 0u;
+        const uint32_t code = (pe >= 0 && pe < d.P2) ? route2_of(mbyte[u], pe) : 0u;
         dz[2 * u] = code == 1u ? g[u] : 0.f;
         dz[2 * u + 1] = code == 2u ? g[u] : 0.f;
       }
@@ -1502,417 +1399,16 @@ __global__ __launch_bounds__(kPotThreads) void potes_input_grad_pair_kernel(
   }
 }
 
-// ---------------------------------------------------------------------------------- dimreduc
-// z[B][O] = h[B][K] . W[O][K]^T + bias for a SKINNY output (O <= 32; the Potes head is 19968 -> 20,
-// models.py:376).  hipBLASLt runs this shape as 32 workgroups with no split-K: 53 us at bs=256
-// for a 20 MB read.  The first version here (VALU dot products against an LDS copy of W, 16 rows x
-// 1024 columns per block) ran 18 us, bound by ds_read_b128 of W and instruction issue.  This one
-// uses the f32-input matrix instruction, v_mfma_f32_32x32x2_f32 (exact f32, same peak as the f32
-// VALU but none of its issue slots and no LDS in the inner loop):
-//   D[o][b] += W[o][k] * h[b][k]      A = W (rows o >= O are zero lanes), B = h^T, 32 x 32 x 2
-// Block = 32 batch rows x one 1024-wide K chunk, 4 waves x 256 columns.  Per 64 columns a lane
-// (r = lane & 31, half = lane >> 5) takes the 32 consecutive floats h[row r][k0 + 32 half ..]
-// and the same span of W[r][..] (through LDS, see the kernel); MFMA step j multiplies element
-// j of both (the k index may be permuted freely inside a reduction as long as A and B agree).
-// The four waves' 32x32 tiles are added in a fixed order through LDS; per-chunk partials are
-// summed in a fixed order by the consumer (deterministic).
-constexpr int kSkinnyMaxO = 32;
-constexpr int kSkinnyRows = 32;     // batch rows per block
-constexpr int kSkinnyChunk = 512;   // K elements per block (one partial per chunk)
-typedef float f16v __attribute__((ext_vector_type(16)));
-
-constexpr int kSkinnyWaves = 4;     // 128 columns per wave, in steps of 64
-constexpr int kSkStep = 64;         // columns per MFMA round
-constexpr int kSkStride = 68;       // LDS row stride in floats (16-byte aligned, +4 against banks)
-
-// The matrix instruction wants lane = (row, k-half): read straight from memory that is 32-byte
-// pieces of 32 rows per request (14.5 us).  So each wave loads its 32 x 64 tile of h and O x 64
-// tile of W row-contiguously (4 rows x 256 B per request), parks them in LDS and reads them back
-// in operand order; the next step's global loads are in flight while the MFMAs run.
-// MASK: h is the feature matrix BEFORE Dropout(p1); the dropout is applied while the tile is
-// parked in LDS: element e = b*K + k owns `bits` (1, 2, 4 or 8) consecutive random bits of `mask`
-// (bit offset e*bits), kept iff their value >= thr, kept values times `scale`.  Spares the
-// separate dropout pass (a 20 MB write and re-read at bs=256).
-// BITS: 0 = the mask's bits per element is the run-time argument; 2 = compile-time (Dropout(.25),
-// the reference's value: constant shifts and masks in the decode).
-template <int O, bool MASK, int BITS = 0>
-__global__ __launch_bounds__(kSkinnyWaves * 64) void skinny_linear_partial_kernel(
-    const float* __restrict__ h, const float* __restrict__ W, float* __restrict__ partial, int B,
-    int K, const uint8_t* __restrict__ mask, float scale, int thr, int bits_rt) {
-  const int bits = BITS ? BITS : bits_rt;
-  constexpr int kWRows = (O + 3) / 4 * 4;                                // W tile rows in LDS
-  constexpr int kWaveFloats = (32 + kWRows) * kSkStride;
-  __shared__ __align__(16) float smem[kSkinnyWaves * kWaveFloats];
-  constexpr int kPerWave = kSkinnyChunk / kSkinnyWaves;                  // 256 columns
-  constexpr int kSteps = kPerWave / kSkStep;                             // 4
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int r = lane & 31, half = lane >> 5;
-  const int row_base = blockIdx.x * kSkinnyRows, ks = blockIdx.y;
-  const int k_w = ks * kSkinnyChunk + wave * kPerWave;
-  float* xs = smem + wave * kWaveFloats;            // [32][kSkStride]
-  float* ws = xs + 32 * kSkStride;                  // [kWRows][kSkStride]
-  // loader mapping: request `it` covers rows 4 it + (lane >> 4), float4 column lane & 15
-  const int lr = lane >> 4, lc = 4 * (lane & 15);
-  f4 gx[8], gw[kWRows / 4];
-  uint32_t gm[8];
-  auto fetch = [&](int step) {
-    const int k = k_w + kSkStep * step + lc;
-    const bool ok = k < K;                          // K % 4 == 0: a float4 is inside or outside
-    const f4 z4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      const int row = row_base + 4 * it + lr;
-      const size_t e = (size_t)(row < B ? row : B - 1) * K + (ok ? k : 0);
-      const f4 v = *reinterpret_cast<const f4*>(h + e);
-      gx[it] = ok ? v : z4;
-      if (MASK) {     // the 4*bits random bits of this float4 (e % 4 == 0: byte- or word-aligned)
-        const size_t bit = e * (size_t)bits;
-        gm[it] = bits == 8   ? *reinterpret_cast<const uint32_t*>(mask + e)
-                 : bits == 4 ? (uint32_t)*reinterpret_cast<const uint16_t*>(mask + (bit >> 3))
-                             : (uint32_t)mask[bit >> 3] >> (bit & 7);
-      }
-    }
-#pragma unroll
-    for (int it = 0; it < kWRows / 4; ++it) {
-      const int o = 4 * it + lr;
-      const f4 v = *reinterpret_cast<const f4*>(W + (size_t)(o < O ? o : 0) * K + (ok ? k : 0));
-      gw[it] = (ok && o < O) ? v : z4;
-    }
-  };
-  fetch(0);
-  f16v acc;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll 1
-  for (int step = 0; step < kSteps; ++step) {
-#pragma unroll
-    for (int it = 0; it < 8; ++it) {
-      f4 v = gx[it];
-      if (MASK) {
-        const uint32_t m = gm[it], fm = (1u << bits) - 1u;
-        v.x = (int)(m & fm) >= thr ? v.x * scale : 0.f;
-        v.y = (int)((m >> bits) & fm) >= thr ? v.y * scale : 0.f;
-        v.z = (int)((m >> (2 * bits)) & fm) >= thr ? v.z * scale : 0.f;
-        v.w = (int)((m >> (3 * bits)) & fm) >= thr ? v.w * scale : 0.f;
-      }
-      *reinterpret_cast<f4*>(xs + (4 * it + lr) * kSkStride + lc) = v;
-    }
-#pragma unroll
-    for (int it = 0; it < kWRows / 4; ++it)
-      *reinterpret_cast<f4*>(ws + (4 * it + lr) * kSkStride + lc) = gw[it];
-    if (step + 1 < kSteps) fetch(step + 1);
-    __syncthreads();                                // tiles complete (all waves run in step)
-    f4 xa[8], wa[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      xa[q] = *reinterpret_cast<const f4*>(xs + r * kSkStride + 32 * half + 4 * q);
-      const f4 z4 = {0.f, 0.f, 0.f, 0.f};
-      wa[q] = r < O ? *reinterpret_cast<const f4*>(ws + (r < O ? r : 0) * kSkStride + 32 * half + 4 * q)
-                    : z4;
-    }
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[q].x, xa[q].x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[q].y, xa[q].y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[q].z, xa[q].z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[q].w, xa[q].w, acc, 0, 0, 0);
-    }
-    __syncthreads();                                // tiles consumed before they are overwritten
-  }
-  // fixed-order sum of the waves' tiles (reusing the staging memory), then one partial per block
-  float* red = smem;                                // [kSkinnyWaves - 1][16][64]
-  if (wave > 0) {
-#pragma unroll
-    for (int i = 0; i < 16; ++i) red[((wave - 1) * 16 + i) * 64 + lane] = acc[i];
-  }
-  __syncthreads();
-  if (wave > 0) return;
-#pragma unroll
-  for (int w = 0; w < kSkinnyWaves - 1; ++w)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] += red[(w * 16 + i) * 64 + lane];
-  // C/D layout: column = lane & 31 (batch row), row o = (i & 3) + 8 (i >> 2) + 4 half
-  const int row = row_base + r;
-  if (row < B) {
-    float* dst = partial + ((size_t)ks * B + row) * O;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int o = (i & 3) + 8 * (i >> 2) + 4 * half;
-      if (o < O) dst[o] = acc[i];
-    }
-  }
-}
-
-__global__ void skinny_linear_reduce_kernel(const float* __restrict__ partial,
-                                            const float* __restrict__ bias, float* __restrict__ z,
-                                            int B, int O, int KS) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * O) return;
-  float v = bias ? bias[i % O] : 0.f;
-  for (int ks = 0; ks < KS; ++ks) v += partial[(size_t)ks * B * O + i];
-  z[i] = v;
-}
-
-// Sum the per-block partial vectors in a fixed order: grads[e] = sum_g partial[g][e].
-// Column e of the G partial rows, summed by one 256-thread block in a fixed order (thread t takes
-// rows t, t + 256, ...; then a tree over the threads): the value is in red[0] for thread 0.
-__device__ __forceinline__ float potes_reduce_column(const float* __restrict__ partial, int G, int e,
-                                                     float* red) {
-  float a = 0.f;
-  for (int g = threadIdx.x; g < G; g += kPotThreads) a += partial[(size_t)g * kNGrad + e];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int o = kPotThreads / 2; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-    __syncthreads();
-  }
-  return red[0];
-}
-
-__global__ __launch_bounds__(kPotThreads) void potes_reduce_kernel(const float* __restrict__ partial,
-                                                                   float* __restrict__ grads,
-                                                                   int G) {
-  __shared__ float red[kPotThreads];
-  const float v = potes_reduce_column(partial, G, blockIdx.x, red);
-  if (threadIdx.x == 0) grads[blockIdx.x] = v;
-}
-
-// ---------------------------------------------------------------------------------- optimiser
-// clip_grad_value_ + Adam (L2 weight decay) for one parameter tensor in one pass
-// (train_model.py:557-558, 404-407, 566).  torch's foreach/fused Adam launches 512-thread blocks
-// per 65536-element chunk: the 400k-element `dimreduc.weight` gets 7 blocks (41 us), and value
-// clipping is two more foreach launches.  Same update rule as torch.optim.Adam:
-//   g = clamp(g, -clip, clip) + wd * p;  m = lerp(m, g, 1-b1);  v = b2*v + (1-b2)*g*g
-//   p -= (lr / (1-b1^t)) * m / (sqrt(v) / sqrt(1-b2^t) + eps)
-__global__ __launch_bounds__(256) void adam_clip_kernel(float* __restrict__ p,
-                                                        const float* __restrict__ g,
-                                                        float* __restrict__ m,
-                                                        float* __restrict__ v, long long n,
-                                                        float clip, float wd, float one_m_b1,
-                                                        float b2, float one_m_b2, float step_size,
-                                                        float inv_bc2_sqrt, float eps) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long long)gridDim.x * blockDim.x) {
-    float gi = g[i];
-    if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
-    const float pi = p[i];
-    gi = fmaf(wd, pi, gi);
-    float mi = m[i], vi = v[i];
-    mi = fmaf(one_m_b1, gi - mi, mi);                 // exp_avg.lerp_(grad, 1 - beta1)
-    vi = fmaf(one_m_b2 * gi, gi, b2 * vi);            // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
-    const float denom = sqrtf(vi) * inv_bc2_sqrt + eps;
-    p[i] = pi - step_size * (mi / denom);
-    m[i] = mi;
-    v[i] = vi;
-  }
-}
-
-// All parameter tensors of a model in ONE launch: eight ~3 us launches (six of them on tensors of
-// <= 160 elements) become one.  The tensor table travels by value in the kernel arguments; a block
-// owns kAdamEPB consecutive elements of one tensor and finds it by a uniform scan of blk_start.
-constexpr int kAdamMaxTensors = 32;
-constexpr int kAdamEPB = 1024;
-struct AdamTable {
-  float* p[kAdamMaxTensors];
-  const float* g[kAdamMaxTensors];
-  float* m[kAdamMaxTensors];
-  float* v[kAdamMaxTensors];
-  long long n[kAdamMaxTensors];
-  int blk_start[kAdamMaxTensors + 1];
-  int count;
-};
-
-// hyper != nullptr: the eight scalars are read from device memory instead (clip, wd, 1-b1, b2,
-// 1-b2, step_size, 1/sqrt(bc2), eps — pcgmix_adam_hyper's layout): a launch captured in a
-// hipGraph then follows OneCycleLR's lr/beta1 and the bias corrections from replay to replay.
-// partial != nullptr: the launch carries kNGrad EXTRA blocks behind the table's own — block
-// red_first + e sums column e of the conv stack's per-block gradient partials exactly as
-// potes_reduce_kernel does (same order, same bits), stores it at grads[e] (what the parameters'
-// .grad tensors alias) and applies the update to the one element it belongs to: the tensor of the
-// table whose gradient pointer lies inside grads[0 .. kNGrad) (such tensors own no blocks of the
-// table).  One launch instead of two at the end of a captured training step.
-__global__ __launch_bounds__(256) void adam_clip_multi_kernel(AdamTable tab, float clip, float wd,
-                                                              float one_m_b1, float b2,
-                                                              float one_m_b2, float step_size,
-                                                              float inv_bc2_sqrt, float eps,
-                                                              const float* __restrict__ hyper,
-                                                              const float* __restrict__ partial,
-                                                              float* __restrict__ grads, int G,
-                                                              int red_first) {
-  if (hyper) {
-    clip = hyper[0]; wd = hyper[1]; one_m_b1 = hyper[2]; b2 = hyper[3];
-    one_m_b2 = hyper[4]; step_size = hyper[5]; inv_bc2_sqrt = hyper[6]; eps = hyper[7];
-  }
-  if (partial && (int)blockIdx.x >= red_first) {
-    __shared__ float red[kPotThreads];
-    const int e = (int)blockIdx.x - red_first;
-    float gi = potes_reduce_column(partial, G, e, red);
-    if (threadIdx.x != 0) return;
-    grads[e] = gi;
-    const float* ge = grads + e;
-    for (int t = 0; t < tab.count; ++t) {
-      if (ge >= tab.g[t] && ge < tab.g[t] + tab.n[t]) {
-        const long long i = ge - tab.g[t];
-        if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
-        const float pi = tab.p[t][i];
-        gi = fmaf(wd, pi, gi);
-        float mi = tab.m[t][i], vi = tab.v[t][i];
-        mi = fmaf(one_m_b1, gi - mi, mi);
-        vi = fmaf(one_m_b2 * gi, gi, b2 * vi);
-        const float denom = sqrtf(vi) * inv_bc2_sqrt + eps;
-        tab.p[t][i] = pi - step_size * (mi / denom);
-        tab.m[t][i] = mi;
-        tab.v[t][i] = vi;
-        return;
-      }
-    }
-    return;
-  }
-  int t = 0;
-  while (t + 1 < tab.count && (int)blockIdx.x >= tab.blk_start[t + 1]) ++t;
-  float* __restrict__ p = tab.p[t];
-  const float* __restrict__ g = tab.g[t];
-  float* __restrict__ m = tab.m[t];
-  float* __restrict__ v = tab.v[t];
-  const long long n = tab.n[t];
-  const long long base = (long long)((int)blockIdx.x - tab.blk_start[t]) * kAdamEPB;
-#pragma unroll
-  for (int j = 0; j < kAdamEPB / 256; ++j) {
-    const long long i = base + j * 256 + threadIdx.x;
-    if (i >= n) break;
-    float gi = g[i];
-    if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
-    const float pi = p[i];
-    gi = fmaf(wd, pi, gi);
-    float mi = m[i], vi = v[i];
-    mi = fmaf(one_m_b1, gi - mi, mi);
-    vi = fmaf(one_m_b2 * gi, gi, b2 * vi);
-    const float denom = sqrtf(vi) * inv_bc2_sqrt + eps;
-    p[i] = pi - step_size * (mi / denom);
-    m[i] = mi;
-    v[i] = vi;
-  }
-}
-
 }  // namespace pcgmix
 
-extern "C" int pcgmix_adam_hyper(float clip, float lr, float beta1, float beta2, float eps,
-                                 float weight_decay, long long step, float* out8) {
-  if (!out8 || step < 1) return hipErrorInvalidValue;
-  // bias corrections in float64 on the host, as torch computes them from Python floats
-  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-  out8[0] = clip;
-  out8[1] = weight_decay;
-  out8[2] = 1.0f - beta1;
-  out8[3] = beta2;
-  out8[4] = 1.0f - beta2;
-  out8[5] = (float)((double)lr / bc1);
-  out8[6] = (float)(1.0 / std::sqrt(bc2));
-  out8[7] = eps;
-  return hipSuccess;
-}
-
-static int adam_multi_launch(int n_tensors, float* const* p, const float* const* g, float* const* m,
-                             float* const* v, const long long* n, const float* h8,
-                             const float* hyper_dev, hipStream_t stream,
-                             const float* partial = nullptr, float* grads = nullptr, int G = 0);
-
-extern "C" int pcgmix_adam_clip_multi_dev_f32(int n_tensors, float* const* p, const float* const* g,
-                                              float* const* m, float* const* v, const long long* n,
-                                              const float* hyper_dev, pcgmix_stream_t stream) {
-  if (n_tensors < 0 || !hyper_dev || (n_tensors > 0 && (!p || !g || !m || !v || !n)))
-    return hipErrorInvalidValue;
-  const float zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  return adam_multi_launch(n_tensors, p, g, m, v, n, zero8, hyper_dev,
-                           reinterpret_cast<hipStream_t>(stream));
-}
-
-extern "C" int pcgmix_adam_clip_multi_reduce_dev_f32(int n_tensors, float* const* p,
-                                                     const float* const* g, float* const* m,
-                                                     float* const* v, const long long* n,
-                                                     const float* hyper_dev, const float* partial,
-                                                     float* grads, int G, pcgmix_stream_t stream) {
-  if (n_tensors <= 0 || !hyper_dev || !p || !g || !m || !v || !n || !partial || !grads || G <= 0)
-    return hipErrorInvalidValue;
-  const float zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  return adam_multi_launch(n_tensors, p, g, m, v, n, zero8, hyper_dev,
-                           reinterpret_cast<hipStream_t>(stream), partial, grads, G);
-}
-
-extern "C" int pcgmix_potes_reduce_f32(const float* partial, float* grads, int G, pcgmix_stream_t stream) {
-  if (!partial || !grads || G <= 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(pcgmix::potes_reduce_kernel, dim3(pcgmix::kNGrad), dim3(pcgmix::kPotThreads), 0,
-                     reinterpret_cast<hipStream_t>(stream), partial, grads, G);
-  return (int)hipGetLastError();
-}
-
-extern "C" int pcgmix_adam_clip_multi_f32(int n_tensors, float* const* p, const float* const* g,
-                                          float* const* m, float* const* v, const long long* n,
-                                          float clip, float lr, float beta1, float beta2, float eps,
-                                          float weight_decay, long long step,
-                                          pcgmix_stream_t stream) {
-  if (n_tensors < 0 || step < 1 || (n_tensors > 0 && (!p || !g || !m || !v || !n)))
-    return hipErrorInvalidValue;
-  float h8[8];
-  pcgmix_adam_hyper(clip, lr, beta1, beta2, eps, weight_decay, step, h8);
-  return adam_multi_launch(n_tensors, p, g, m, v, n, h8, nullptr,
-                           reinterpret_cast<hipStream_t>(stream));
-}
-
-static int adam_multi_launch(int n_tensors, float* const* p, const float* const* g, float* const* m,
-                             float* const* v, const long long* n, const float* h8,
-                             const float* hyper_dev, hipStream_t stream, const float* partial,
-                             float* grads, int G) {
-  using namespace pcgmix;
-  if (partial && n_tensors > kAdamMaxTensors) return hipErrorInvalidValue;   // one table, one launch
-  for (int first = 0; first < n_tensors; first += kAdamMaxTensors) {
-    AdamTable tab;
-    tab.count = 0;
-    int blocks = 0;
-    const int last = first + kAdamMaxTensors < n_tensors ? first + kAdamMaxTensors : n_tensors;
-    for (int i = first; i < last; ++i) {
-      if (n[i] < 0 || (n[i] > 0 && (!p[i] || !g[i] || !m[i] || !v[i]))) return hipErrorInvalidValue;
-      if (n[i] == 0) continue;
-      // tensors whose gradient lives in grads[0 .. kNGrad) are updated by the reduction blocks
-      const bool deferred = partial && g[i] >= grads && g[i] < grads + kNGrad;
-      const long long nb = deferred ? 0 : (n[i] + kAdamEPB - 1) / kAdamEPB;
-      if (nb > (1ll << 30) - blocks) return hipErrorInvalidValue;
-      const int k = tab.count++;
-      tab.p[k] = p[i]; tab.g[k] = g[i]; tab.m[k] = m[i]; tab.v[k] = v[i]; tab.n[k] = n[i];
-      tab.blk_start[k] = blocks;
-      blocks += (int)nb;
-    }
-    if (tab.count == 0) continue;
-    tab.blk_start[tab.count] = blocks;
-    const int red_first = blocks;
-    if (partial) blocks += kNGrad;
-    hipLaunchKernelGGL(adam_clip_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tab,
-                       h8[0], h8[1], h8[2], h8[3], h8[4], h8[5], h8[6], h8[7], hyper_dev, partial, grads, G,
-                       red_first);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
+// Cap on a launch's persistent blocks: `dflt`, or what the environment variable `name` says
+// (tuning runs) if that is in [1, max].
+static long long env_blocks(const char* name, long long dflt, long long max) {
+  if (const char* env = getenv(name)) {
+    const long long v = atoll(env);
+    if (v >= 1 && v <= max) return v;
   }
-  return hipSuccess;
-}
-
-extern "C" int pcgmix_adam_clip_f32(float* p, const float* g, float* m, float* v, long long n,
-                                    float clip, float lr, float beta1, float beta2, float eps,
-                                    float weight_decay, long long step, pcgmix_stream_t stream) {
-  using namespace pcgmix;
-  if (!p || !g || !m || !v || n < 0 || step < 1) return hipErrorInvalidValue;
-  if (n == 0) return hipSuccess;
-  // bias corrections in float64 on the host, as torch computes them from Python floats
-  const double bc1 = 1.0 - std::pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - std::pow((double)beta2, (double)step);
-  const float step_size = (float)((double)lr / bc1);
-  const float inv_bc2_sqrt = (float)(1.0 / std::sqrt(bc2));
-  long long blocks = (n + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(adam_clip_kernel, dim3((unsigned)blocks), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), p, g, m, v, n, clip, weight_decay,
-                     1.0f - beta1, beta2, 1.0f - beta2, step_size, inv_bc2_sqrt, eps);
-  return (int)hipGetLastError();
+  return dflt;
 }
 
 extern "C" int pcgmix_potes_out_len(int T) {
@@ -1921,26 +1417,17 @@ extern "C" int pcgmix_potes_out_len(int T) {
 
 extern "C" int pcgmix_potes_bwd_blocks(int N, int T) {
   if (N <= 0 || T < 14) return 0;
-  const pcgmix::PotesDims d = pcgmix::potes_dims(T);
-  const long long work = (long long)N * ((d.P2 + 2 + pcgmix::kBwdTP - 1) / pcgmix::kBwdTP);  // = tiles
+  const long long work = (long long)N * pcgmix::potes_bwd_tiles(pcgmix::potes_dims(T));
   // persistent blocks: 4 per CU (128 VGPRs, 4 waves per SIMD: 51.9 us at 1024 blocks, 53.0 at 768,
   // 52.6 at 1536; profiles/r4_potes_bwd_sweep.txt)
-  long long cap = 1024;
-  if (const char* env = getenv("PCGMIX_POTES_BWD_BLOCKS")) {   // tuning runs
-    const long long v = atoll(env);
-    if (v >= 1 && v <= 65535) cap = v;
-  }
+  const long long cap = env_blocks("PCGMIX_POTES_BWD_BLOCKS", 1024, 65535);
   return (int)(work < cap ? work : cap);
 }
 
 // Persistent blocks of the matrix-core forward: four per CU (128 VGPRs), tiles handed out by stride.
 static unsigned potes_fwd_mfma_blocks(int N, const pcgmix::PotesDims& d) {
   const long long items = (long long)N * ((d.P2 + pcgmix::kFwdTP - 1) / pcgmix::kFwdTP);
-  long long cap = 4 * 256;
-  if (const char* env = getenv("PCGMIX_POTES_FWD_BLOCKS")) {   // tuning runs
-    const long long v = atoll(env);
-    if (v >= 1 && v <= (1 << 20)) cap = v;
-  }
+  const long long cap = env_blocks("PCGMIX_POTES_FWD_BLOCKS", 4 * 256, 1 << 20);
   return (unsigned)(items < cap ? items : cap);
 }
 
@@ -1961,8 +1448,8 @@ extern "C" int pcgmix_potes_stack_fwd_f32(const float* x, const float* w1, const
 extern "C" long long pcgmix_potes_mask_bytes(int N, int T, int layer) {
   if (N <= 0 || T < 14) return 0;
   const pcgmix::PotesDims d = pcgmix::potes_dims(T);
-  return layer == 2 ? (long long)N * pcgmix::kC2 * ((d.P2 + 3) / 4)
-                    : (layer == 1 ? (long long)N * pcgmix::kC1 * pcgmix::potes_s1_row_bytes(d) : 0);
+  return layer == 2 ? (long long)N * pcgmix::kC2 * d.m2row()
+                    : (layer == 1 ? (long long)N * pcgmix::kC1 * d.s1row() : 0);
 }
 
 extern "C" int pcgmix_potes_stack_fwd_save_f32(const float* x, const float* w1, const float* b1,
@@ -2007,10 +1494,9 @@ extern "C" int pcgmix_potes_stack_bwd_f32(const float* x, const float* grad_h2, 
     return hipErrorInvalidValue;
   const int G = pcgmix_potes_bwd_blocks(N, T);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(potes_bwd_kernel<false>, dim3((unsigned)G), dim3(kPotThreads), 0, s, x, grad_h2,
-                     nullptr, w1, b1, w2, b2, partial, N, T);
-  hipLaunchKernelGGL(potes_reduce_kernel, dim3(kNGrad), dim3(kPotThreads), 0, s, partial, grads, G);
-  return (int)hipGetLastError();
+  hipLaunchKernelGGL(potes_bwd_recompute_kernel, dim3((unsigned)G), dim3(kPotThreads), 0, s, x,
+                     grad_h2, w1, b1, w2, b2, partial, N, T);
+  return pcgmix_potes_reduce_f32(partial, grads, G, stream);
 }
 
 extern "C" int pcgmix_potes_stack_bwd_mask_f32(const float* x, const float* grad_h2,
@@ -2024,9 +1510,8 @@ extern "C" int pcgmix_potes_stack_bwd_mask_f32(const float* x, const float* grad
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(potes_bwd_pair_kernel, dim3((unsigned)G), dim3(kPotThreads), 0, s, x, grad_h2,
                      m2, w1, b1, w2, b2, partial, N, T);
-  if (grads)      // NULL: the caller reduces later (pcgmix_adam_clip_multi_reduce_dev_f32 / pcgmix_potes_reduce_f32)
-    hipLaunchKernelGGL(potes_reduce_kernel, dim3(kNGrad), dim3(kPotThreads), 0, s, partial, grads, G);
-  return (int)hipGetLastError();
+  // grads == NULL: the caller reduces later (pcgmix_adam_clip_multi_reduce_dev_f32 / pcgmix_potes_reduce_f32)
+  return grads ? pcgmix_potes_reduce_f32(partial, grads, G, stream) : (int)hipGetLastError();
 }
 
 extern "C" int pcgmix_potes_stack_input_grad_mask_f32(const float* grad_h2, const uint8_t* m2,
@@ -2040,73 +1525,10 @@ extern "C" int pcgmix_potes_stack_input_grad_mask_f32(const float* grad_h2, cons
   // persistent blocks: 6 resident per CU (81 VGPRs, 22 KB of LDS); twice that many, the second
   // half starting as the first ends, evens out the tail: 1024: 34.0, 1536: 33.2, 2048: 31.3,
   // 3072: 30.6 us at N = 1024 x 5000 (profiles/r4_potes_ingrad_pair.txt)
-  long long cap = 3072;
-  if (const char* env = getenv("PCGMIX_POTES_INGRAD_BLOCKS")) {   // tuning runs
-    const long long v = atoll(env);
-    if (v >= 1 && v <= 65535) cap = v;
-  }
+  const long long cap = env_blocks("PCGMIX_POTES_INGRAD_BLOCKS", 3072, 65535);
   const long long work = (long long)N * ((T + kInNU - 1) / kInNU);
   hipLaunchKernelGGL(potes_input_grad_pair_kernel, dim3((unsigned)(work < cap ? work : cap)),
                      dim3(kPotThreads), 0, reinterpret_cast<hipStream_t>(stream), grad_h2, m2, s1, w1,
                      w2, grad_x, N, T);
-  return (int)hipGetLastError();
-}
-
-extern "C" int pcgmix_skinny_linear_splits(int B, int K) {
-  if (B <= 0 || K <= 0) return 0;
-  return (K + pcgmix::kSkinnyChunk - 1) / pcgmix::kSkinnyChunk;   // one partial per K chunk
-}
-
-namespace pcgmix {
-// Launch the split-K partial products of z = h W^T (shared with the fused head, pcgmix_head.hip).
-hipError_t launch_skinny_partial(const float* h, const float* W, float* partial, int B, int K,
-                                 int O, hipStream_t s, const uint8_t* mask, float scale, int thr,
-                                 int bits) {
-  if (!h || !W || !partial || B <= 0 || K <= 0 || (K & 3) || O <= 0 || O > kSkinnyMaxO)
-    return hipErrorInvalidValue;
-  if ((reinterpret_cast<uintptr_t>(h) | reinterpret_cast<uintptr_t>(W)) & 15)
-    return hipErrorInvalidValue;
-  if (mask && ((reinterpret_cast<uintptr_t>(mask) & 3) ||
-               (bits != 1 && bits != 2 && bits != 4 && bits != 8)))
-    return hipErrorInvalidValue;
-  const int KS = pcgmix_skinny_linear_splits(B, K);
-  dim3 grid((unsigned)((B + kSkinnyRows - 1) / kSkinnyRows), (unsigned)KS),
-      block(kSkinnyWaves * 64);
-  if (O == 20 && mask && bits == 2) {
-    hipLaunchKernelGGL((skinny_linear_partial_kernel<20, true, 2>), grid, block, 0, s, h, W, partial, B,
-                       K, mask, scale, thr, bits);
-  } else if (O == 20 && mask) {
-    hipLaunchKernelGGL((skinny_linear_partial_kernel<20, true>), grid, block, 0, s, h, W, partial, B, K,
-                       mask, scale, thr, bits);
-  } else if (mask) {
-    return hipErrorInvalidValue;                      // the masked variant exists for the Potes head
-  } else if (O == 20) {
-    hipLaunchKernelGGL((skinny_linear_partial_kernel<20, false>), grid, block, 0, s, h, W, partial, B,
-                       K, nullptr, 1.f, 0, 8);
-  } else if (O == 8) {
-    hipLaunchKernelGGL((skinny_linear_partial_kernel<8, false>), grid, block, 0, s, h, W, partial, B,
-                       K, nullptr, 1.f, 0, 8);
-  } else if (O == 16) {
-    hipLaunchKernelGGL((skinny_linear_partial_kernel<16, false>), grid, block, 0, s, h, W, partial, B,
-                       K, nullptr, 1.f, 0, 8);
-  } else {
-    return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-}  // namespace pcgmix
-
-extern "C" int pcgmix_skinny_linear_fwd_f32(const float* h, const float* W, const float* bias,
-                                            float* partial, float* z, int B, int K, int O,
-                                            pcgmix_stream_t stream) {
-  using namespace pcgmix;
-  if (!z) return hipErrorInvalidValue;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const hipError_t e = launch_skinny_partial(h, W, partial, B, K, O, s, nullptr, 1.f, 0, 8);
-  if (e != hipSuccess) return (int)e;
-  const int KS = pcgmix_skinny_linear_splits(B, K);
-  const int n = B * O;
-  hipLaunchKernelGGL(skinny_linear_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
-                     partial, bias, z, B, O, KS);
   return (int)hipGetLastError();
 }

@@ -24,11 +24,12 @@
 //   narrow_input_grad_kernel  dL/dx from dL/dh2, m2, s1 and the weights alone; a thread owns four
 //                             consecutive inputs.
 // Arithmetic: float32, every conv output an in-order fmaf chain from the bias over (input channel,
-// tap); ReLU / max-pool routing by relu_pool2's rule of pcgmix_potes.hip (first maximum wins).
+// tap); ReLU / max-pool routing by relu_pool2 (pcgmix_potes_stack.h: first maximum wins).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "pcgmix_kernels.h"
+#include "pcgmix_potes_stack.h"
 
 namespace pcgmix {
 namespace narrow {
@@ -40,27 +41,14 @@ constexpr int kNarXN = 4 * kNarTP + 16;     // staged inputs x[4 p0 - 4 .. 4 p0 
 constexpr int kInTU = 4 * kThreads;         // inputs per block of the input gradient
 constexpr int kMaxN = 65535;                // rows: grid.y
 
-struct Dims {
-  int T, P1, P2, s1row, m2row, pext;
-};
-__host__ __device__ inline Dims dims(int T) {
-  Dims d;
-  d.T = T;
-  d.P1 = (T - 2) / 2;           // conv k5 pad1, MaxPool1d(2) floor
-  d.P2 = (d.P1 - 2) / 2;
-  d.s1row = (d.P1 >> 2) + 1;    // bytes per (row, channel) of s1
-  d.m2row = (d.P2 + 3) / 4;     // bytes per (row, channel) of m2
-  // pooled positions the forward walks: p < P2 are outputs; even p up to 2*(P1/4) each write one
-  // byte of s1 (byte p/2 holds first-layer positions 2p-1 .. 2p+2), and 2*(P1/4) >= P2
-  d.pext = 2 * d.s1row - 1;
-  return d;
-}
 // without s1 (inference, weight gradient only) only the outputs p < P2 matter
-__host__ __device__ inline int fwd_tiles(const Dims& d, bool with_s1) {
-  return ((with_s1 ? d.pext : d.P2) + kNarTP - 1) / kNarTP;
+// with it the forward walks further: even p up to 2*(P1/4) each write one byte of s1 (byte p/2 holds
+// first-layer positions 2p-1 .. 2p+2), and 2*(P1/4) >= P2
+__host__ __device__ inline int fwd_tiles(const PotesDims& d, bool with_s1) {
+  return ((with_s1 ? 2 * d.s1row() - 1 : d.P2) + kNarTP - 1) / kNarTP;
 }
 // the weight gradient owns first-layer positions q = 2p, 2p+1 < P1 and outputs p < P2 <= P1/2
-__host__ __device__ inline int bwd_tiles(const Dims& d) {
+__host__ __device__ inline int bwd_tiles(const PotesDims& d) {
   return ((d.P1 + 1) / 2 + kNarTP - 1) / kNarTP;
 }
 
@@ -113,17 +101,6 @@ __device__ __forceinline__ void load_window(const float* xs, float (&xw)[20]) {
   }
 }
 
-// ReLU + MaxPool(2) of a pair of conv outputs: the value, and 0 dead / 1 first won / 2 second won
-// (torch keeps the FIRST maximum: strict '>'), as relu_pool2 of pcgmix_potes.hip.
-__device__ __forceinline__ void relu_pool2(float za, float zb, bool valid, float& a, uint32_t& sc) {
-  const float ra = fmaxf(za, 0.f), rb = fmaxf(zb, 0.f);
-  const bool second = rb > ra;
-  const float best = second ? rb : ra;
-  const uint32_t code = second ? 2u : (ra > 0.f ? 1u : 0u);
-  a = valid ? best : 0.f;
-  sc = valid ? code : 0u;
-}
-
 // First layer around pooled output p from the window xw[e] = x[4p - 4 + e]: a1[c][r] and its
 // selector for positions q = 2p - 1 + r, r < 6 (zero outside [0, P1): conv2's padding).  Conv output
 // i = 2q + h = 4p - 2 + m (m = 2r + h) reads x[i - 1 + k] = xw[1 + m + k].
@@ -172,7 +149,8 @@ __global__ __launch_bounds__(kThreads) void narrow_fwd_kernel(
                       ((long long)blockIdx.y * gridDim.x + blockIdx.x) * kThreads + threadIdx.x,
                       (long long)gridDim.x * gridDim.y * kThreads);
   __shared__ __align__(16) float xs[kNarXN];
-  const Dims d = dims(T);
+  const PotesDims d = potes_dims(T);
+  const int s1row = d.s1row(), m2row = d.m2row();
   const int n = blockIdx.y, p0 = blockIdx.x * kNarTP, p = p0 + (int)threadIdx.x;
   const float* xrow = x + (size_t)n * T;
   const bool fast = !(T & 3) && !(reinterpret_cast<uintptr_t>(x) & 15);
@@ -185,11 +163,11 @@ __global__ __launch_bounds__(kThreads) void narrow_fwd_kernel(
   float a1[C1][6];
   uint32_t sel[C1][6];
   layer1<C1>(W.w1, W.b1, xw, p, d.P1, a1, sel);
-  if (s1 && !(p & 1) && (p >> 1) < d.s1row) {
+  if (s1 && !(p & 1) && (p >> 1) < s1row) {
     // position q in bits 2*((q+1)&3) of byte (q+1)>>2: q + 1 = 2p + r, p even: r < 4 is byte p/2
 #pragma unroll
     for (int c = 0; c < C1; ++c)
-      s1[((size_t)n * C1 + c) * d.s1row + (p >> 1)] =
+      s1[((size_t)n * C1 + c) * s1row + (p >> 1)] =
           (uint8_t)(sel[c][0] | (sel[c][1] << 2) | (sel[c][2] << 4) | (sel[c][3] << 6));
   }
   const bool own = p < d.P2;
@@ -206,7 +184,7 @@ __global__ __launch_bounds__(kThreads) void narrow_fwd_kernel(
       uint32_t b = code << (2 * (threadIdx.x & 3));
       b |= __shfl_xor(b, 1);
       b |= __shfl_xor(b, 2);
-      if (own && !(threadIdx.x & 3)) m2[((size_t)n * C2 + co) * d.m2row + (p >> 2)] = (uint8_t)b;
+      if (own && !(threadIdx.x & 3)) m2[((size_t)n * C2 + co) * m2row + (p >> 2)] = (uint8_t)b;
     }
   }
 }
@@ -224,7 +202,7 @@ struct Routed {
     code = 0u;
     if (p >= 0 && p < P2) {
       gv = g[(size_t)co * P2 + p];
-      code = (m[(size_t)co * m2row + (p >> 2)] >> (2 * (p & 3))) & 3u;
+      code = route2(m + (size_t)co * m2row, p);
     }
   }
 };
@@ -255,7 +233,8 @@ __global__ __launch_bounds__(kThreads) void narrow_bwd_kernel(
   constexpr int kLen = grad_len<C1, C2>();
   __shared__ __align__(16) float xs[kNarXN];
   __shared__ float red[4];
-  const Dims d = dims(T);
+  const PotesDims d = potes_dims(T);
+  const int m2row = d.m2row();
   const int tiles = bwd_tiles(d), items = N * tiles;
   const bool fast = !(T & 3) && !(reinterpret_cast<uintptr_t>(x) & 15);
   Weights<C1, C2> W;
@@ -273,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void narrow_bwd_kernel(
     float a1[C1][6];
     uint32_t sel[C1][6];
     layer1<C1>(W.w1, W.b1, xw, p, d.P1, a1, sel);
-    const Routed<C2> R = {grad_h2 + (size_t)n * C2 * d.P2, m2 + (size_t)n * C2 * d.m2row, d.P2, d.m2row};
+    const Routed<C2> R = {grad_h2 + (size_t)n * C2 * d.P2, m2 + (size_t)n * C2 * m2row, d.P2, m2row};
     // gradients of the conv2 outputs j = 2p - 4 + jj, jj < 8 (pooled outputs p-2 .. p+1)
     float gz2[C2][8];
 #pragma unroll
@@ -348,12 +327,13 @@ template <int C1, int C2>
 __global__ __launch_bounds__(kThreads) void narrow_input_grad_kernel(
     const float* __restrict__ grad_h2, const uint8_t* __restrict__ m2, const uint8_t* __restrict__ s1,
     const float* __restrict__ w1, const float* __restrict__ w2, float* __restrict__ grad_x, int T) {
-  const Dims d = dims(T);
+  const PotesDims d = potes_dims(T);
+  const int s1row = d.s1row(), m2row = d.m2row();
   const int n = blockIdx.y, u = blockIdx.x * kThreads + (int)threadIdx.x;
   if (4 * u >= T) return;
   Weights<C1, C2> W;
   load_weights<C1, C2>(W, w1, nullptr, w2, nullptr);
-  const Routed<C2> R = {grad_h2 + (size_t)n * C2 * d.P2, m2 + (size_t)n * C2 * d.m2row, d.P2, d.m2row};
+  const Routed<C2> R = {grad_h2 + (size_t)n * C2 * d.P2, m2 + (size_t)n * C2 * m2row, d.P2, m2row};
   float gz2[C2][10];
 #pragma unroll
   for (int co = 0; co < C2; ++co)
@@ -368,13 +348,13 @@ __global__ __launch_bounds__(kThreads) void narrow_input_grad_kernel(
   float dx[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int c = 0; c < C1; ++c) {
-    const uint8_t* srow = s1 + ((size_t)n * C1 + c) * d.s1row;
+    const uint8_t* srow = s1 + ((size_t)n * C1 + c) * s1row;
     float gz1[10];
 #pragma unroll
     for (int qq = 0; qq < 5; ++qq) {
       const int q = 2 * u - 2 + qq;
       uint32_t s = 0u;
-      if (q >= 0 && q < d.P1) s = (srow[(q + 1) >> 2] >> (2 * ((q + 1) & 3))) & 3u;
+      if (q >= 0 && q < d.P1) s = route2(srow, q + 1);
       float ga = 0.f;
 #pragma unroll
       for (int co = 0; co < C2; ++co)
@@ -404,6 +384,7 @@ inline int grad_len_of(int C1, int C2) { return kK * C1 + C1 + kK * C1 * C2 + C2
 }  // namespace narrow
 }  // namespace pcgmix
 
+using namespace pcgmix;
 using namespace pcgmix::narrow;
 
 extern "C" int pcgmix_potes_narrow_supported(int C1, int C2) { return supported(C1, C2) ? 1 : 0; }
@@ -415,14 +396,14 @@ extern "C" int pcgmix_potes_narrow_grad_len(int C1, int C2) {
 extern "C" int pcgmix_potes_narrow_bwd_blocks(int N, int T, int C1, int C2) {
   if (!supported(C1, C2) || N <= 0 || N > kMaxN || T < 14) return 0;
   // persistent blocks, four per CU: each ends with grad_len block-wide sums, so few and long
-  const long long work = (long long)N * bwd_tiles(dims(T));
+  const long long work = (long long)N * bwd_tiles(potes_dims(T));
   return (int)(work < 1024 ? work : 1024);
 }
 
 extern "C" long long pcgmix_potes_narrow_mask_bytes(int N, int T, int C1, int C2, int layer) {
   if (!supported(C1, C2) || N <= 0 || N > kMaxN || T < 14) return 0;
-  const Dims d = dims(T);
-  return layer == 2 ? (long long)N * C2 * d.m2row : (layer == 1 ? (long long)N * C1 * d.s1row : 0);
+  const PotesDims d = potes_dims(T);
+  return layer == 2 ? (long long)N * C2 * d.m2row() : (layer == 1 ? (long long)N * C1 * d.s1row() : 0);
 }
 
 extern "C" int pcgmix_potes_narrow_fwd_f32(const float* x, const float* w1, const float* b1,
@@ -435,7 +416,7 @@ extern "C" int pcgmix_potes_narrow_fwd_f32(const float* x, const float* w1, cons
     return hipErrorInvalidValue;
   if (!pcgmix::dropout_fill_args_ok(rnd_out, rnd_bytes, N)) return hipErrorInvalidValue;
   if (N == 0) return hipSuccess;
-  const dim3 grid((unsigned)fwd_tiles(dims(T), s1 != nullptr), (unsigned)N), block(kThreads);
+  const dim3 grid((unsigned)fwd_tiles(potes_dims(T), s1 != nullptr), (unsigned)N), block(kThreads);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   uint4* rnd = reinterpret_cast<uint4*>(rnd_out);
   const long long n16 = rnd_out ? rnd_bytes / 16 : 0ll;

@@ -14,6 +14,7 @@ features can also happen inside the head's tail kernel (``loss_and_logits(..., l
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -32,11 +33,52 @@ def _warn_once(msg: str) -> None:
         warnings.warn(msg, RuntimeWarning, stacklevel=3)
 
 
+class _StackCalls(NamedTuple):
+    """What differs between the conv stack's widths: the library calls to make, whether (C1, C2)
+    trail their arguments, the length of the flat gradient vector, whether ``defer_reduce`` is
+    honoured.  ``bwd`` / ``input_grad`` are the recomputing backward, None where there is none;
+    ``fwd`` None: ``fwd_save`` with no masks."""
+    fwd: Optional[str]
+    fwd_save: str
+    mask_bytes: str
+    bwd_blocks: str
+    bwd_mask: str
+    input_grad_mask: str
+    bwd: Optional[str]
+    input_grad: Optional[str]
+    tail: tuple
+    grad_len: int
+    defer: bool
+
+
+def _stack_calls(lib, C1: int, C2: int) -> _StackCalls:
+    if (C1, C2) == (8, 4):                             # csrc/pcgmix_potes.hip
+        return _StackCalls(
+            "pcgmix_potes_stack_fwd_f32", "pcgmix_potes_stack_fwd_save_f32", "pcgmix_potes_mask_bytes",
+            "pcgmix_potes_bwd_blocks", "pcgmix_potes_stack_bwd_mask_f32",
+            "pcgmix_potes_stack_input_grad_mask_f32", "pcgmix_potes_stack_bwd_f32",
+            "pcgmix_potes_stack_input_grad_f32", (), 212, True)          # grads[212], pcgmix_hip.h
+    return _StackCalls(                                # csrc/pcgmix_potes_narrow.hip
+        None, "pcgmix_potes_narrow_fwd_f32", "pcgmix_potes_narrow_mask_bytes",
+        "pcgmix_potes_narrow_bwd_blocks", "pcgmix_potes_narrow_bwd_mask_f32",
+        "pcgmix_potes_narrow_input_grad_mask_f32", None, None, (C1, C2),
+        lib.pcgmix_potes_narrow_grad_len(C1, C2), False)
+
+
+def _split_stack_grads(grads, C1: int, C2: int):
+    """The flat gradient vector [gw1 | gb1 | gw2 | gb2] as views."""
+    o1, o2, o3 = 5 * C1, 6 * C1, 6 * C1 + 5 * C1 * C2
+    return grads[0:o1].view(C1, 1, 5), grads[o1:o2], grads[o2:o3].view(C2, C1, 5), grads[o3:]
+
+
 class PotesStackFunction(torch.autograd.Function):
     """conv(1->8,k5,p1)+ReLU+pool2 -> conv(8->4,k5,p1)+ReLU+pool2 on (N,T) rows as ONE HIP kernel
-    forward and one (+ a 212-block reduction) backward (csrc/pcgmix_potes.hip).  Dispatches on the
-    weight shapes: layers [1,1] and [2,1] (the small models of the reference's size ladder) run
-    the same chain through their own kernels (csrc/pcgmix_potes_narrow.hip, mask-based only).
+    forward and one (+ a 212-block reduction, csrc/pcgmix_optim.hip) backward
+    (csrc/pcgmix_potes.hip).  Dispatches on the weight shapes (``_stack_calls``): layers [1,1] and
+    [2,1] (the small models of the reference's size ladder) run the same chain through their own
+    kernels (csrc/pcgmix_potes_narrow.hip: mask-based only, and the weight gradient always reduced
+    in its own call — ``defer_reduce`` is not consulted, so the optimiser's fold finds nothing
+    deferred).
 
     ``use_masks`` (default): when a gradient will be needed the forward also stores where its
     ReLUs were alive and which element won each max-pool (2 bits per second-layer output; a byte
@@ -65,8 +107,8 @@ class PotesStackFunction(torch.autograd.Function):
         lib = _lib.load()
         P2 = lib.pcgmix_potes_out_len(T)
         C1, C2 = int(w1.shape[0]), int(w2.shape[0])
-        narrow = (C1, C2) != (8, 4)                     # the small models' own kernels
-        if narrow and not lib.pcgmix_potes_narrow_supported(C1, C2):
+        calls = _stack_calls(lib, C1, C2)
+        if calls.tail and not lib.pcgmix_potes_narrow_supported(C1, C2):
             raise RuntimeError(f"PotesStackFunction: no HIP conv stack for layers [{C1},{C2}]")
         w1c, b1c, w2c, b2c = (t.detach().contiguous() for t in (w1, b1, w2, b2))
         h2 = torch.empty((N, C2, P2), dtype=torch.float32, device=x.device)
@@ -80,40 +122,26 @@ class PotesStackFunction(torch.autograd.Function):
         # rnd without any gradient (frozen conv stack, head-only fine-tuning in train mode): the
         # mask-saving forward still runs, for the dropout bytes it fills on the side
         save = PotesStackFunction.use_masks and N > 0 and (any(ctx.needs_input_grad) or rnd is not None)
-        if narrow and not PotesStackFunction.use_masks and any(ctx.needs_input_grad):
+        if calls.bwd is None and not PotesStackFunction.use_masks and any(ctx.needs_input_grad):
             raise RuntimeError("PotesStackFunction: the narrow conv stacks have no recomputing "
                                "backward (needs use_masks)")
-        if save and narrow:
-            m2 = torch.empty(lib.pcgmix_potes_narrow_mask_bytes(N, T, C1, C2, 2), dtype=torch.uint8,
-                             device=x.device)
-            if need_x:
-                s1 = torch.empty(lib.pcgmix_potes_narrow_mask_bytes(N, T, C1, C2, 1),
-                                 dtype=torch.uint8, device=x.device)
-            _lib.check(lib.pcgmix_potes_narrow_fwd_f32(
-                x.data_ptr(), w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(),
-                h2.data_ptr(), m2.data_ptr(), opt(s1), N, T, C1, C2, *rnd_args),
-                "pcgmix_potes_narrow_fwd_f32")
-        elif save:
-            m2 = torch.empty(lib.pcgmix_potes_mask_bytes(N, T, 2), dtype=torch.uint8, device=x.device)
-            if need_x:
-                s1 = torch.empty(lib.pcgmix_potes_mask_bytes(N, T, 1), dtype=torch.uint8,
-                                 device=x.device)
-            _lib.check(lib.pcgmix_potes_stack_fwd_save_f32(
-                x.data_ptr(), w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(),
-                h2.data_ptr(), m2.data_ptr(), opt(s1), N, T, *rnd_args),
-                "pcgmix_potes_stack_fwd_save_f32")
-        elif rnd is not None:
+        if not save and rnd is not None:
             raise RuntimeError("PotesStackFunction: dropout bytes are filled by the mask-saving "
                                "forward (needs use_masks)")
-        elif narrow:
-            _lib.check(lib.pcgmix_potes_narrow_fwd_f32(
-                x.data_ptr(), w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr(),
-                h2.data_ptr(), None, None, N, T, C1, C2, None, 0, None, 0, stream),
-                "pcgmix_potes_narrow_fwd_f32")
+        weights = (w1c.data_ptr(), b1c.data_ptr(), w2c.data_ptr(), b2c.data_ptr())
+        if save:
+            mask_bytes = getattr(lib, calls.mask_bytes)
+            m2 = torch.empty(mask_bytes(N, T, *calls.tail, 2), dtype=torch.uint8, device=x.device)
+            if need_x:
+                s1 = torch.empty(mask_bytes(N, T, *calls.tail, 1), dtype=torch.uint8, device=x.device)
+        if save or calls.fwd is None:
+            fill = rnd_args if save else (None, 0, None, 0, stream)
+            _lib.check(getattr(lib, calls.fwd_save)(
+                x.data_ptr(), *weights, h2.data_ptr(), opt(m2), opt(s1), N, T, *calls.tail, *fill),
+                calls.fwd_save)
         else:
-            _lib.check(lib.pcgmix_potes_stack_fwd_f32(x.data_ptr(), w1c.data_ptr(), b1c.data_ptr(),
-                                                      w2c.data_ptr(), b2c.data_ptr(), h2.data_ptr(),
-                                                      N, T, stream), "pcgmix_potes_stack_fwd_f32")
+            _lib.check(getattr(lib, calls.fwd)(x.data_ptr(), *weights, h2.data_ptr(), N, T, stream),
+                       calls.fwd)
         ctx.save_for_backward(x, w1c, b1c, w2c, b2c, m2, s1)
         return h2
 
@@ -125,74 +153,45 @@ class PotesStackFunction(torch.autograd.Function):
         g = grad_h2.contiguous()
         stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
         C1, C2 = int(w1.shape[0]), int(w2.shape[0])
-        if (C1, C2) != (8, 4):
-            return PotesStackFunction._backward_narrow(ctx, g, lib, stream)
+        calls = _stack_calls(lib, C1, C2)
         gx = gw1 = gb1 = gw2 = gb2 = None
-        if ctx.needs_input_grad[0]:                    # saliency: d score / d input
-            gx = torch.empty_like(x)
-            if s1 is not None:
-                _lib.check(lib.pcgmix_potes_stack_input_grad_mask_f32(
-                    g.data_ptr(), m2.data_ptr(), s1.data_ptr(), w1.data_ptr(), w2.data_ptr(),
-                    gx.data_ptr(), N, T, stream), "pcgmix_potes_stack_input_grad_mask_f32")
-            else:
-                _lib.check(lib.pcgmix_potes_stack_input_grad_f32(
-                    x.data_ptr(), g.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                    b2.data_ptr(), gx.data_ptr(), N, T, stream), "pcgmix_potes_stack_input_grad_f32")
-        if any(ctx.needs_input_grad[1:]):
-            G = lib.pcgmix_potes_bwd_blocks(N, T)
-            partial = torch.empty((G, 212), dtype=torch.float32, device=x.device)
-            grads = torch.empty(212, dtype=torch.float32, device=x.device)
-            if m2 is not None:
-                defer = PotesStackFunction.defer_reduce
-                if defer is not None and "partial" in defer:
-                    defer = None                       # a second stack in the same step: reduce here
-                _lib.check(lib.pcgmix_potes_stack_bwd_mask_f32(
-                    x.data_ptr(), g.data_ptr(), m2.data_ptr(), w1.data_ptr(), b1.data_ptr(),
-                    w2.data_ptr(), b2.data_ptr(), partial.data_ptr(),
-                    grads.data_ptr() if defer is None else None, N, T, stream),
-                    "pcgmix_potes_stack_bwd_mask_f32")
-                if defer is not None:
-                    defer.update(partial=partial, grads=grads, G=G)
-            else:
-                _lib.check(lib.pcgmix_potes_stack_bwd_f32(
-                    x.data_ptr(), g.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
-                    b2.data_ptr(), partial.data_ptr(), grads.data_ptr(), N, T, stream),
-                    "pcgmix_potes_stack_bwd_f32")
-            gw1, gb1 = grads[0:40].view(8, 1, 5), grads[40:48]
-            gw2, gb2 = grads[48:208].view(4, 8, 5), grads[208:212]
-        return gx, gw1, gb1, gw2, gb2, None, None
-
-    @staticmethod
-    def _backward_narrow(ctx, g, lib, stream):
-        """The small models' backward (csrc/pcgmix_potes_narrow.hip): always from the saved routing,
-        and the weight gradient always reduced in its own call — ``defer_reduce`` is not consulted,
-        so the optimiser's fold finds nothing deferred."""
-        x, w1, b1, w2, b2, m2, s1 = ctx.saved_tensors
-        N, T = x.shape
-        C1, C2 = int(w1.shape[0]), int(w2.shape[0])
-        gx = gw1 = gb1 = gw2 = gb2 = None
-        if N == 0:
+        if N == 0 and calls.bwd is None:
+            # an empty batch saved no routing; where a recomputing backward exists it takes it
             if ctx.needs_input_grad[0]:
                 gx = torch.zeros_like(x)
             if any(ctx.needs_input_grad[1:]):
                 gw1, gb1, gw2, gb2 = (torch.zeros_like(t) for t in (w1, b1, w2, b2))
             return gx, gw1, gb1, gw2, gb2, None, None
-        if ctx.needs_input_grad[0]:
+        weights = (w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr())
+        if ctx.needs_input_grad[0]:                    # saliency: d score / d input
             gx = torch.empty_like(x)
-            _lib.check(lib.pcgmix_potes_narrow_input_grad_mask_f32(
-                g.data_ptr(), m2.data_ptr(), s1.data_ptr(), w1.data_ptr(), w2.data_ptr(),
-                gx.data_ptr(), N, T, C1, C2, stream), "pcgmix_potes_narrow_input_grad_mask_f32")
+            if s1 is not None:
+                _lib.check(getattr(lib, calls.input_grad_mask)(
+                    g.data_ptr(), m2.data_ptr(), s1.data_ptr(), w1.data_ptr(), w2.data_ptr(),
+                    gx.data_ptr(), N, T, *calls.tail, stream), calls.input_grad_mask)
+            else:
+                _lib.check(getattr(lib, calls.input_grad)(
+                    x.data_ptr(), g.data_ptr(), *weights, gx.data_ptr(), N, T, stream),
+                    calls.input_grad)
         if any(ctx.needs_input_grad[1:]):
-            G, L = lib.pcgmix_potes_narrow_bwd_blocks(N, T, C1, C2), lib.pcgmix_potes_narrow_grad_len(C1, C2)
+            G, L = getattr(lib, calls.bwd_blocks)(N, T, *calls.tail), calls.grad_len
             partial = torch.empty((G, L), dtype=torch.float32, device=x.device)
             grads = torch.empty(L, dtype=torch.float32, device=x.device)
-            _lib.check(lib.pcgmix_potes_narrow_bwd_mask_f32(
-                x.data_ptr(), g.data_ptr(), m2.data_ptr(), w1.data_ptr(), b1.data_ptr(),
-                w2.data_ptr(), b2.data_ptr(), partial.data_ptr(), grads.data_ptr(), N, T, C1, C2,
-                stream), "pcgmix_potes_narrow_bwd_mask_f32")
-            o1, o2, o3 = 5 * C1, 6 * C1, 6 * C1 + 5 * C1 * C2
-            gw1, gb1 = grads[0:o1].view(C1, 1, 5), grads[o1:o2]
-            gw2, gb2 = grads[o2:o3].view(C2, C1, 5), grads[o3:o3 + C2]
+            if m2 is not None:
+                defer = PotesStackFunction.defer_reduce if calls.defer else None
+                if defer is not None and "partial" in defer:
+                    defer = None                       # a second stack in the same step: reduce here
+                _lib.check(getattr(lib, calls.bwd_mask)(
+                    x.data_ptr(), g.data_ptr(), m2.data_ptr(), *weights, partial.data_ptr(),
+                    grads.data_ptr() if defer is None else None, N, T, *calls.tail, stream),
+                    calls.bwd_mask)
+                if defer is not None:
+                    defer.update(partial=partial, grads=grads, G=G)
+            else:
+                _lib.check(getattr(lib, calls.bwd)(
+                    x.data_ptr(), g.data_ptr(), *weights, partial.data_ptr(), grads.data_ptr(),
+                    N, T, stream), calls.bwd)
+            gw1, gb1, gw2, gb2 = _split_stack_grads(grads, C1, C2)
         return gx, gw1, gb1, gw2, gb2, None, None
 
 

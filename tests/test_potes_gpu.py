@@ -150,7 +150,7 @@ def test_saved_masks_equal_recomputed_routing(device):
 
 
 def _counter_hash(n_words, key):
-    """numpy restatement of counter_hash (csrc/pcgmix_potes.hip): murmur3's 32-bit finaliser, keyed."""
+    """numpy restatement of counter_hash (csrc/pcgmix_kernels.h): murmur3's 32-bit finaliser, keyed."""
     k0, k1 = np.uint32(key & 0xFFFFFFFF), np.uint32(key >> 32)
     with np.errstate(over="ignore"):
         h = np.arange(n_words, dtype=np.uint32) * np.uint32(0x9E3779B1) + k0

@@ -598,3 +598,63 @@ def test_clip_adam_interleaved_captured_and_eager_steps(device):
         assert torch.equal(x, y)
         assert torch.equal(oa.state[x]["exp_avg_sq"], ob.state[y]["exp_avg_sq"])
     assert all(float(v["step"]) == 8.0 for v in oa.state_dict()["state"].values())
+
+
+def test_adam_entry_points_share_one_update(device):
+    """One step through each of the library's three Adam paths leaves p, exp_avg and exp_avg_sq
+    bit-equal: pcgmix_adam_clip_f32 per tensor, pcgmix_adam_clip_multi_f32 (table blocks), and
+    pcgmix_adam_clip_multi_reduce_dev_f32 with G = 1 and partial = the gradient buffer (the folded
+    reduction then adds only zeros, so it is exact).  Tensors: the conv stack's four, their
+    gradients aliased into one 212-float buffer, plus one of 1025 elements — one past a table
+    block's 1024, so two table blocks and a partial one."""
+    import ctypes
+    from pcgmix_amd import _lib
+    lib = _lib.load()
+    torch.manual_seed(0)
+    shapes = [(8, 1, 5), (8,), (4, 8, 5), (4,), (1025,)]
+    offs = [0, 40, 48, 208]
+    p0 = [torch.randn(s, device=device) for s in shapes]
+    m0 = [torch.randn(s, device=device) * 0.01 for s in shapes]
+    v0 = [torch.rand(s, device=device) * 1e-3 for s in shapes]
+    gbuf = torch.randn(212, device=device) * 0.3          # clip = 0.1 bites on some elements
+    gbig = torch.randn(1025, device=device) * 0.3
+    hp = dict(clip=0.1, lr=0.01, b1=0.9, b2=0.999, eps=1e-8, wd=1e-4)
+    step = 3
+    floats = [ctypes.c_float(hp[k]) for k in ("clip", "lr", "b1", "b2", "eps", "wd")]
+    stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+    def run(path):
+        p, m, v = ([t.clone() for t in ts] for ts in (p0, m0, v0))
+        # the reduce path writes the column sums into `flat`, which the four gradients alias
+        flat = torch.zeros(212, device=device) if path == "reduce" else gbuf.clone()
+        g = [flat[o:o + t.numel()] for o, t in zip(offs, p)] + [gbig.clone()]
+        arr = ctypes.c_void_p * len(p)
+        tabs = [arr(*[t.data_ptr() for t in ts]) for ts in (p, g, m, v)]
+        n = (ctypes.c_longlong * len(p))(*[t.numel() for t in p])
+        if path == "single":
+            for pi, gi, mi, vi in zip(p, g, m, v):
+                _lib.check(lib.pcgmix_adam_clip_f32(pi.data_ptr(), gi.data_ptr(), mi.data_ptr(),
+                                                    vi.data_ptr(), pi.numel(), *floats, step, stream),
+                           "pcgmix_adam_clip_f32")
+        elif path == "multi":
+            _lib.check(lib.pcgmix_adam_clip_multi_f32(len(p), *tabs, n, *floats, step, stream),
+                       "pcgmix_adam_clip_multi_f32")
+        else:
+            host = np.zeros(8, dtype=np.float32)
+            _lib.check(lib.pcgmix_adam_hyper(*floats, step, host.ctypes.data), "pcgmix_adam_hyper")
+            hyper = torch.from_numpy(host).to(device)
+            partial = gbuf.clone()                         # (G = 1, 212)
+            _lib.check(lib.pcgmix_adam_clip_multi_reduce_dev_f32(
+                len(p), *tabs, n, hyper.data_ptr(), partial.data_ptr(), flat.data_ptr(), 1, stream),
+                "pcgmix_adam_clip_multi_reduce_dev_f32")
+            assert torch.equal(flat, gbuf)
+        torch.cuda.synchronize(device)
+        return p, m, v
+
+    ref = run("single")
+    for path in ("multi", "reduce"):
+        got = run(path)
+        for name, a, b in zip(("p", "exp_avg", "exp_avg_sq"), ref, got):
+            for i, (x, y) in enumerate(zip(a, b)):
+                assert torch.equal(x, y), (path, name, i, float((x - y).abs().max()))
+    assert not any(torch.equal(x, y) for x, y in zip(ref[0], p0))   # the step did something
