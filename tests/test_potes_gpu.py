@@ -231,8 +231,8 @@ def test_forward_staging_paths_agree(T, device):
     out = []
     for x in (x_al, x_un):
         h2 = torch.empty(N, 4, P2, device=device)
-        m2 = torch.zeros(lib.pcgmix_potes_mask_bytes(N, T, 2), dtype=torch.uint8, device=device)
-        s1 = torch.zeros(lib.pcgmix_potes_mask_bytes(N, T, 1), dtype=torch.uint8, device=device)
+        m2 = torch.full((lib.pcgmix_potes_mask_bytes(N, T, 2),), 0xFF, dtype=torch.uint8, device=device)
+        s1 = torch.full((lib.pcgmix_potes_mask_bytes(N, T, 1),), 0xFF, dtype=torch.uint8, device=device)
         _lib.check(lib.pcgmix_potes_stack_fwd_save_f32(
             x.data_ptr(), c1.weight.data_ptr(), c1.bias.data_ptr(), c2.weight.data_ptr(),
             c2.bias.data_ptr(), h2.data_ptr(), m2.data_ptr(), s1.data_ptr(), N, T, None, 0, None, 0, st), "fwd")
