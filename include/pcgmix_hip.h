@@ -495,6 +495,61 @@ int pcgmix_potes_narrow_input_grad_mask_f32(const float* grad_h2, const uint8_t*
                                             pcgmix_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Big Potes conv stacks (the wide end of the reference's model-size ladder).         [device]
+ *
+ * The same chain on the N = 4*B band rows x (N,T) for the two big models of models.py:339-343
+ * (CNN_potes_big64and32_TS, layers [64,32]; CNN_potes_big128and64_TS, layers [128,64]) over
+ * models.py:359-381:
+ *     Conv1d(1->C1,k5,pad1) + ReLU + MaxPool1d(2) -> Conv1d(C1->C2,k5,pad1) + ReLU + MaxPool1d(2)
+ * (C1,C2) in {(64,32), (128,64)}; torch weight layouts as above; float32, T >= 14,
+ * P2 = pcgmix_potes_out_len(T).  csrc/pcgmix_potes_big.hip: the first layer on the VALU into LDS,
+ * the second layer and both transposed products as implicit GEMMs on v_mfma_f32_32x32x2_f32 — exact
+ * float32, every second-layer output the chain "b2, then (input channel, tap) in order".
+ *
+ *   pcgmix_potes_big_supported(C1,C2)      1 for (64,32) and (128,64), else 0
+ *   pcgmix_potes_big_grad_len(C1,C2)       5*C1 + C1 + 5*C1*C2 + C2 (10656, 41792); 0 if unsupported
+ *   pcgmix_potes_big_bwd_blocks            G = partial rows the weight gradient needs
+ *   pcgmix_potes_big_mask_bytes            bytes of m2 (layer = 2) / s1 (layer = 1)
+ *                                          (both helpers: 0 for whatever the launching entry points
+ *                                          refuse, as in the narrow section)
+ *   pcgmix_potes_big_fwd_f32               ONE launch: h2 (N,C2,P2); m2 != NULL: + m2 uint8
+ *                                          (N, C2, ceil(P2/4)); s1 != NULL: + s1 uint8
+ *                                          (N, C1, P1/4 + 1) (only the input gradient reads it); the
+ *                                          encodings defined above with 8 -> C1 and 4 -> C2.
+ *                                          rnd_out, rnd_bytes, key_dev, key: exactly as in
+ *                                          pcgmix_potes_narrow_fwd_f32 — the same hash, the same
+ *                                          checks, the same bytes for a key and a length.
+ *   pcgmix_potes_big_bwd_mask_f32          weight gradients: recomputes layer 1 from x, routes
+ *                                          through m2; two persistent launches write `partial`
+ *                                          (G, grad_len) — gw2 | gb2, then gw1 | gb1 through the
+ *                                          transposed second layer — and a third reduces it in a
+ *                                          fixed order (no float atomics) into grads =
+ *                                          [gw1 | gb1 | gw2 | gb2].  grads == NULL is NOT supported:
+ *                                          hipErrorInvalidValue.
+ *   pcgmix_potes_big_input_grad_mask_f32   dL/dx (N,T) from grad_h2, m2, s1 and the weights alone;
+ *                                          every element of grad_x is written.
+ * The refusal contract of the narrow section holds word for word: hipErrorInvalidValue, nothing
+ * launched and no output touched, for an unsupported (C1,C2), T < 14, N < 0 (or > 65535), a NULL
+ * required pointer or a misaligned rnd_out; N == 0 succeeds without a launch.  All are legal on a
+ * capturing stream.  PCGMIX_POTES_BIG_BWD_BLOCKS in the environment caps G (tuning runs, tests).
+ */
+int pcgmix_potes_big_supported(int C1, int C2);
+int pcgmix_potes_big_grad_len(int C1, int C2);
+int pcgmix_potes_big_bwd_blocks(int N, int T, int C1, int C2);
+long long pcgmix_potes_big_mask_bytes(int N, int T, int C1, int C2, int layer);
+int pcgmix_potes_big_fwd_f32(const float* x, const float* w1, const float* b1, const float* w2,
+                             const float* b2, float* h2, uint8_t* m2, uint8_t* s1, int N, int T,
+                             int C1, int C2, uint8_t* rnd_out, long long rnd_bytes,
+                             const uint32_t* key_dev, uint64_t key, pcgmix_stream_t stream);
+int pcgmix_potes_big_bwd_mask_f32(const float* x, const float* grad_h2, const uint8_t* m2,
+                                  const float* w1, const float* b1, const float* w2, const float* b2,
+                                  float* partial, float* grads, int N, int T, int C1, int C2,
+                                  pcgmix_stream_t stream);
+int pcgmix_potes_big_input_grad_mask_f32(const float* grad_h2, const uint8_t* m2, const uint8_t* s1,
+                                         const float* w1, const float* w2, float* grad_x, int N,
+                                         int T, int C1, int C2, pcgmix_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Skinny linear layer forward (the Potes head's `dimreduc`, models.py:376, 430).    [device]
  *
  *   z (B,O) = h (B,K) . W (O,K)^T + bias (O)      O in {8, 16, 20}, K % 4 == 0

@@ -83,6 +83,14 @@ SIGNATURES = {
                                                                      ctypes.c_uint64, _ptr]),
     "pcgmix_potes_narrow_bwd_mask_f32": (_c_int, [_ptr] * 9 + [_c_int] * 4 + [_ptr]),
     "pcgmix_potes_narrow_input_grad_mask_f32": (_c_int, [_ptr] * 6 + [_c_int] * 4 + [_ptr]),
+    "pcgmix_potes_big_supported": (_c_int, [_c_int, _c_int]),
+    "pcgmix_potes_big_grad_len": (_c_int, [_c_int, _c_int]),
+    "pcgmix_potes_big_bwd_blocks": (_c_int, [_c_int] * 4),
+    "pcgmix_potes_big_mask_bytes": (ctypes.c_longlong, [_c_int] * 5),
+    "pcgmix_potes_big_fwd_f32": (_c_int, [_ptr] * 8 + [_c_int] * 4 + [_ptr, ctypes.c_longlong, _ptr,
+                                                                  ctypes.c_uint64, _ptr]),
+    "pcgmix_potes_big_bwd_mask_f32": (_c_int, [_ptr] * 9 + [_c_int] * 4 + [_ptr]),
+    "pcgmix_potes_big_input_grad_mask_f32": (_c_int, [_ptr] * 6 + [_c_int] * 4 + [_ptr]),
     "pcgmix_skinny_linear_splits": (_c_int, [_c_int, _c_int]),
     "pcgmix_skinny_linear_fwd_f32": (_c_int, [_ptr] * 5 + [_c_int, _c_int, _c_int, _ptr]),
     "pcgmix_adam_clip_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, ctypes.c_longlong, _c_float, _c_float,

@@ -58,6 +58,12 @@ def _stack_calls(lib, C1: int, C2: int) -> _StackCalls:
             "pcgmix_potes_bwd_blocks", "pcgmix_potes_stack_bwd_mask_f32",
             "pcgmix_potes_stack_input_grad_mask_f32", "pcgmix_potes_stack_bwd_f32",
             "pcgmix_potes_stack_input_grad_f32", (), 212, True)          # grads[212], pcgmix_hip.h
+    if lib.pcgmix_potes_big_supported(C1, C2):         # csrc/pcgmix_potes_big.hip
+        return _StackCalls(
+            None, "pcgmix_potes_big_fwd_f32", "pcgmix_potes_big_mask_bytes",
+            "pcgmix_potes_big_bwd_blocks", "pcgmix_potes_big_bwd_mask_f32",
+            "pcgmix_potes_big_input_grad_mask_f32", None, None, (C1, C2),
+            lib.pcgmix_potes_big_grad_len(C1, C2), False)
     return _StackCalls(                                # csrc/pcgmix_potes_narrow.hip
         None, "pcgmix_potes_narrow_fwd_f32", "pcgmix_potes_narrow_mask_bytes",
         "pcgmix_potes_narrow_bwd_blocks", "pcgmix_potes_narrow_bwd_mask_f32",
@@ -78,7 +84,8 @@ class PotesStackFunction(torch.autograd.Function):
     [2,1] (the small models of the reference's size ladder) run the same chain through their own
     kernels (csrc/pcgmix_potes_narrow.hip: mask-based only, and the weight gradient always reduced
     in its own call — ``defer_reduce`` is not consulted, so the optimiser's fold finds nothing
-    deferred).
+    deferred), and so do layers [64,32] and [128,64] (the big models; csrc/pcgmix_potes_big.hip:
+    the second layer on the f32 matrix instruction, mask-based only, never deferred).
 
     ``use_masks`` (default): when a gradient will be needed the forward also stores where its
     ReLUs were alive and which element won each max-pool (2 bits per second-layer output; a byte
@@ -108,7 +115,8 @@ class PotesStackFunction(torch.autograd.Function):
         P2 = lib.pcgmix_potes_out_len(T)
         C1, C2 = int(w1.shape[0]), int(w2.shape[0])
         calls = _stack_calls(lib, C1, C2)
-        if calls.tail and not lib.pcgmix_potes_narrow_supported(C1, C2):
+        if calls.tail and not (lib.pcgmix_potes_narrow_supported(C1, C2)
+                               or lib.pcgmix_potes_big_supported(C1, C2)):
             raise RuntimeError(f"PotesStackFunction: no HIP conv stack for layers [{C1},{C2}]")
         w1c, b1c, w2c, b2c = (t.detach().contiguous() for t in (w1, b1, w2, b2))
         h2 = torch.empty((N, C2, P2), dtype=torch.float32, device=x.device)
@@ -123,7 +131,7 @@ class PotesStackFunction(torch.autograd.Function):
         # mask-saving forward still runs, for the dropout bytes it fills on the side
         save = PotesStackFunction.use_masks and N > 0 and (any(ctx.needs_input_grad) or rnd is not None)
         if calls.bwd is None and not PotesStackFunction.use_masks and any(ctx.needs_input_grad):
-            raise RuntimeError("PotesStackFunction: the narrow conv stacks have no recomputing "
+            raise RuntimeError("PotesStackFunction: the narrow and big conv stacks have no recomputing "
                                "backward (needs use_masks)")
         if not save and rnd is not None:
             raise RuntimeError("PotesStackFunction: dropout bytes are filled by the mask-saving "
@@ -514,9 +522,10 @@ class CNN_potes(nn.Module):
 
     def _fused(self, x: torch.Tensor) -> bool:
         """The hand-written HIP stacks apply to float32 input on a HIP device for the reference
-        configuration (layers [8,4]) and for the narrow widths the library reports as supported
-        ([1,1], [2,1]: ``pcgmix_potes_narrow_supported``; those only with
-        ``PotesStackFunction.use_masks``, they have no recomputing backward).  Host tensors (CPU-side
+        configuration (layers [8,4]) and for the narrow and big widths the library reports as
+        supported ([1,1], [2,1]: ``pcgmix_potes_narrow_supported``; [64,32], [128,64]:
+        ``pcgmix_potes_big_supported``; those only with ``PotesStackFunction.use_masks``, they have
+        no recomputing backward).  Host tensors (CPU-side
         tests, gloo rehearsals) and an explicit ``self.fused = False`` take torch's ops; a DEVICE
         tensor that cannot take the HIP kernels does so too, but says so — a GPU run must not lose
         its kernels without a word."""
@@ -526,13 +535,14 @@ class CNN_potes(nn.Module):
         widths = (c1.out_channels, c2.out_channels)
         ok = widths == (8, 4) or bool(
             PotesStackFunction.use_masks
-            and _lib.load().pcgmix_potes_narrow_supported(widths[0], widths[1]))
+            and (_lib.load().pcgmix_potes_narrow_supported(*widths)
+                 or _lib.load().pcgmix_potes_big_supported(*widths)))
         ok = ok and x.dtype == torch.float32 and x.shape[-1] >= 14
         if not ok:
             _warn_once(f"CNN_potes: input {tuple(x.shape)} {x.dtype} / layers "
                        f"[{c1.out_channels},{c2.out_channels}] cannot use the fused HIP conv stack "
-                       "(needs float32, T >= 14 and layers [8,4], or [1,1] / [2,1] with "
-                       "PotesStackFunction.use_masks): running torch/MIOpen ops instead")
+                       "(needs float32, T >= 14 and layers [8,4], or [1,1] / [2,1] / [64,32] / "
+                       "[128,64] with PotesStackFunction.use_masks): running torch/MIOpen ops instead")
         return ok
 
     def _fused_head(self, x: torch.Tensor) -> bool:
@@ -670,8 +680,8 @@ def CNN_potes_twopercent_TS(num_channels: int = 4, num_classes: int = 2,
 
 def CNN_potes_big64and32_TS(num_channels: int = 4, num_classes: int = 2, dataset: str = "PhysioNet",
                             dropout: float = 0.25, sig_len: int | None = None) -> CNN_potes:
-    """Reference factory (models.py:342-343): layers [64,32], linear = 79744 (T = 2500).  No
-    hand-written stack at this width: the conv branch runs through torch/MIOpen (``_fused``)."""
+    """Reference factory (models.py:342-343): layers [64,32], linear = 79744 (T = 2500).  The
+    conv branch runs on the f32-matrix-instruction HIP stack (csrc/pcgmix_potes_big.hip, ``_fused``)."""
     return CNN_potes(c_in=num_channels, c_out=num_classes, layers=[64, 32],
                      linear=_potes_linear(sig_len, 32, 79744), dropout=dropout)
 
@@ -679,7 +689,7 @@ def CNN_potes_big64and32_TS(num_channels: int = 4, num_classes: int = 2, dataset
 def CNN_potes_big128and64_TS(num_channels: int = 4, num_classes: int = 2, dataset: str = "PhysioNet",
                              dropout: float = 0.25, sig_len: int | None = None) -> CNN_potes:
     """Reference factory (models.py:339-340): layers [128,64], linear = 159488 (T = 2500).  As
-    ``CNN_potes_big64and32_TS``: torch/MIOpen conv branch."""
+    ``CNN_potes_big64and32_TS``: the HIP conv stack of csrc/pcgmix_potes_big.hip."""
     return CNN_potes(c_in=num_channels, c_out=num_classes, layers=[128, 64],
                      linear=_potes_linear(sig_len, 64, 159488), dropout=dropout)
 

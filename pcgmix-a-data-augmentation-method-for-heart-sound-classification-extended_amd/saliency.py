@@ -105,8 +105,8 @@ def _potes_direct(model: torch.nn.Module, data: torch.Tensor):
     from . import models
     m = model.module if isinstance(model, (torch.nn.DataParallel,
                                            torch.nn.parallel.DistributedDataParallel)) else model
-    # the chain's conv kernels are the [8,4] ones: a narrow model ([1,1], [2,1]) is fused too, but
-    # goes through autograd and its own input-gradient kernel
+    # the chain's conv kernels are the [8,4] ones: a narrow or big model ([1,1], [2,1]; [64,32],
+    # [128,64]) is fused too, but goes through autograd and its own input-gradient kernel
     if (isinstance(m, models.CNN_potes) and not m.training and data.dim() == 3 and data.shape[1] == 4
             and data.shape[0] > 0 and data.is_contiguous() and models.PotesStackFunction.use_masks
             and (m.cnn1[0][0].out_channels, m.cnn1[1][0].out_channels) == (8, 4)

@@ -301,11 +301,12 @@ POTES_LADDER = {
 def build_model(args) -> nn.Module:
     """The models of the hot path (train_model.py:296, 337-370: 'Potes', 'resnet9' and the two
     model-size ladders around them), head sized for ``args.sig_len`` (the reference hard-codes
-    T = 2500).  'Potes', 'Potes(noDropout)', 'Potes0.1' and 'Potes0.02' run their conv branch on the
-    hand-written HIP stacks; the two 'PotesBig*' models run through torch/MIOpen, with the warning
-    that path already gives.  Every ResNet9 width of the ladder (2 ... 1024) runs its BatchNorm +
-    ReLU + pool through the HIP kernels, in training and in eval mode: they take C = 2 and every
-    multiple of 4 up to 1024 (``pcgmix_bnrp_supported``), so no ResNet9 name warns."""
+    T = 2500).  Every Potes name runs its conv branch on a hand-written HIP stack: 'Potes' and
+    'Potes(noDropout)' on the [8,4] kernels, 'Potes0.1' and 'Potes0.02' on the narrow ones, the two
+    'PotesBig*' models on the f32-matrix-instruction ones (csrc/pcgmix_potes_big.hip).  Every
+    ResNet9 width of the ladder (2 ... 1024) runs its BatchNorm + ReLU + pool through the HIP
+    kernels, in training and in eval mode: they take C = 2 and every multiple of 4 up to 1024
+    (``pcgmix_bnrp_supported``), so no ResNet9 name warns."""
     sig_len = getattr(args, "sig_len", 2500)
     if args.dataset in SPECTROGRAM_DATASETS:
         if args.model != "resnet9":
