@@ -31,7 +31,7 @@ extern "C" {
  * language binding does not need the HIP headers). */
 typedef struct ihipStream_t* pcgmix_stream_t;
 
-#define PCGMIX_ABI_VERSION 24
+#define PCGMIX_ABI_VERSION 25
 
 /* ABI version of the loaded library (== PCGMIX_ABI_VERSION it was built with). */
 int pcgmix_abi_version(void);
@@ -873,7 +873,8 @@ int pcgmix_augment_plain_f32(pcgmix_ctx* ctx, const float* x, float* y,
  * two-launch path (PCGMIX_NO_ARMED=1), bit for bit.  The waiting blocks give up `timeout_ticks`
  * (100 MHz; default 1 s) after the kernel started; the call notices (records written later than
  * 0.4 s after the launch: stream synchronisation, abort word) and launches the splice again.
- * stats: out3 = steps armed | of them checked after a stream synchronisation | of them relaunched.
+ * stats: out3 = steps armed | of them checked after a stream synchronisation | kernels given up
+ * (relaunched unarmed, or released by pcgmix_augment_plain_abort / the next begin).
  * debug (tests): the relays' timeout and a host stall in front of the record write; 0, 0 = defaults. */
 int pcgmix_ctx_armed_stats(pcgmix_ctx* ctx, long long* out3);
 /* The armed plain step (no warp) in two calls, for a binding with host work of its own between the
@@ -884,8 +885,14 @@ int pcgmix_ctx_armed_stats(pcgmix_ctx* ctx, long long* out3);
  * hipError_t on failure.  A pending pcgmix_ctx_set_payload travels with the launch.
  * finish: boundaries (validated: -1 / -2 as pcgmix_augment_plain_f32, the waiting kernel is released),
  * label pick-up, partner draw into mix_out (HOST int64 (B)), records + lambda.  hipErrorNotReady without
- * a begin.  A begin that is never finished is released by the next begin (or by the blocks' timeout). */
+ * a begin.  A begin that is never finished is released by pcgmix_augment_plain_abort, by the next begin
+ * (or by the blocks' timeout).
+ * abort: for the caller whose own work between begin and finish failed (numpy refused the step number, an
+ * interrupt): if a begin is open, the waiting kernel is told to give up at once (its output is then
+ * undefined), the step is closed and counted in stats' third number; 0.  Nothing open: 0, nothing done.
+ * hipErrorInvalidValue for a NULL context. */
 #define PCGMIX_NOT_ARMED (-3)
+int pcgmix_augment_plain_abort(pcgmix_ctx* ctx);
 int pcgmix_augment_plain_begin(pcgmix_ctx* ctx, const float* x, float* y, const int64_t* target_ohe_dev,
                                int num_classes, int B, int C, int T, pcgmix_stream_t stream);
 int pcgmix_augment_plain_finish(pcgmix_ctx* ctx, const int64_t* frames, uint64_t step, float lam,

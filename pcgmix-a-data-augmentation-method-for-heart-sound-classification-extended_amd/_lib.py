@@ -12,7 +12,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpcgmix_hip.so")
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _c_int = ctypes.c_int
 _c_float = ctypes.c_float
@@ -147,6 +147,7 @@ SIGNATURES = {
     "pcgmix_augment_plain_begin": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr]),
     "pcgmix_augment_plain_begin_edges": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),
     "pcgmix_augment_plain_finish": (_c_int, [_ptr, _ptr, ctypes.c_uint64, _c_float, _ptr]),
+    "pcgmix_augment_plain_abort": (_c_int, [_ptr]),
     "pcgmix_ctx_armed_debug": (_c_int, [_ptr, ctypes.c_uint64, _c_int]),
     "pcgmix_ctx_labels_begin": (_c_int, [_ptr, _ptr, _c_int, _c_int, _ptr, _ptr]),
     "pcgmix_ctx_labels_wait": (_c_int, [_ptr, _ptr, _c_int, _ptr]),
@@ -239,6 +240,45 @@ def load() -> ctypes.CDLL:
             raise PcgmixLibraryError(f"ABI version mismatch: library {got}, binding {ABI_VERSION}")
         _lib = lib
     return _lib
+
+
+STEP_MODULE_PATH = os.path.join(_HERE, "_pcgmix_step.so")
+NO_NATIVE_STEP = bool(os.environ.get("PCGMIX_NO_NATIVE_STEP"))    # A/B runs of one tree: the Python path
+_step_module = None
+_step_tried = False
+
+
+def native_step_module(objects: dict):
+    """The compiled entry point of the armed plain step (csrc/pcgmix_pystep.cpp), bound to the loaded
+    library: ``objects`` (the Python callables it works with) is completed with the addresses of the entry
+    points it calls, taken from the CDLL ``load()`` holds — one library instance, one step context for
+    both callers.  None when PCGMIX_NO_NATIVE_STEP is set or the module was never built (``make`` builds
+    it with the library); a module that is there and does not load is an error."""
+    global _step_module, _step_tried
+    _step_tried = True
+    if NO_NATIVE_STEP or not os.path.exists(STEP_MODULE_PATH):
+        return None
+    lib = load()
+    lib = getattr(lib, "_lib", lib)                       # (a _Recorder while a step is taped)
+    from . import _pcgmix_step as mod
+    if mod.ABI_VERSION != ABI_VERSION:
+        raise PcgmixLibraryError(f"ABI version mismatch: {STEP_MODULE_PATH} {mod.ABI_VERSION}, "
+                                 f"binding {ABI_VERSION}")
+    for name in ("pcgmix_ctx_gate", "pcgmix_augment_plain_begin_edges", "pcgmix_augment_plain_finish",
+                 "pcgmix_augment_plain_abort"):
+        objects[name] = ctypes.cast(getattr(lib, name), ctypes.c_void_p).value
+    mod.bind(objects)
+    _step_module = mod
+    return mod
+
+
+def native_step_loaded() -> bool:
+    """Whether augment()'s armed plain step runs through the compiled entry point in this process (it is
+    bound at the first step; asking earlier binds it now)."""
+    if not _step_tried:
+        from . import augmentations
+        augmentations._bind_native_step()
+    return _step_module is not None
 
 
 def check(err: int, what: str) -> None:

@@ -550,9 +550,14 @@ def splice_plain(recipe, data: torch.Tensor, labels, frames, step: int,
         err = lib.pcgmix_augment_plain_begin_edges(ctx, data.data_ptr(), out.data_ptr(), ohe_ptr, n_cls, B, C, T,
                                                    fr_ptr, stream)
         if err == 0:
-            lam, _ = hostprep.draw_lambda_knots(step, alpha, sigma, 0)
-            mix_buf, mix = _index_out(B)
-            err = lib.pcgmix_augment_plain_finish(ctx, fr_ptr, step, _c_float(lam), mix_buf)
+            try:                                  # no begin without an end: a kernel is waiting
+                lam, _ = hostprep.draw_lambda_knots(step, alpha, sigma, 0)
+                mix_buf, mix = _index_out(B)
+                c_lam = _c_float(lam)
+            except BaseException:
+                lib.pcgmix_augment_plain_abort(ctx)
+                raise
+            err = lib.pcgmix_augment_plain_finish(ctx, fr_ptr, step, c_lam, mix_buf)
             if err:
                 _check_splice(err, "pcgmix_augment_plain_finish")
             return out, mix
@@ -626,6 +631,26 @@ def _salopt_step(srec, g, data: torch.Tensor, ohe: Optional[torch.Tensor], label
         _c_float(lam), mode, knots_ptr, n_knots, mix.ctypes.data, B, C, T, stream),
         "pcgmix_ctx_salopt_finish")
     return out, mix
+
+
+def _bind_native_step(*call):
+    """First use of ``_native_step``: bind the compiled entry point (``_lib.native_step_module``), put its
+    ``step`` — or None, when it is switched off or unbuilt — in this function's place, and make the call
+    (without arguments: bind only)."""
+    global _native_step
+    mod = _lib.native_step_module({
+        "empty_like": torch.empty_like, "raw_stream": _get_raw_stream, "Tensor": torch.Tensor,
+        "float32": torch.float32, "int64": torch.int64, "np_random": np.random, "np_empty": np.empty,
+        "np_int64": np.dtype(np.int64), "ndarray": np.ndarray, "lib": _lib, "contexts": _CTX,
+        "step_context": step_context, "check_splice": _check_splice, "check": _lib.check})
+    _native_step = mod.step if mod is not None else None
+    return _native_step(*call) if call and _native_step is not None else None
+
+
+# The armed plain step from one compiled call: ``_native_step(recipe, data, target_ohe, frames, step,
+# host_labels)`` returns augment()'s tuple, or None when it declines (then nothing was launched and the
+# Python path below runs as ever).  None here switches it off (tests; PCGMIX_NO_NATIVE_STEP=1 at import).
+_native_step = _bind_native_step
 
 
 def gate_passes(recipe, method: str, step: int, index: int) -> bool:
@@ -871,6 +896,11 @@ def augment(args, data, target_ohe, frames, wav, step_counter, model, device, RE
     route = hostprep.route(args.method, False)         # cached: the one lookup of the hot path
     family = route.family
     if family == "splice":
+        native = _native_step
+        if native is not None and _lib.TAPE is None:      # (a taped step records its launches: Python path)
+            done = native(route.plain, data, target_ohe, frames, step, host_labels)
+            if done is not None:
+                return done
         _check_data(data, 3)
         plain = route.plain
         if plain.__class__ is tuple and data.shape[0] > 0:       # the common case: one library call

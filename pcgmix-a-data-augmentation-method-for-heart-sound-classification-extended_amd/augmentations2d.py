@@ -45,6 +45,7 @@ import numpy as np
 import torch
 
 from . import _lib, hostprep
+from . import augmentations as _aug1d           # (its _native_step is read per call: tests switch it)
 from .augmentations import (LatentBlend, _as_numpy_frames, _batch_dense, _blend_planes, _check_data,  # noqa: F401
                             _label_source, _raw_stream, apply_plan, blend_targets, gate_passes,
                             latent_blend, splice_plain, upload_array)
@@ -140,10 +141,15 @@ def _augment_splice2d(args, route, data, target_ohe, frames, wav, step: int, dev
     B, Cc, F, W = data.shape
     plain = route.plain
     if plain.__class__ is tuple and B > 0:             # durratiomixup: one library call
+        rows = data.view(B, Cc * F, W)
+        native = _aug1d._native_step
+        if native is not None and _lib.TAPE is None:   # the compiled armed step, as augmentations.augment
+            done = native(plain, rows, target_ohe, frames, step, host_labels)
+            if done is not None:                       # (a rejected gate hands `rows` itself back)
+                return (data if done[0] is rows else done[0].view(B, Cc, F, W)), target_ohe, done[2], None
         if not gate_passes(plain, args.method, step, data.device.index):
             return data, target_ohe, [], None
-        out, mix = splice_plain(plain, data.view(B, Cc * F, W), host_labels, frames, step,
-                                target_ohe=target_ohe)
+        out, mix = splice_plain(plain, rows, host_labels, frames, step, target_ohe=target_ohe)
         return out.view(B, Cc, F, W), target_ohe, mix, None
     if isinstance(plain, Exception):
         raise plain

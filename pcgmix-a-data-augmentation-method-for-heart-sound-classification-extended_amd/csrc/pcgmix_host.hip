@@ -1229,17 +1229,23 @@ struct PlainStep {
 //    leave the chain.
 // First half: everything up to and including the launch.  lam is needed here only for the splice + warp
 // kernel (its knots come with lam out of one draw); the plain kernel takes it from the record.
+// A begin whose finish does not come (the caller raised in between): the waiting kernel is told to give up.
+void armed_release(pcgmix_ctx* c) {
+  pcgmix_ctx::ArmedOpen& o = c->armed_open;
+  if (!o.open) return;
+  armed_write(c, o.seq | pcgmix::kArmedAbort, nullptr, nullptr, o.B);
+  if (o.warp) (void)slot_commit(c, o.my_slot, o.s);        // the kernel may still read the slot's knots
+  o.open = false;
+  ++c->armed_aborted;
+}
+
 int armed_begin(PlainStep& p, bool arm_warp) {
   pcgmix_ctx* c = p.c;
   const int B = p.B, C = p.C, T = p.T;
   hipStream_t s = p.s;
   hipError_t e = hipSuccess;
   pcgmix_ctx::ArmedOpen& o = c->armed_open;
-  if (o.open) {                              // a begin whose finish never came (the caller raised in between)
-    armed_write(c, o.seq | pcgmix::kArmedAbort, nullptr, nullptr, o.B);
-    if (o.warp) (void)slot_commit(c, o.my_slot, o.s);
-    o.open = false;
-  }
+  armed_release(c);                          // a stale open step: nobody called abort for it
   const int my_slot = c->next;               // (splice + warp only: the slot that carries the knots)
   Slot& sl = c->slot[my_slot];
   const double* op_dev = nullptr;
@@ -1562,6 +1568,15 @@ extern "C" int pcgmix_augment_plain_finish(pcgmix_ctx* c, const int64_t* frames,
               c->armed_open.B, c->armed_open.C, c->armed_open.T, c->armed_open.s,
               reinterpret_cast<pcgmix_stream_t>(c->armed_open.s), std::chrono::steady_clock::now()};
   return armed_finish(p);
+}
+
+extern "C" int pcgmix_augment_plain_abort(pcgmix_ctx* c) {
+  if (!c) return hipErrorInvalidValue;
+  if (!c->armed_open.open) return hipSuccess;
+  DeviceGuard guard(c->device);              // (the splice + warp form records an event behind its slot)
+  if (guard.err != hipSuccess) return (int)guard.err;
+  armed_release(c);
+  return hipSuccess;
 }
 
 extern "C" int pcgmix_ctx_armed_stats(pcgmix_ctx* c, long long* out3) {
