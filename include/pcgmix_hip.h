@@ -1033,7 +1033,9 @@ int pcgmix_time_warp_row_f64(const double* spline_op, const double* knots, int n
                              const float* x, int T, float* y, double* xp_out);
 
 /* ------------------------------------------------------------------------------------------
- * The paper's spectrogram comparison baselines.  csrc/pcgmix_baselines2d.hip.
+ * The paper's spectrogram comparison baselines.  csrc/pcgmix_baselines.hip (zero_rects_kernel) and
+ * csrc/pcgmix_cutpaste.hip (cutpaste_rows_kernel, the segment-table copy shared with the 1D
+ * cut-and-paste family).
  *
  * One launch each for the O(B*C*F*W) part of the reference's 2D baseline branches
  * (augmentations2d.py:461-617); the RNG, the parsing and the per-sample tables stay in
@@ -1053,7 +1055,9 @@ int pcgmix_time_warp_row_f64(const double* spline_op, const double* knots, int n
  *       PCGMIX_PIECE_PARTNER  x[mix[b]]  at p + shift
  *       PCGMIX_PIECE_ZERO     0
  *     along that axis (the other coordinates unchanged); positions beyond the last hi, and source
- *     positions outside the input, give 0.  mix device int32 (B), values in [0, B).  x != y.   */
+ *     positions outside the input, give 0.  mix device int32 (B), values in [0, B).  x != y.
+ *     The batch runs along gridDim.y and gridDim.z, as for pcgmix_cutpaste_rows_f32:
+ *     B <= 32768 * 1024, hipErrorInvalidValue beyond.                                        */
 #define PCGMIX_PIECE_SEGS 5
 #define PCGMIX_PIECE_OWN 0
 #define PCGMIX_PIECE_PARTNER 1
@@ -1064,7 +1068,8 @@ int pcgmix_piecewise_rows_f32(const float* x, float* y, const int32_t* segs, con
                               int axis, int B, int C, int F, int W, int Wo, pcgmix_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * The heart-cycle cut-and-paste family and durmixrespscale.  csrc/pcgmix_cutpaste.hip.
+ * The heart-cycle cut-and-paste family (cutpaste_rows_kernel) and durmixrespscale
+ * (splice_scale_kernel).  csrc/pcgmix_cutpaste.hip.
  *
  * One launch each, on (B, C, T) float32 contiguous batches; the RNG, the partner selection and the
  * per-sample tables stay in hostprep.py.  B == 0 returns 0 and launches nothing.  The input and
@@ -1075,8 +1080,9 @@ int pcgmix_piecewise_rows_f32(const float* x, float* y, const int32_t* segs, con
  *   durratiocutmix) and cutmix_multidim_tensors (:30-58; :1121-1151 lengthcutmix, :1153-1182
  *   datasetcutmix, :1184-1213 wavcutmix, :1285-1316 labelcutmix, with their 'cutout' suffix):
  *     segs device int32 (B, PCGMIX_PIECE_SEGS, 4), {lo, hi, src, shift} along T in the convention
- *     of pcgmix_piecewise_rows_f32 (contiguous, ordered; positions beyond the last hi and source
- *     positions outside [0, T) give 0); mix device int32 (B), values in [0, B).
+ *     of pcgmix_piecewise_rows_f32, whose kernel this is (contiguous, ordered; positions beyond the
+ *     last hi and source positions outside [0, T) give 0); mix device int32 (B), values in [0, B);
+ *     B <= 32768 * 1024.
  *     junctions: NULL, or device int32 (B, 4) {c1, c2, ov, unused} — the '(smooth)' cross-fade
  *     (:41-51): for ov in 1..PCGMIX_CUTPASTE_MAX_OVERLAP and t in [c1-ov, c1+ov), j = t-(c1-ov),
  *       y[b,c,t] = float(double(x[b,c,t]) * (1 - s[j]) + double(x[mix[b],c,c2-ov+j]) * s[j])

@@ -18,7 +18,7 @@ frozen ResNet9-2D 'base' checkpoint through ``saliency.get_saliency_maps(dim=2)`
 displacement search and offset splice.
 
 The paper's spectrogram comparison baselines (augmentations2d.py:461-617) run through the same
-call, with the reference's return values (csrc/pcgmix_baselines2d.hip):
+call, with the reference's return values (csrc/pcgmix_baselines.hip, csrc/pcgmix_cutpaste.hip):
 
     timemask(t)[+p]            columns [int(u1*f[-1]), int(u2*f[-1])) of every row and channel
                                zeroed IN PLACE; returns ``data`` itself, ``[]``, None

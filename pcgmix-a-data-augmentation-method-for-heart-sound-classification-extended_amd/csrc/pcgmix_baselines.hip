@@ -1,13 +1,18 @@
-// pcgmix_baselines.hip — the paper's 1D comparison augmentations for gfx950 (MI355X).
+// pcgmix_baselines.hip — the paper's comparison augmentations for gfx950 (MI355X).
 //
 // The reference runs them through the same augment() call as PCGmix (augmentations.py:777-862,
-// 1002-1048); here each is one launch on the caller's stream:
+// 1002-1048; the spectrogram ones through augmentations2d.py:461-617); here each is one launch on
+// the caller's stream:
 //
 //   mixup(same|mix)      blend_rows_kernel    y[b] = x[b]*lam + x[mix[b]]*(1-lam)      fp32, unfused
 //   magnitudewarp        scale_rows_kernel    y = float(double(x) * S_bc(t))           whole row
 //   respiratoryscale     scale_rows_kernel    y = float(double(x) * s[t])              s from numpy
 //   timemask             zero_spans_kernel    x[b, :, s0:s1] = 0                       in place
 //   timewarp             time_warp_kernel     np.interp(arange(T), xp, x_row), xp from the spline
+//   2D timemask/freqmask zero_rects_kernel    x[b, :, f0:f1, t0:t1] = 0                in place
+//
+// (2D mixup and latentmixup's blend are blend_rows_kernel on the flat sample planes; 2D cutmix and
+// durratiocutmix are the segment-table kernel of pcgmix_cutpaste.hip.)
 //
 // The first four stream (8 algorithmic bytes per element, 12 for the blend: the partner row is
 // a second read).  The time warp is one workgroup per (b, c) row: xp in LDS (global workspace
@@ -28,10 +33,9 @@ namespace {
 constexpr int kThreadsB = 256;
 constexpr int kUnrollB = 4;                         // quads in flight per lane
 constexpr int kEpbB = kThreadsB * 4 * kUnrollB;     // elements per block of the streaming kernels
+constexpr int kZeroChunk = kThreadsB * 4;           // rectangle elements per block
 constexpr int kMaxKnotsB = 64;
 constexpr int kTwLdsMaxT = 5120;                    // 12 B per sample (xp f64 + index i32) <= 60 KB
-
-typedef float float4_a __attribute__((ext_vector_type(4), aligned(16)));
 
 // ---- numpy's interp (numpy/_core/src/multiarray/compiled_base.c) ------------------------------
 // binary_search_with_guess: -1 below xp[0], len above xp[len-1]; linear for len <= 4; otherwise the
@@ -241,6 +245,32 @@ __global__ __launch_bounds__(kThreadsB) void zero_spans_kernel(float* __restrict
   for (int t = s0 + threadIdx.x; t < s1; t += kThreadsB) xr[t] = 0.f;
 }
 
+// 2D timemask / freqmask (and any per-sample rectangle): rect (B, 4) = [f0, f1, t0, t1), applied to
+// every channel, clipped to the plane here as well; only the zeroed elements are touched.
+// grid (B*C, chunks of the largest rectangle).
+__global__ __launch_bounds__(kThreadsB) void zero_rects_kernel(float* __restrict__ x,
+                                                               const int32_t* __restrict__ rect,
+                                                               int C, int F, int W) {
+  const long long plane = blockIdx.x;
+  const int b = (int)(plane / C);
+  int f0 = rect[4 * b], f1 = rect[4 * b + 1], t0 = rect[4 * b + 2], t1 = rect[4 * b + 3];
+  f0 = f0 < 0 ? 0 : f0;
+  t0 = t0 < 0 ? 0 : t0;
+  f1 = f1 > F ? F : f1;
+  t1 = t1 > W ? W : t1;
+  const int h = f1 - f0, w = t1 - t0;
+  if (h <= 0 || w <= 0) return;
+  const int area = h * w;
+  const int lo = (int)blockIdx.y * kZeroChunk;
+  if (lo >= area) return;
+  const int hi = lo + kZeroChunk < area ? lo + kZeroChunk : area;
+  float* xp = x + (size_t)plane * F * W + (size_t)f0 * W + t0;
+  for (int i = lo + (int)threadIdx.x; i < hi; i += kThreadsB) {
+    const int r = i / w, c = i - r * w;
+    xp[r * W + c] = 0.f;
+  }
+}
+
 // timewarp: one workgroup per (b, c) row.  LDS: xp (T doubles) then the search results (T ints)
 // when T <= kTwLdsMaxT, otherwise the same two arrays in the caller's workspace.
 template <bool LDS>
@@ -292,8 +322,6 @@ __global__ __launch_bounds__(kThreadsB) void time_warp_kernel(const float* __res
   for (int t = threadIdx.x; t < T; t += kThreadsB)
     yr[t] = (float)np_interp_pick((double)t, (long long)jx[t], xp, fp, T);
 }
-
-inline bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
 
 // rows (or samples) along gridDim.x, whose limit is the 2^32 work-items of a dispatch; chunks of a
 // row along gridDim.y (<= 65535)
@@ -370,6 +398,21 @@ extern "C" int pcgmix_zero_spans_f32(float* x, const int32_t* spans, int B, int 
   if (!grid_ok(rows, 1)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(zero_spans_kernel, dim3((unsigned)rows), dim3(kThreadsB), 0, reinterpret_cast<hipStream_t>(stream),
                      x, spans, C, T);
+  return hipGetLastError();
+}
+
+extern "C" int pcgmix_zero_rects_f32(float* x, const int32_t* rect, int B, int C, int F, int W,
+                                     int max_area, pcgmix_stream_t stream) {
+  if (B < 0 || C <= 0 || F <= 0 || W <= 0 || max_area < 0) return hipErrorInvalidValue;
+  if (B == 0 || max_area == 0) return hipSuccess;
+  if (!x || !rect) return hipErrorInvalidValue;
+  const long long planes = (long long)B * C;
+  if ((long long)F * W >= (1LL << 31)) return hipErrorInvalidValue;
+  const long long area = (long long)F * W < max_area ? (long long)F * W : max_area;
+  const long long chunks = (area + kZeroChunk - 1) / kZeroChunk;
+  if (!grid_ok(planes, chunks)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(zero_rects_kernel, dim3((unsigned)planes, (unsigned)chunks), dim3(kThreadsB), 0,
+                     reinterpret_cast<hipStream_t>(stream), x, rect, C, F, W);
   return hipGetLastError();
 }
 

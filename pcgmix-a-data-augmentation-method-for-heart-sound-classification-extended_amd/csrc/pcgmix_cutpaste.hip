@@ -1,25 +1,29 @@
-// pcgmix_cutpaste.hip — the heart-cycle cut-and-paste family and durmixrespscale for gfx950 (MI355X).
+// pcgmix_cutpaste.hip — the segment-table copy (the heart-cycle cut-and-paste family in 1D, cutmix and
+// durratiocutmix on spectrograms) and durmixrespscale for gfx950 (MI355X).
 //
 // The reference builds these per sample in a Python loop (a clone, two to four slice copies and a
 // copy into data_new, plus a host round trip for the sinusoid); here each call is ONE launch on the
-// caller's stream over (B, C, T) float32 batches:
+// caller's stream over float32 batches:
 //
 //   durratiocutmix, wav-durratiocutmix                cutpaste_rows_kernel   augmentations.py:340-366,
-//   labelcutmix, lengthcutmix, datasetcutmix,                                :30-58, :983-1000,
+//   labelcutmix, lengthcutmix, datasetcutmix,           (B, C, T)            :30-58, :983-1000,
 //   wavcutmix  (+ '(smooth)', '(rand)', 'cutout')                            :1101-1213, :1285-1316
+//   2D cutmix, durratiocutmix                         cutpaste_rows_kernel   augmentations2d.py:574-617
+//                                                       (B, C, F, W) -> (B, C, F, Wo)
 //   durmixrespscale                                   splice_scale_kernel    :734-775 (:289-337)
 //
-// cutpaste_rows_kernel: per sample a table of PCGMIX_PIECE_SEGS ordered segments along T — the
-// sample itself, its partner at a shift, or zeros (the convention of pcgmix_piecewise_rows_f32) —
-// plus the '(smooth)' junction: over [c1-ov, c1+ov) the output is
+// cutpaste_rows_kernel: per sample a table of PCGMIX_PIECE_SEGS ordered segments along one axis — T,
+// the columns of a spectrogram, or its frequency rows (the '(rand)durratiocutmix' quirk) — each the
+// sample itself, its partner at a shift along that axis, or zeros.  The 1D instantiations add the
+// '(smooth)' junction: over [c1-ov, c1+ov) the output is
 //   float(double(own[t]) * (1 - s[j]) + double(partner[c2-ov+j]) * s[j]),  j = t - (c1-ov),
 // with s = the reference's sigmoid(ov) table (computed on the host by numpy): float64 multiply,
 // multiply, add, each rounded on its own, the sum rounded once to float32.  A zero segment wins over
 // the window (the 'cutout' suffix is applied after the paste), the window over a copied segment.
 // Partner reads at a shift are misaligned: one unaligned 16-byte load per quad, all loads of a lane
 // issued before its first store, element loads only for quads that straddle a segment boundary, the
-// window or the row's edge; non-temporal stores.  Every source index is range-checked in the kernel,
-// whatever the tables hold: an element whose source lies outside the row is 0.
+// window or the input's edge; non-temporal stores.  Every source index is range-checked in the kernel,
+// whatever the tables hold: an element whose source lies outside the input is 0.
 //
 // splice_scale_kernel: the splice of pcgmix_mix_warp_f32 without warp (fp32 mul, mul, add,
 // uncontracted; '(rand)' offsets) and the float64 row multiply of pcgmix_scale_rows_f32 applied to
@@ -91,96 +95,116 @@ struct Junction {
   int lo, n, psh, ov;   // window [lo, lo+n), partner index = t + psh, table row ov-1; n == 0: none
 };
 
-// One output element of row c at position t.
-__device__ __forceinline__ float cutpaste_elem(const Table& P, const Junction& J, const double* __restrict__ sig,
-                                      const float* xo, const float* xm, int t, int T) {
-  const Piece q = piece_at(P, t);
+// One output element at column col of a row whose frequency index is f; ro, rm = that row in the
+// sample and in its partner.  ROWS: the segments run along f (the source is q.sh rows away), else
+// along col.
+template <bool ROWS, bool JUNC>
+__device__ __forceinline__ float piece_elem(const Table& P, const Junction& J, const double* __restrict__ sig,
+                                            const float* ro, const float* rm, int f, int col, int F, int W) {
+  const Piece q = piece_at(P, ROWS ? f : col);
   if (!copies(q)) return 0.f;
-  const int j = t - J.lo;
-  if ((unsigned)j < (unsigned)J.n) {
-    const int sp = t + J.psh;
-    if (sp < 0 || sp >= T) return 0.f;
-    const double s = sig[(J.ov - 1) * 2 * kMaxOv + j];
-    const double a = __dmul_rn((double)xo[t], __dsub_rn(1.0, s));
-    const double b = __dmul_rn((double)xm[sp], s);
-    return __double2float_rn(__dadd_rn(a, b));
+  if (ROWS) {
+    const int sf = f + q.sh;
+    if (sf < 0 || sf >= F || col >= W) return 0.f;
+    return (q.src == PCGMIX_PIECE_OWN ? ro : rm)[q.sh * W + col];
   }
-  const int st = t + q.sh;
-  if (st < 0 || st >= T) return 0.f;
-  return (q.src == PCGMIX_PIECE_OWN ? xo : xm)[st];
+  if (JUNC) {
+    const int j = col - J.lo;
+    if ((unsigned)j < (unsigned)J.n) {
+      const int sp = col + J.psh;
+      if (sp < 0 || sp >= W) return 0.f;
+      const double s = sig[(J.ov - 1) * 2 * kMaxOv + j];
+      const double a = __dmul_rn((double)ro[col], __dsub_rn(1.0, s));
+      const double b = __dmul_rn((double)rm[sp], s);
+      return __double2float_rn(__dadd_rn(a, b));
+    }
+  }
+  const int sc = col + q.sh;
+  if (sc < 0 || sc >= W) return 0.f;
+  return (q.src == PCGMIX_PIECE_OWN ? ro : rm)[sc];
 }
 
-// grid (chunks of the C*T plane, B).  VEC: T % 4 == 0, x and y 16-byte aligned, T >= 4.
-template <bool VEC>
+// y (B, R, Wo) from x (B, R, W), R = C * F rows per sample; grid (chunks of the R*Wo output plane,
+// batch as (y, z)).  The 1D family is F = 1, R = C, W = Wo = T with the junction window (JUNC); the
+// 2D forms have none, and their segments run along the columns or (ROWS, Wo == W) along F.
+// VEC: Wo % 4 == 0 (a quad never straddles two rows), W >= 4, y 16-byte aligned.
+template <bool VEC, bool ROWS, bool JUNC>
 __global__ __launch_bounds__(kThreadsC) void cutpaste_rows_kernel(
     const float* __restrict__ x, float* __restrict__ y, const int32_t* __restrict__ segs,
     const int32_t* __restrict__ mix, const int32_t* __restrict__ junc,
-    const double* __restrict__ sig, int B, int C, int T) {
+    const double* __restrict__ sig, int B, int R, int F, int Win, int Wo) {
+  static_assert(!(ROWS && JUNC), "the junction window runs along the columns");
+  // only the 2D column form changes the width: elsewhere one row pitch serves loads and stores
+  const int W = (ROWS || JUNC) ? Wo : Win;
   const int b = blockIdx.z * kBatchPerZ + blockIdx.y;
   if (b >= B) return;  // block-uniform
-  const int32_t* t = segs + (size_t)b * PCGMIX_PIECE_SEGS * 4;
-  const Table P = load_table(t);
+  const Table P = load_table(segs + (size_t)b * PCGMIX_PIECE_SEGS * 4);
   Junction J{0, 0, 0, 0};
-  if (junc && sig) {
+  if (JUNC && junc && sig) {
     const int c1 = junc[4 * b], c2 = junc[4 * b + 1], ov = junc[4 * b + 2];
     if (ov >= 1 && ov <= kMaxOv) J = Junction{c1 - ov, 2 * ov, c2 - c1, ov};
   }
   int m = mix[b];
   m = (m < 0 || m >= B) ? b : m;  // memory safety; the host validates as well
-  const int plane = C * T;
-  const float* xo = x + (size_t)b * plane;
-  const float* xm = x + (size_t)m * plane;
-  float* yo = y + (size_t)b * plane;
+  const size_t in_plane = (size_t)R * W;
+  const int out_plane = R * Wo;
+  const float* xo = x + (size_t)b * in_plane;
+  const float* xm = x + (size_t)m * in_plane;
+  float* yo = y + (size_t)b * out_plane;
   const int base = (int)blockIdx.x * kEpbC;
   if (VEC) {
     // Phase 1, branch-free: one 16-byte load per quad — its source when the quad lies in one copied
-    // segment, outside the window and inside the row (unaligned at a shift), else the sample's own
-    // quad (a valid address whose value is not used).  Phase 2: zeros, the element path, the store.
+    // segment, outside the window and inside the input (unaligned at a column shift), else a valid
+    // address whose value is not used: the sample's own quad where the output plane is the input plane
+    // (1D), its first quad otherwise (with Wo > W the output offset lies outside the input).
+    // Phase 2: zeros, the element path, the store.
     float4_u v[kUnrollC];
-    int mode[kUnrollC], cc[kUnrollC], tt[kUnrollC];  // mode: 0 copy, 1 zero, 2 by element, -1 none
+    int mode[kUnrollC], rr[kUnrollC], cc[kUnrollC];  // mode: 0 copy, 1 zero, 2 by element, -1 none
 #pragma unroll
     for (int u = 0; u < kUnrollC; ++u) {
       const int o = base + (u * kThreadsC + (int)threadIdx.x) * 4;
-      const int oc = o < plane ? o : 0;
-      const int c = oc / T;
-      const int t0 = oc - c * T;
-      const Piece q0 = piece_at(P, t0);
-      const Piece q3 = piece_at(P, t0 + 3);
-      const int st = t0 + q0.sh;
+      const int oc = o < out_plane ? o : 0;
+      const int r = oc / Wo;
+      const int col = oc - r * Wo, f = ROWS ? r % F : 0;
+      const Piece q0 = piece_at(P, ROWS ? f : col);
+      const Piece q3 = ROWS ? q0 : piece_at(P, col + 3);
+      const int sf = f + (ROWS ? q0.sh : 0);
+      const int sc = col + (ROWS ? 0 : q0.sh);
       const bool one = q0.k == q3.k;
-      const bool inside = st >= 0 && st + 3 < T;
-      const bool window = t0 + 3 >= J.lo && t0 < J.lo + J.n;
-      mode[u] = o >= plane ? -1 : !one ? 2 : !copies(q0) ? 1 : (window || !inside) ? 2 : 0;
-      const float* p = mode[u] == 0 ? (q0.src == PCGMIX_PIECE_OWN ? xo : xm) + c * T + st : xo + oc;
+      const bool inside = sf >= 0 && (!ROWS || sf < F) && sc >= 0 && sc + 3 < W;
+      const bool window = JUNC && col + 3 >= J.lo && col < J.lo + J.n;
+      mode[u] = o >= out_plane ? -1 : !one ? 2 : !copies(q0) ? 1 : (window || !inside) ? 2 : 0;
+      const float* p = mode[u] == 0 ? (q0.src == PCGMIX_PIECE_OWN ? xo : xm) + (r - f + sf) * W + sc
+                                    : JUNC ? xo + oc : xo;
       v[u] = *reinterpret_cast<const float4_u*>(p);
-      cc[u] = c;
-      tt[u] = t0;
+      rr[u] = r;
+      cc[u] = col;
     }
 #pragma unroll
     for (int u = 0; u < kUnrollC; ++u) {
       if (mode[u] < 0) continue;
-      const int c = cc[u], t0 = tt[u];
+      const int r = rr[u], col = cc[u];
       float4_a w;
       if (mode[u] == 0) {
         w = (float4_a){v[u].x, v[u].y, v[u].z, v[u].w};
       } else if (mode[u] == 1) {
         w = (float4_a){0.f, 0.f, 0.f, 0.f};
       } else {
-        const float* ro = xo + c * T;
-        const float* rm = xm + c * T;
-        w.x = cutpaste_elem(P, J, sig, ro, rm, t0, T);
-        w.y = cutpaste_elem(P, J, sig, ro, rm, t0 + 1, T);
-        w.z = cutpaste_elem(P, J, sig, ro, rm, t0 + 2, T);
-        w.w = cutpaste_elem(P, J, sig, ro, rm, t0 + 3, T);
+        const int f = ROWS ? r % F : 0;
+        const float* ro = xo + r * W;
+        const float* rm = xm + r * W;
+        w.x = piece_elem<ROWS, JUNC>(P, J, sig, ro, rm, f, col, F, W);
+        w.y = piece_elem<ROWS, JUNC>(P, J, sig, ro, rm, f, col + 1, F, W);
+        w.z = piece_elem<ROWS, JUNC>(P, J, sig, ro, rm, f, col + 2, F, W);
+        w.w = piece_elem<ROWS, JUNC>(P, J, sig, ro, rm, f, col + 3, F, W);
       }
-      __builtin_nontemporal_store(w, reinterpret_cast<float4_a*>(yo + c * T + t0));
+      __builtin_nontemporal_store(w, reinterpret_cast<float4_a*>(yo + r * Wo + col));
     }
   } else {
-    const int end = base + kEpbC < plane ? base + kEpbC : plane;
+    const int end = base + kEpbC < out_plane ? base + kEpbC : out_plane;
     for (int o = base + (int)threadIdx.x; o < end; o += kThreadsC) {
-      const int c = o / T;
-      const int t0 = o - c * T;
-      yo[o] = cutpaste_elem(P, J, sig, xo + c * T, xm + c * T, t0, T);
+      const int r = o / Wo;
+      yo[o] = piece_elem<ROWS, JUNC>(P, J, sig, xo + r * W, xm + r * W, ROWS ? r % F : 0, o - r * Wo, F, W);
     }
   }
 }
@@ -208,10 +232,8 @@ __global__ __launch_bounds__(kThreadsC) void splice_scale_kernel(
   const size_t own_base = (size_t)b * plane;
   const size_t par_base = (size_t)m * plane;
   if constexpr (VEC == 4) {
-    // The two phases of mix_body (pcgmix_mix.hip): all own, partner and row loads of a lane are in
-    // flight together; the partner quad is ONE unaligned 16-byte load at the shift of the first
-    // blended element, elements with another shift (a state boundary inside the quad) or a clamped
-    // quad are patched by a scalar load in phase 2.
+    // The two phases of mix_body (pcgmix_mix.hip) on the same quad_plan / quad_blend: all own, partner
+    // and row loads of a lane are in flight together.
     float4_a own[U];
     float4_u par[U];
     double2_a r01[U], r23[U];
@@ -223,20 +245,8 @@ __global__ __launch_bounds__(kThreadsC) void splice_scale_kernel(
       const int ii = valid ? i : 0;
       const int c = ii / T;
       const int t0 = ii - c * T;
-      bool hit[4];
-      int d[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) d[e] = blend_shift(sm, t0 + e, hit[e]);
-      const int dsel = hit[0] ? d[0] : hit[1] ? d[1] : hit[2] ? d[2] : hit[3] ? d[3] : 0;
-      int src0 = t0 + dsel;
-      src0 = src0 < 0 ? 0 : (src0 > T - 4 ? T - 4 : src0);
-      const bool clamped = src0 != t0 + dsel;
-      int mask = valid ? 0x100 : 0;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        if (hit[e]) mask |= 1 << e;
-        if (hit[e] && (clamped || d[e] != dsel)) mask |= 16 << e;
-      }
+      int src0;
+      const int mask = (valid ? 0x100 : 0) | quad_plan(sm, t0, T, src0);
       own[q] = *reinterpret_cast<const float4_a*>(x + own_base + ii);
       // not predicated (a branch around the load would serialise a lane's loads): a quad without a
       // blended element re-reads its own quad, a line that is in flight already
@@ -254,20 +264,11 @@ __global__ __launch_bounds__(kThreadsC) void splice_scale_kernel(
       const int mask = masks[q];
       if (!(mask & 0x100)) continue;
       const int t0 = t0s[q], c = cs[q];
-      const float o[4] = {own[q].x, own[q].y, own[q].z, own[q].w};
-      const float pv[4] = {par[q].x, par[q].y, par[q].z, par[q].w};
       const double rw[4] = {r01[q].x, r01[q].y, r23[q].x, r23[q].y};
       float out[4];
+      quad_blend(out, own[q], par[q], x + par_base + (size_t)c * T, sm, t0, mask, lam, oml);
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float v = pv[e];
-        if (mask & (16 << e)) {  // rare: patch with the element's own shift
-          bool h;
-          const int de = blend_shift(sm, t0 + e, h);
-          v = x[par_base + (size_t)c * T + t0 + e + de];
-        }
-        out[e] = scale64((mask & (1 << e)) ? blend(o[e], v, lam, oml) : o[e], rw[e]);
-      }
+      for (int e = 0; e < 4; ++e) out[e] = scale64(out[e], rw[e]);
       const float4_a v4 = {out[0], out[1], out[2], out[3]};
       const int i = chunk0 + (q * kThreadsC + (int)threadIdx.x) * 4;
       __builtin_nontemporal_store(v4, reinterpret_cast<float4_a*>(y + own_base + i));
@@ -285,8 +286,6 @@ __global__ __launch_bounds__(kThreadsC) void splice_scale_kernel(
   }
 }
 
-inline bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
-
 // grid for `chunks` blocks per sample and B samples; false when it does not fit
 inline bool batch_grid(long long chunks, int B, dim3* grid) {
   if (chunks <= 0 || chunks > 0x7fffffffLL || B > kBatchPerZ * 1024) return false;
@@ -300,6 +299,23 @@ inline bool batch_grid(long long chunks, int B, dim3* grid) {
 
 using namespace pcgmix;
 
+// Launches the segment-table kernel over y (B, R, Wo) from x (B, R, W).
+template <bool ROWS, bool JUNC>
+static int launch_rows(bool vec, const float* x, float* y, const int32_t* segs, const int32_t* mix,
+                       const int32_t* junc, const double* sig, int B, int R, int F, int W, int Wo,
+                       pcgmix_stream_t stream) {
+  dim3 grid;
+  if (!batch_grid(((long long)R * Wo + kEpbC - 1) / kEpbC, B, &grid)) return hipErrorInvalidValue;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (vec)
+    hipLaunchKernelGGL((cutpaste_rows_kernel<true, ROWS, JUNC>), grid, dim3(kThreadsC), 0, s, x, y, segs, mix, junc,
+                       sig, B, R, F, W, Wo);
+  else
+    hipLaunchKernelGGL((cutpaste_rows_kernel<false, ROWS, JUNC>), grid, dim3(kThreadsC), 0, s, x, y, segs, mix, junc,
+                       sig, B, R, F, W, Wo);
+  return hipGetLastError();
+}
+
 extern "C" int pcgmix_cutpaste_rows_f32(const float* x, float* y, const int32_t* segs,
                                         const int32_t* mix, const int32_t* junctions,
                                         const double* sigmoid_tab, int B, int C, int T,
@@ -311,19 +327,25 @@ extern "C" int pcgmix_cutpaste_rows_f32(const float* x, float* y, const int32_t*
   // in-sample indices are 32-bit (one integer division per quad)
   if (plane >= (1LL << 31) - kEpbC) return hipErrorInvalidValue;
   // the input and the output may not overlap: every sample reads another sample's rows
-  const uintptr_t xa = reinterpret_cast<uintptr_t>(x), ya = reinterpret_cast<uintptr_t>(y);
-  const unsigned long long bytes = (unsigned long long)B * plane * sizeof(float);
-  if (xa < ya + bytes && ya < xa + bytes) return hipErrorInvalidValue;
-  dim3 grid;
-  if (!batch_grid((plane + kEpbC - 1) / kEpbC, B, &grid)) return hipErrorInvalidValue;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (T % 4 == 0 && aligned16(x) && aligned16(y))
-    hipLaunchKernelGGL((cutpaste_rows_kernel<true>), grid, dim3(kThreadsC), 0, s, x, y, segs, mix, junctions,
-                       sigmoid_tab, B, C, T);
-  else
-    hipLaunchKernelGGL((cutpaste_rows_kernel<false>), grid, dim3(kThreadsC), 0, s, x, y, segs, mix, junctions,
-                       sigmoid_tab, B, C, T);
-  return hipGetLastError();
+  if (ranges_overlap(x, y, (unsigned long long)B * plane * sizeof(float))) return hipErrorInvalidValue;
+  return launch_rows<false, true>(T % 4 == 0 && aligned16(x) && aligned16(y), x, y, segs, mix, junctions,
+                                  sigmoid_tab, B, C, 1, T, T, stream);
+}
+
+extern "C" int pcgmix_piecewise_rows_f32(const float* x, float* y, const int32_t* segs,
+                                         const int32_t* mix, int axis, int B, int C, int F, int W,
+                                         int Wo, pcgmix_stream_t stream) {
+  if (B < 0 || C <= 0 || F <= 0 || W <= 0 || Wo <= 0 || (axis != 0 && axis != 1))
+    return hipErrorInvalidValue;
+  if (axis == 1 && Wo != W) return hipErrorInvalidValue;
+  if (B == 0) return hipSuccess;
+  if (!x || !y || !segs || !mix || x == y) return hipErrorInvalidValue;
+  // in-sample indices are 32-bit (one integer division per quad): both planes below 2^31 - kEpbC
+  if ((long long)C * F * Wo >= (1LL << 31) - kEpbC || (long long)C * F * W >= (1LL << 31))
+    return hipErrorInvalidValue;
+  const bool vec = Wo % 4 == 0 && W >= 4 && aligned16(y);
+  return axis == 1 ? launch_rows<true, false>(vec, x, y, segs, mix, nullptr, nullptr, B, C * F, F, W, Wo, stream)
+                   : launch_rows<false, false>(vec, x, y, segs, mix, nullptr, nullptr, B, C * F, F, W, Wo, stream);
 }
 
 extern "C" int pcgmix_mix_scale_f32(const float* x, float* y, const int32_t* frames,
@@ -334,9 +356,7 @@ extern "C" int pcgmix_mix_scale_f32(const float* x, float* y, const int32_t* fra
   if (!x || !y || !frames || !mix_idx || !row || x == y) return hipErrorInvalidValue;
   const long long plane = (long long)C * T;
   if (plane >= (1LL << 31) - kThreadsC * 8) return hipErrorInvalidValue;
-  const uintptr_t xa = reinterpret_cast<uintptr_t>(x), ya = reinterpret_cast<uintptr_t>(y);
-  const unsigned long long bytes = (unsigned long long)B * plane * sizeof(float);
-  if (xa < ya + bytes && ya < xa + bytes) return hipErrorInvalidValue;
+  if (ranges_overlap(x, y, (unsigned long long)B * plane * sizeof(float))) return hipErrorInvalidValue;
   const float oml = 1.0f - lam;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const bool vec = T % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(row);

@@ -7,6 +7,14 @@
 
 namespace pcgmix {
 
+inline bool aligned16(const void* p) { return !(reinterpret_cast<uintptr_t>(p) & 15); }
+
+// true when the byte ranges [a, a + bytes) and [b, b + bytes) intersect
+inline bool ranges_overlap(const void* a, const void* b, unsigned long long bytes) {
+  const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+  return pa < pb + bytes && pb < pa + bytes;
+}
+
 // Large dynamic-LDS opt-in is a per-device property of the kernel: raise it once per
 // (kernel, device) — `done` is a bitmask indexed by the current device (<= 64 devices).
 inline hipError_t allow_large_lds(const void* kernel, unsigned long long* done, int bytes) {
@@ -171,7 +179,7 @@ __device__ __forceinline__ uint32_t onehot_argmax4(const int64_t* __restrict__ o
   return packed;
 }
 
-// ---- device code shared by the splice kernels (pcgmix_mix.hip, pcgmix_cutpaste.hip) -----------------
+// ---- device code shared by the streaming kernels (pcgmix_mix.hip, pcgmix_cutpaste.hip, pcgmix_baselines.hip)
 // 16-byte vector whose address is only known to be 4-byte aligned (partner rows are read at
 // an arbitrary sample offset); gfx950 global loads handle the misalignment in hardware.
 typedef float float4_u __attribute__((ext_vector_type(4), aligned(4)));

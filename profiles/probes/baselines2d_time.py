@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The paper's spectrogram comparison baselines (csrc/pcgmix_baselines2d.hip) at (256, 1, 128, 128).
+"""The paper's spectrogram comparison baselines (csrc/pcgmix_baselines.hip, pcgmix_cutpaste.hip) at
+(256, 1, 128, 128).
 
   augment   steady-state time of one augment() call: 20 warm-up calls, then 200 calls back to
             back (a fresh step each, every gate firing), one synchronisation at the end; beside it

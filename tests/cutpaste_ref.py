@@ -1,6 +1,7 @@
-"""CPU restatements for the cut-and-paste tests (tests/test_cutpaste_cpu.py, test_cutpaste_gpu.py):
-what the kernels of csrc/pcgmix_cutpaste.hip compute from a plan's tables, in numpy, element by
-element, and the golden files' helpers.  Not a test module."""
+"""CPU restatements for the cut-and-paste and 2D cutmix tests (tests/test_cutpaste_cpu.py,
+test_cutpaste_gpu.py, test_baselines2d_cpu.py, test_baselines2d_gpu.py): what the kernels of
+csrc/pcgmix_cutpaste.hip compute from a plan's tables, in numpy, and the golden files' helpers.
+Not a test module."""
 import glob
 import os
 
@@ -35,51 +36,52 @@ def assert_np_state(g):
     assert has_gauss == int(tail[1]) and (not has_gauss or cached == tail[2])
 
 
-def piece_index(segs_b, T):
-    """Per position of one sample: index of the segment it falls in (the LAST segment whose lo <= p,
-    as the kernels choose it), -1 where the position is zero for lying outside the table."""
-    lo = segs_b[:, 0]
-    p = np.arange(T)
-    k = np.zeros(T, dtype=np.int64)
-    for j in range(1, segs_b.shape[0]):
-        k[p >= lo[j]] = j
-    k[p < lo[0]] = -1
-    k[p >= segs_b[-1, 1]] = -1
-    return k
+def replay_pieces(x, segs, mix, axis, Wo, junctions=None, sig_tab=None):
+    """The segment-table contract of pcgmix_piecewise_rows_f32 and pcgmix_cutpaste_rows_f32
+    (include/pcgmix_hip.h) in numpy, for all samples at once: y (B, C, F, Wo) from x (B, C, F, W) and
+    the (B, 5, 4) table {lo, hi, src, shift} along the columns (axis 0) or along F (axis 1).  A position
+    takes the LAST segment whose lo <= p; it is zero before the first lo, at or beyond the last hi, in a
+    ZERO segment and where its source position lies outside the input.  junctions (B, 4) with the
+    (10, 20) float64 coefficient table: the '(smooth)' window along the columns (W == Wo)."""
+    B, C, F, W = x.shape
+    n_out, n_in = (Wo, W) if axis == 0 else (F, F)
+    rows = np.arange(B)[:, None]
+    mix = np.asarray(mix).astype(np.int64)
+    m = np.where((mix >= 0) & (mix < B), mix, np.arange(B))
+    p = np.arange(n_out)[None, :]
+    k = np.zeros((B, n_out), dtype=np.int64)
+    for j in range(1, segs.shape[1]):
+        k[p >= segs[:, j, 0:1]] = j
+    src = np.take_along_axis(segs[:, :, 2], k, 1)
+    st = p + np.take_along_axis(segs[:, :, 3], k, 1).astype(np.int64)
+    copied = ((src == OWN) | (src == PARTNER)) & (p >= segs[:, 0, 0:1]) & (p < segs[:, -1, 1:2])
+    ok = copied & (st >= 0) & (st < n_in)
+    who = np.where(src == OWN, rows, m[:, None])
+    stc = np.clip(st, 0, n_in - 1)
+    if axis == 0:
+        y = np.where(ok[:, :, None, None], x[who, :, :, stc], np.float32(0)).transpose(0, 2, 3, 1)
+    else:
+        y = np.where(ok[:, :, None, None], x[who, :, stc, :], np.float32(0)).transpose(0, 2, 1, 3)
+    y = np.ascontiguousarray(y)
+    if junctions is not None:
+        assert axis == 0 and W == Wo
+        c1, c2, ov = (junctions[:, i].astype(np.int64) for i in range(3))
+        for j in range(2 * MAX_OV):
+            t, sp = c1 - ov + j, c2 - ov + j
+            bs = np.nonzero((ov >= 1) & (ov <= MAX_OV) & (j < 2 * ov) & (t >= 0) & (t < W))[0]
+            bs = bs[copied[bs, t[bs]]]
+            inside = ((sp[bs] >= 0) & (sp[bs] < W))[:, None, None]
+            s = sig_tab[ov[bs] - 1, j][:, None, None]
+            val = (x[bs, :, :, t[bs]].astype(np.float64) * (1.0 - s)
+                   + x[m[bs], :, :, np.clip(sp[bs], 0, W - 1)].astype(np.float64) * s).astype(np.float32)
+            y[bs, :, :, t[bs]] = np.where(inside, val, np.float32(0))
+    return y
 
 
 def replay_cutpaste(x, segs, mix, junctions=None, sig_tab=None):
     """pcgmix_cutpaste_rows_f32 in numpy: (B, C, T) float32 from the (B, 5, 4) table, the partners,
-    the optional (B, 4) junctions and the (10, 20) float64 coefficient table."""
-    B, C, T = x.shape
-    y = np.zeros_like(x)
-    p = np.arange(T)
-    for b in range(B):
-        m = int(mix[b])
-        m = b if not 0 <= m < B else m
-        k = piece_index(segs[b], T)
-        src = np.where(k >= 0, segs[b][np.maximum(k, 0), 2], ZERO)
-        sh = np.where(k >= 0, segs[b][np.maximum(k, 0), 3], 0)
-        st = p + sh
-        ok = (src != ZERO) & (st >= 0) & (st < T)
-        stc = np.clip(st, 0, T - 1)
-        row = np.where(src == OWN, x[b][:, stc], x[m][:, stc])
-        y[b] = np.where(ok, row, np.float32(0))
-        if junctions is not None:
-            c1, c2, ov = (int(v) for v in junctions[b][:3])
-            if 1 <= ov <= MAX_OV:
-                for j in range(2 * ov):
-                    t = c1 - ov + j
-                    if not 0 <= t < T or src[t] == ZERO:
-                        continue
-                    sp = c2 - ov + j
-                    if not 0 <= sp < T:
-                        y[b, :, t] = 0
-                        continue
-                    s = sig_tab[ov - 1, j]
-                    y[b, :, t] = (x[b, :, t].astype(np.float64) * (1.0 - s)
-                                  + x[m, :, sp].astype(np.float64) * s).astype(np.float32)
-    return y
+    the optional (B, 4) junctions and the (10, 20) float64 coefficient table — the F = 1 case."""
+    return replay_pieces(x[:, :, None, :], segs, mix, 0, x.shape[2], junctions, sig_tab)[:, :, 0, :]
 
 
 def replay_splice(x, frames, mix, off, lam32):

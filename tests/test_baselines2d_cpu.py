@@ -12,6 +12,7 @@ import torch
 
 import pcgmix_amd  # noqa: F401
 from pcgmix_amd import hostprep as H
+from cutpaste_ref import replay_pieces
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 BASE2D_FILES = sorted(glob.glob(os.path.join(GOLDEN, "base2d_*.npz")))
@@ -54,22 +55,6 @@ class ProbeNet(torch.nn.Module):
         if depth == 2:
             return h
         return h.flatten(1) * 4.0
-
-
-def apply_segments(x, segs, mix, axis, out_cols):
-    """numpy restatement of pcgmix_piecewise_rows_f32 (include/pcgmix_hip.h)."""
-    B, C, F, W = x.shape
-    y = np.zeros((B, C, F, out_cols), np.float32)
-    for b in range(B):
-        for lo, hi, src, sh in segs[b]:
-            if src == 2 or hi <= lo:
-                continue
-            s = x[b] if src == 0 else x[mix[b]]
-            if axis == 0:
-                y[b, :, :, lo:hi] = s[:, :, lo + sh:hi + sh]
-            else:
-                y[b, :, lo:hi, :] = s[:, lo + sh:hi + sh, :]
-    return y
 
 
 def plan_for(g):
@@ -262,7 +247,7 @@ def test_plan_matches_the_reference(path):
     segs = plan.segs
     assert (segs[:, 0, 0] == 0).all() and (segs[:, :-1, 1] == segs[:, 1:, 0]).all()
     assert (segs[:, -1, 1] == (plan.out_cols if plan.seg_axis == 0 else x.shape[2])).all()
-    assert np.array_equal(apply_segments(x, segs, plan.mix, plan.seg_axis, plan.out_cols), g["y"])
+    assert np.array_equal(replay_pieces(x, segs, plan.mix, plan.seg_axis, plan.out_cols), g["y"])
     if "(rand)" in method and "durratiocutmix" in method:
         assert plan.seg_axis == 1
         off = H.rand_offsets(g["frames"], plan.mix, int(g["step"]))

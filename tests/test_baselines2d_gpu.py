@@ -14,6 +14,7 @@ import torch
 
 import pcgmix_amd  # noqa: F401
 from pcgmix_amd import augmentations2d, hostprep, models2d, synthetic, train_model as tm
+from cutpaste_ref import replay_pieces
 from test_baselines2d_cpu import BASE2D_FILES, ProbeNet, load, np_state_is, set_np_state
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -337,37 +338,23 @@ def test_odd_shapes_against_torch(method, shape):
     assert y.shape == want.shape and torch.equal(y, want)
 
 
-def ref_pieces(x, segs, mix, axis, Wo):
-    """Element-wise numpy restatement of the pcgmix_piecewise_rows_f32 contract (include/pcgmix_hip.h):
-    the last segment whose lo <= p, zero before the first / at or beyond the last hi / for a ZERO
-    segment / for a source position outside the input."""
-    B, C, F, W = x.shape
-    y = np.zeros((B, C, F, Wo), np.float32)
-    for b in range(B):
-        lo, end = segs[b, :, 0], segs[b, -1, 1]
-        for p in range(Wo if axis == 0 else F):
-            if p < lo[0] or p >= end:
-                continue
-            k = int(np.nonzero(lo <= p)[0][-1])
-            src, sh = segs[b, k, 2], segs[b, k, 3]
-            if src not in (0, 1):
-                continue
-            s = x[b] if src == 0 else x[mix[b]]
-            q = p + sh
-            if axis == 0 and 0 <= q < W:
-                y[b, :, :, p] = s[:, :, q]
-            elif axis == 1 and 0 <= q < F:
-                y[b, :, p, :] = s[:, q, :]
-    return y
-
-
 @pytest.mark.parametrize("axis, F, W, Wo", [(0, 13, 20, 20), (0, 13, 18, 13), (0, 9, 7, 12), (0, 11, 3, 8),
                                             (1, 13, 16, 16), (1, 14, 15, 15)])
 def test_piecewise_kernel_on_random_tables(axis, F, W, Wo):
     """Any contiguous table: zero segments between short copies, empty segments, shifts that leave the
     input, an end before the last position — the vector and the element paths."""
+    check_random_tables(axis, F, W, Wo, B=12)
+
+
+def test_piecewise_kernel_output_plane_twice_the_input():
+    """Wo = 2 W on the vector path: the output offset of a quad lies outside a sample's input plane,
+    and for the last sample outside ``x`` — the load a non-copy quad issues must not use it."""
+    check_random_tables(0, 5, 8, 16, B=2)
+
+
+def check_random_tables(axis, F, W, Wo, B):
     rs = np.random.RandomState(F * 100 + W)
-    B, C = 12, 2
+    C = 2
     N = Wo if axis == 0 else F
     x = rs.standard_normal((B, C, F, W)).astype(np.float32)
     mix = rs.permutation(B)
@@ -384,4 +371,4 @@ def test_piecewise_kernel_on_random_tables(axis, F, W, Wo):
     data = torch.from_numpy(x).to(DEV)
     y = augmentations2d.piecewise_rows(data, segs, mix, axis, Wo)
     torch.cuda.synchronize()
-    assert np.array_equal(y.cpu().numpy(), ref_pieces(x, segs, mix, axis, Wo))
+    assert np.array_equal(y.cpu().numpy(), replay_pieces(x, segs, mix, axis, Wo))

@@ -19,7 +19,7 @@ import pcgmix_amd  # noqa: F401
 from pcgmix_amd import _lib, augmentations, augmentations2d, hostprep, models, synthetic
 from pcgmix_amd import train_model as tm
 from cutpaste_ref import (CUTOUT2D_FILES, CUTPASTE_FILES, assert_np_state, load, replay_cutpaste,
-                          replay_mixscale, replay_plan, set_np_state)
+                          replay_mixscale, replay_pieces, replay_plan, set_np_state)
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -184,6 +184,52 @@ def test_cutpaste_kernel_on_random_tables(shape, seed, wild):
     got = run_cutpaste(x, segs, mix, junc)
     want = replay_cutpaste(x, segs, mix, junc, hostprep.sigmoid_table())
     assert np.array_equal(got, want)
+
+
+# ------------------------------------------------------------------ one kernel behind both entry points
+@pytest.mark.parametrize("wild", [False, True], ids=["valid", "sources_outside_the_row"])
+@pytest.mark.parametrize("T", [37, 64], ids=["by_element", "by_quad"])
+def test_same_table_through_both_entry_points(T, wild):
+    """pcgmix_cutpaste_rows_f32 without junctions and pcgmix_piecewise_rows_f32 along the columns of a
+    one-row image (F = 1, W = Wo = T) are the same copy: identical bytes, equal to the restatement."""
+    B, C = 3, 2
+    rs = np.random.RandomState(10 * T + wild)
+    x = rs.standard_normal((B, C, T)).astype(np.float32)
+    segs = random_table(rs, B, T, wild)
+    mix = rs.randint(0, B, size=B)
+    one = run_cutpaste(x, segs, mix, None)
+    two = augmentations2d.piecewise_rows(dev(x).view(B, C, 1, T), segs, mix, 0, T)
+    torch.cuda.synchronize()
+    two = two.cpu().numpy()[:, :, 0, :]
+    assert np.array_equal(one.view(np.uint32), two.view(np.uint32))
+    assert np.array_equal(one, replay_pieces(x[:, :, None, :], segs, mix, 0, T)[:, :, 0, :])
+
+
+BIG_B = 32768 + 2            # the batch runs along gridDim.y up to 32768, then along gridDim.z
+
+
+@pytest.mark.parametrize("wild", [False, True], ids=["valid", "sources_outside_the_row"])
+def test_cutpaste_batch_across_the_grid_z_boundary(wild):
+    B, C, T = BIG_B, 1, 8
+    rs = np.random.RandomState(5 + wild)
+    x = rs.standard_normal((B, C, T)).astype(np.float32)
+    segs = random_table(rs, B, T, wild)
+    mix = rs.randint(0, B, size=B)                               # partners on either side of the boundary
+    junc = random_junctions(rs, B, T, wild)
+    got = run_cutpaste(x, segs, mix, junc)
+    assert np.array_equal(got, replay_cutpaste(x, segs, mix, junc, hostprep.sigmoid_table()))
+
+
+@pytest.mark.parametrize("axis", [0, 1], ids=["columns", "freq_rows"])
+def test_piecewise_batch_across_the_grid_z_boundary(axis):
+    B, C, F, W = BIG_B, 1, 2, 4
+    rs = np.random.RandomState(7 + axis)
+    x = rs.standard_normal((B, C, F, W)).astype(np.float32)
+    segs = random_table(rs, B, W if axis == 0 else F, True)
+    mix = rs.randint(0, B, size=B)
+    y = augmentations2d.piecewise_rows(dev(x), segs, mix, axis, W)
+    torch.cuda.synchronize()
+    assert np.array_equal(y.cpu().numpy(), replay_pieces(x, segs, mix, axis, W))
 
 
 def random_splice(rs, B, C, T):
