@@ -360,13 +360,20 @@ def make_optimizer(args, model: nn.Module):
     return opt, sched
 
 
+def rank_and_world():
+    """(rank, world size) of this process; (0, 1) without an initialised process group."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        return dist.get_rank(), dist.get_world_size()
+    return 0, 1
+
+
 def wrap_distributed(model: nn.Module, device: torch.device) -> nn.Module:
     """One process per GPU; gradients are averaged by an all-reduce (RCCL over xGMI when the
     process group is 'nccl').  The whole model fits one bucket (<= 26 MB), so the single
     all-reduce overlaps the tail of backward.  BatchNorm statistics stay per rank, as they are
     per replica under the reference's DataParallel."""
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+    if rank_and_world()[1] == 1:
         return model
     ids = [device.index] if device.type == "cuda" else None
     return nn.parallel.DistributedDataParallel(model, device_ids=ids, bucket_cap_mb=64,
@@ -444,10 +451,10 @@ def augmentation_counter(args, step_counter):
     streams per rank that never collide across steps.  One process: unchanged."""
     if not getattr(args, "rank_seed", False):
         return step_counter
-    import torch.distributed as dist
-    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+    rank, world = rank_and_world()
+    if world == 1:
         return step_counter
-    return _SeedView(int(step_counter.count) * dist.get_world_size() + dist.get_rank())
+    return _SeedView(int(step_counter.count) * world + rank)
 
 
 def reseed_device_rng(args, device) -> None:
@@ -460,9 +467,7 @@ def reseed_device_rng(args, device) -> None:
     seed = getattr(args, "seed_fix", None)
     if seed is not None and device.type == "cuda":
         if getattr(args, "rank_seed", False):           # non-reference: per-rank dropout masks
-            import torch.distributed as dist
-            if dist.is_available() and dist.is_initialized():
-                seed = int(seed) + dist.get_rank()
+            seed = int(seed) + rank_and_world()[0]
         torch.cuda.manual_seed(int(seed))
 
 
@@ -499,16 +504,22 @@ def latent_method(args) -> bool:
     return method_route(args).family == "latent"
 
 
-def cutpaste_method(args) -> bool:
-    """True when ``args.method`` reaches the cut-and-paste family, durmixrespscale or bare cutout:
-    eager ``train_step`` only."""
-    return method_route(args).family == "cutpaste"
-
-
 def cutpaste_graph_message(args) -> str:
     return (f"method {args.method!r} ({method_route(args).branch}) is not "
             f"wired into the captured step: its per-step segment tables have no slot in the graph's "
             f"static block; use train_step")
+
+
+def capture_refusal(args) -> Optional[str]:
+    """Why a step of ``args`` cannot be captured and stays with the eager ``train_step``
+    (``GraphedTrainStep`` raises it, the drivers test it), or None.  The cut-and-paste family
+    includes durmixrespscale and bare cutout."""
+    if args.dataset in SPECTROGRAM_DATASETS:
+        return "graphed step is wired for the 1D path"
+    family = method_route(args).family
+    if family == "latent":
+        return LATENT_GRAPH_MESSAGE
+    return cutpaste_graph_message(args) if family == "cutpaste" else None
 
 
 def latent_fused_model(args, model, criterion, data, target_ohe, epoch):
@@ -540,6 +551,19 @@ def latent_host_step(args, data, target, target_ohe, step: int):
     with torch.cuda.device(data.device):
         mix_dev, inv_dev = augmentations.latent_partners(plan.mix, data.device)
     return mix_dev, inv_dev, float(plan.lam32)
+
+
+def clips_outside_optimizer(args, optimizer) -> bool:
+    """``clip_grad_value_`` as a pass of its own: ClipAdam clips in its kernel."""
+    return bool(args.grad_clip) and not isinstance(optimizer, ClipAdam)
+
+
+def add_stats(stats: dict, loss, out, truth) -> None:
+    """One step into ``stats``; ``truth`` is class indices (B,) or target rows (B, classes)."""
+    with torch.no_grad():
+        stats["loss_sum"] += loss
+        stats["hits"] += (out.argmax(1) == (truth.argmax(1) if truth.dim() == 2 else truth)).sum()
+        stats["seen"] += out.shape[0]
 
 
 def train_step(args, model, batch, device, optimizer, scheduler, criterion, epoch, step_counter,
@@ -578,7 +602,7 @@ def train_step(args, model, batch, device, optimizer, scheduler, criterion, epoc
             sync.attach()
         sync.pack()
         sync.reduce_and_bind()
-    if args.grad_clip and not isinstance(optimizer, ClipAdam):      # ClipAdam clips in its kernel
+    if clips_outside_optimizer(args, optimizer):
         nn.utils.clip_grad_value_([p for p in model.parameters() if p.grad is not None],
                                   clip_value=args.grad_clip)
     reseed_device_rng(args, device)
@@ -588,11 +612,42 @@ def train_step(args, model, batch, device, optimizer, scheduler, criterion, epoc
         scheduler.step()
     step_counter.add()
     if stats is not None:
-        with torch.no_grad():
-            stats["loss_sum"] += loss.detach()
-            stats["hits"] += (out.argmax(1) == target_ohe.argmax(1)).sum()
-            stats["seen"] += out.shape[0]
+        add_stats(stats, loss.detach(), out, target_ohe)
     return loss.detach()
+
+
+class _StaticBlock:
+    """Everything small the captured step reads and the host decides per step, in ONE static block
+    of float32 words: ``dev`` on the device and ``host``, its image in host memory.  A plain splice
+    carries the image with its index block (``pcgmix_ctx_set_payload``: no copy of its own), other
+    steps upload it with one H2D.  Layout, the same in both copies:
+
+        words 0-1     dropout key (bits)
+        words 2-3     unused
+        words 4-11    the eight Adam scalars (``ClipAdam.next_hyper``)
+        from word 12  the class labels, one byte each, padded to a 16-byte granule
+        behind them   the float targets (B, classes), padded to 4 words
+
+    ``key``, ``hyper``, ``labels`` and ``targets`` are views of ``dev``; ``host_key`` ... of ``host``."""
+
+    def __init__(self, batch_size: int, num_classes: int, device):
+        self.shape = (batch_size, num_classes)
+        self.targets_at = 12 + (batch_size + 15) // 16 * 4       # word offset of the float targets
+        self.dev = torch.zeros(self.targets_at + (batch_size * num_classes + 3) // 4 * 4, device=device)
+        self.host = np.zeros(self.dev.numel(), dtype=np.float32)
+        self.key, self.hyper, self.labels, self.targets = self._views(self.dev, torch.int32, torch.uint8)
+        self.host_key, self.host_hyper, self.host_labels, self.host_targets = \
+            self._views(self.host, np.uint32, np.uint8)
+        self.targets[:, 0] = 1                                 # one-hot rows until a step's own targets arrive
+
+    def _views(self, words, key_dtype, byte_dtype):
+        B, classes = self.shape
+        return (words[0:2].view(key_dtype), words[4:12], words[12:self.targets_at].view(byte_dtype)[:B],
+                words[self.targets_at:self.targets_at + B * classes].reshape(B, classes))
+
+    def payload_bytes(self, labels_mode: bool) -> int:
+        """What a step sends: up to the end of the label bytes, or the whole block."""
+        return self.targets_at * 4 if labels_mode else self.host.nbytes
 
 
 class GraphedTrainStep:
@@ -617,77 +672,73 @@ class GraphedTrainStep:
 
     def __init__(self, args, model, optimizer, scheduler, criterion, device, batch_size, channels,
                  sig_len, sync: Optional[FlatGradSync] = None):
-        if args.dataset in SPECTROGRAM_DATASETS:
-            raise NotImplementedError("graphed step is wired for the 1D path")
-        if latent_method(args):
-            raise NotImplementedError(LATENT_GRAPH_MESSAGE)
-        if cutpaste_method(args):
-            raise NotImplementedError(cutpaste_graph_message(args))
+        refusal = capture_refusal(args)
+        if refusal is not None:
+            raise NotImplementedError(refusal)
         self.args, self.model, self.opt, self.sched = args, model, optimizer, scheduler
         self.ce = criterion.CEloss if hasattr(criterion, "CEloss") else criterion
         self.es = getattr(criterion, "es", None)
         self.device = device
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.x = torch.zeros(batch_size, channels, sig_len, device=device)
-        # Everything small the replay reads and the host decides per step lives in ONE static
-        # block, ``aux`` (float32 words): [0:2] dropout key (bits) | [4:12] Adam scalars |
-        # [12:12+B*classes] the float targets.  ``_payload`` is its host image; a plain splice
-        # carries it with its index block (``pcgmix_ctx_set_payload``: no copy of its own),
-        # other steps upload it with one H2D.
-        # [12:12+B/4] the class labels as bytes | then the float targets.  Hard targets (everything
-        # but '(mixAll)') reach the fused Potes head+loss as those bytes: the payload is then 48 + B
-        # bytes and travels in the splice kernel's ARGUMENTS with the index block — no copy at all
-        # in front of the replay; other models / soft targets read the float block (one H2D).
-        n_t = batch_size * args.num_classes
-        n_lab = (batch_size + 15) // 16 * 4                   # words, 16-byte granules
-        self.aux = torch.zeros(12 + n_lab + (n_t + 3) // 4 * 4, device=device)
-        self.t_u8 = self.aux[12:12 + n_lab].view(torch.uint8)[:batch_size]
-        self.t = self.aux[12 + n_lab:12 + n_lab + n_t].view(batch_size, args.num_classes)
-        self.t[:, 0] = 1
-        self._payload = np.zeros(self.aux.numel(), dtype=np.float32)
-        self._pay_key = self._payload[0:2].view(np.uint32)
-        self._pay_hyper = self._payload[4:12]
-        self._pay_lab = self._payload[12:12 + n_lab].view(np.uint8)[:batch_size]
-        self._pay_t = self._payload[12 + n_lab:12 + n_lab + n_t].reshape(batch_size, args.num_classes)
+        self.block = _StaticBlock(batch_size, args.num_classes, device)
+        self.t_u8, self.t = self.block.labels, self.block.targets
         self._rows = np.arange(batch_size)
+        # Hard targets (everything but '(mixAll)') reach the fused Potes head+loss as class bytes:
+        # the payload is then 48 + B bytes and travels in the splice kernel's ARGUMENTS with the
+        # index block — no copy at all in front of the replay; other models / soft targets read the
+        # float block (one H2D).
         self.labels_mode = bool(                               # same test as _fwd_bwd's
             isinstance(self.ce, CELoss) and not method_route(args).soft_targets
             and args.num_classes <= 255
             and fused_loss_model(model, self.ce, self.x, self.t, None) is not None)
-        self._pay_bytes = (12 + n_lab) * 4 if self.labels_mode else self._payload.nbytes
+        self._pay_bytes = self.block.payload_bytes(self.labels_mode)
         self.sync = sync
         self.bwd_seed = torch.full((), sync.backward_scale if sync else 1.0, device=device)
-        # Dropout inside a captured region costs two extra fill launches per replay (torch's
-        # graph-safe Philox state) on top of the mask kernels.  The Potes head reads random BYTES
-        # instead, from a static buffer that the conv stack's forward kernel fills as a side job
-        # (``pcgmix_potes_stack_fwd_save_f32``: a keyed counter hash).  The key is drawn on the
-        # host from torch's device generator — (seed, offset), offset advanced by 4 per step — so
-        # ``torch.cuda.manual_seed`` behaves as with nn.Dropout, the reference's reseeding before
-        # every optimiser step (``reseed_device_rng``) included.
-        self.rnd = None
-        inner = model.module if hasattr(model, "module") else model
-        if isinstance(inner, models.CNN_potes) and device.type == "cuda":
-            K = inner.dimreduc.in_features
-            drop = inner.cnn1[1][3] if len(inner.cnn1[1]) > 3 else None
-            n_rnd = models.head_dropout_bytes(batch_size, K, float(drop.p) if drop else 0.0)
-            self.rnd = torch.empty((n_rnd + 15) // 16 * 16, dtype=torch.uint8, device=device)
-            inner.dropout_bytes = self.rnd
-            inner.dropout_key = self.aux[0:2].view(torch.int32)
+        self.rnd = self._dropout_buffer(batch_size)
         # The optimiser update is the graph's last node when nothing has to happen between
         # backward and update (no gradient all-reduce) and the optimiser can read its scalars
-        # from ``aux`` (ClipAdam).
+        # from the static block (ClipAdam).
         self.adam_in_graph = isinstance(optimizer, ClipAdam) and optimizer.can_capture() \
             and device.type == "cuda"
         self.graph_update = None        # with a sync: the update as a second graph behind the all-reduce
-        # The warm-up passes run the network on the all-zero placeholder batch: they must leave no
-        # trace.  Weights are not updated (no optimiser step); BatchNorm running statistics and
-        # num_batches_tracked, and the device RNG stream the dropout masks come from, are put
-        # back afterwards, so a graphed run starts from exactly the state an eager run starts from.
-        buffers = [(b, b.detach().clone()) for b in model.buffers()]
+        self._warm_up()
+        tape, fold = self._capture()
+        self._adopt_tape(tape, fold)
+        if self.adam_in_graph and sync is not None:
+            self._capture_update_graph()
+
+    def _dropout_buffer(self, batch_size):
+        """Dropout inside a captured region costs two extra fill launches per replay (torch's
+        graph-safe Philox state) on top of the mask kernels.  The Potes head reads random BYTES
+        instead, from a static buffer that the conv stack's forward kernel fills as a side job
+        (``pcgmix_potes_stack_fwd_save_f32``: a keyed counter hash).  The key is drawn on the host
+        from torch's device generator — (seed, offset), offset advanced by 4 per step — so
+        ``torch.cuda.manual_seed`` behaves as with nn.Dropout, the reference's reseeding before
+        every optimiser step (``reseed_device_rng``) included.  Returns that buffer (handed to the
+        model with the key's device words), or None for another model."""
+        inner = self.model.module if hasattr(self.model, "module") else self.model
+        if not (isinstance(inner, models.CNN_potes) and self.device.type == "cuda"):
+            return None
+        K = inner.dimreduc.in_features
+        drop = inner.cnn1[1][3] if len(inner.cnn1[1]) > 3 else None
+        n_rnd = models.head_dropout_bytes(batch_size, K, float(drop.p) if drop else 0.0)
+        rnd = torch.empty((n_rnd + 15) // 16 * 16, dtype=torch.uint8, device=self.device)
+        inner.dropout_bytes = rnd
+        inner.dropout_key = self.block.key
+        return rnd
+
+    def _warm_up(self):
+        """Three passes on the all-zero placeholder batch, on a side stream: they must leave no
+        trace.  Weights are not updated (no optimiser step); BatchNorm running statistics and
+        num_batches_tracked, and the device RNG stream the dropout masks come from, are put back
+        afterwards, so a graphed run starts from exactly the state an eager run starts from."""
+        import warnings
+        device, sync = self.device, self.sync
+        buffers = [(b, b.detach().clone()) for b in self.model.buffers()]
         rng = torch.cuda.get_rng_state(device)
         side = torch.cuda.Stream(device)
         side.wait_stream(torch.cuda.current_stream(device))
-        import warnings
         warn_always = torch.is_warn_always_enabled()
         torch.set_warn_always(True)                     # the stream-mismatch warning is a warn-once
         try:
@@ -728,13 +779,19 @@ class GraphedTrainStep:
                 b.copy_(saved)
         torch.cuda.set_rng_state(rng, device)
         self.opt.zero_grad(set_to_none=True)
+
+    def _capture(self):
+        """Capture forward + loss + backward (+ the update when ClipAdam is the last node) into
+        ``self.graph``.  Returns ``(tape, fold)``: the library launches recorded on the way (or
+        None) and the conv stack's deferred-reduction record (or None)."""
+        from . import _lib
+        sync = self.sync
         if sync is not None and sync.world > 1:
             # no collective may be in flight while the graph is captured, and every rank must
             # capture (or fail) together
-            torch.cuda.synchronize(device)
+            torch.cuda.synchronize(self.device)
             sync.dist.barrier()
         self.graph = torch.cuda.CUDAGraph()
-        # thread_local: HIP calls of other threads (RCCL's watchdog) must not abort the capture
         # One rank, ClipAdam as the graph's last node: the conv stack's gradient reduction moves
         # into the optimiser launch (models.PotesStackFunction.defer_reduce).
         fold = {} if (self.adam_in_graph and sync is None
@@ -745,20 +802,25 @@ class GraphedTrainStep:
         # current stream instead of replaying the hipGraph — the graph's launch leaves ~5 us of idle
         # GPU per step that back-to-back kernel launches do not (130.8 -> 125.7 us,
         # profiles/probes/tape_vs_graph.py).  The graph object stays: it owns the buffers.
-        from . import _lib
         want_tape = (self.use_tape and fold is not None and self.labels_mode
-                     and isinstance(model, models.CNN_potes) and os.environ.get("PCGMIX_NO_TAPE") is None)
+                     and isinstance(self.model, models.CNN_potes)
+                     and os.environ.get("PCGMIX_NO_TAPE") is None)
         tape = [] if want_tape else None
+        # thread_local: HIP calls of other threads (RCCL's watchdog) must not abort the capture
         with _lib.capture_without_gc(), torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
             models.PotesStackFunction.defer_reduce = fold
             _lib.TAPE = tape
             try:
                 self.loss, self.out = self._fwd_bwd()
                 if self.adam_in_graph and sync is None:
-                    self.opt.capture_update(self.aux[4:12], deferred=fold)
+                    self.opt.capture_update(self.block.hyper, deferred=fold)
             finally:
                 models.PotesStackFunction.defer_reduce = None
                 _lib.TAPE = None
+        return tape, fold
+
+    def _adopt_tape(self, tape, fold) -> None:
+        """``self.tape``: the recorded launches when they are the whole capture, else None."""
         self.tape = None
         if tape is not None and [t[0] for t in tape] == list(self._TAPE_LAUNCHES) \
                 and self._tape_covers_capture(tape, fold):
@@ -767,16 +829,18 @@ class GraphedTrainStep:
             # (a second slot of PipelinedTrainStep), a graph node would have copied them too
             snap = lambda v: type(v)(*v) if isinstance(v, ctypes.Array) else v      # noqa: E731
             self.tape = [(name, fn, tuple(snap(v) for v in a[:-1])) for name, fn, a in tape]
-        if self.adam_in_graph and sync is not None:
-            # N > 1: [forward + backward + pack] | one eager all-reduce | [clip + Adam].  The update
-            # reads the averaged gradients through views of the flat buffer and its eight scalars
-            # from ``aux`` — an N-rank step issues exactly the launches of the one-rank step plus
-            # the collective, and no Python optimiser code runs between them.
-            for p, v in zip(sync.params, sync.views):
-                p.grad = v
-            self.graph_update = torch.cuda.CUDAGraph()
-            with _lib.capture_without_gc(), torch.cuda.graph(self.graph_update, capture_error_mode="thread_local"):
-                self.opt.capture_update(self.aux[4:12])
+
+    def _capture_update_graph(self) -> None:
+        """N > 1: [forward + backward + pack] | one eager all-reduce | [clip + Adam].  The update
+        reads the averaged gradients through views of the flat buffer and its eight scalars from
+        the static block — an N-rank step issues exactly the launches of the one-rank step plus
+        the collective, and no Python optimiser code runs between them."""
+        from . import _lib
+        for p, v in zip(self.sync.params, self.sync.views):
+            p.grad = v
+        self.graph_update = torch.cuda.CUDAGraph()
+        with _lib.capture_without_gc(), torch.cuda.graph(self.graph_update, capture_error_mode="thread_local"):
+            self.opt.capture_update(self.block.hyper)
 
     def _tape_covers_capture(self, tape, fold) -> bool:
         """The tape replaces the graph only if the five recorded launches ARE the capture: no
@@ -816,19 +880,20 @@ class GraphedTrainStep:
         loss.backward(self.bwd_seed)
         if self.sync is not None and self.sync.params is not None:
             self.sync.pack()
-        elif self.args.grad_clip and not isinstance(self.opt, ClipAdam):
+        elif clips_outside_optimizer(self.args, self.opt):
             nn.utils.clip_grad_value_(self.params, clip_value=self.args.grad_clip)
         return loss.detach(), out.detach()
 
     def _next_key(self) -> None:
         """This step's dropout key from torch's device generator (host only, no launch)."""
         z = models.next_dropout_key(self.device)
-        self._pay_key[0] = z & 0xFFFFFFFF
-        self._pay_key[1] = z >> 32
+        self.block.host_key[0] = z & 0xFFFFFFFF
+        self.block.host_key[1] = z >> 32
 
-    def step(self, batch, epoch, step_counter, stats: Optional[dict] = None):
+    def step(self, batch, epoch, step_counter, stats: Optional[dict] = None, next_batch=None):
         """One training step: ``prepare`` (augmentation into the static input, payload) then
-        ``launch`` (replay, optimiser, scheduler, counters) on the current stream."""
+        ``launch`` (replay, optimiser, scheduler, counters) on the current stream.  ``next_batch``
+        is ``PipelinedTrainStep.step``'s lookahead: accepted and unused, one call form for both."""
         self.prepare(batch, epoch, step_counter)
         return self.launch(step_counter, stats)
 
@@ -836,15 +901,14 @@ class GraphedTrainStep:
         """First half of a step, everything in front of the replay: the host image of the static
         block (targets, dropout key, Adam scalars — read from generator / optimiser state as the
         PREVIOUS step's ``launch`` left it, so prepare(k+1) must follow launch(k) on the host) and
-        the augmentation launches, which write this object's static input and ``aux`` on the
+        the augmentation launches, which write this object's static input and block on the
         CURRENT stream.  ``PipelinedTrainStep`` runs it on a side stream for batch k+1 while the
         graph of batch k replays."""
         from . import hostprep, _lib, saliency as _saliency
         data, target, frames, wav, _sq, _idx = batch
         if self.es is not None and epoch > self.es:
             raise NotImplementedError("SELC phase is not captured; use train_step")
-        args = self.args
-        self._batch_size = int(data.shape[0])
+        args, block = self.args, self.block
         data = data.to(self.device, non_blocking=True)
         frames_np = augmentations._as_numpy_frames(frames)
         B, C, T = data.shape
@@ -852,20 +916,20 @@ class GraphedTrainStep:
         # host image of the static block: one-hot float targets, dropout key, Adam scalars
         labels_np = target.numpy() if not target.is_cuda else target.cpu().numpy()
         if self.labels_mode:
-            self._pay_lab[:] = labels_np
+            block.host_labels[:] = labels_np
         else:
-            self._pay_t.fill(0.0)
-            self._pay_t[self._rows, labels_np] = 1.0
+            block.host_targets.fill(0.0)
+            block.host_targets[self._rows, labels_np] = 1.0
         if self.rnd is not None and self.model.training:
             self._next_key()
         if self.adam_in_graph:
-            self.opt.next_hyper(self._pay_hyper)
+            self.opt.next_hyper(block.host_hyper)
         recipe = hostprep.plain_recipe(args.method, False)
         srec = hostprep.salopt_recipe(args.method) if recipe is None else None
         lib, ctx = _lib.load(), augmentations.step_context(data.device.index)
-        _lib.check(lib.pcgmix_ctx_set_payload(ctx, self._payload.ctypes.data, self._pay_bytes,
-                                              self.aux.data_ptr()), "pcgmix_ctx_set_payload")
-        plan = hostprep.MixPlan(fired=False)
+        _lib.check(lib.pcgmix_ctx_set_payload(ctx, block.host.ctypes.data, self._pay_bytes,
+                                              block.dev.data_ptr()), "pcgmix_ctx_set_payload")
+        plan, t_ohe = hostprep.MixPlan(fired=False), None
         if recipe is not None and B > 0:                # plain splice: one library call
             fired = augmentations.gate_passes(recipe, args.method, step, data.device.index)
             if fired:                                   # ... which carries the payload along
@@ -892,8 +956,8 @@ class GraphedTrainStep:
             if fired:
                 sal = None
                 if plan.salopt_mode is not None:        # salopt with '(samePCG)' & co.: general path
-                    t_dev = F.one_hot(target, args.num_classes).to(self.device, non_blocking=True)
-                    sal = _saliency.get_saliency_maps(args, self.device, data, t_dev, frames_np)
+                    t_ohe = F.one_hot(target, args.num_classes).to(self.device, non_blocking=True)
+                    sal = _saliency.get_saliency_maps(args, self.device, data, t_ohe, frames_np)
                 augmentations.apply_plan(plan, data, frames_np, sal, out=self.x)
         if not fired:
             self.x.copy_(data, non_blocking=True)
@@ -901,13 +965,13 @@ class GraphedTrainStep:
         _lib.check(lib.pcgmix_ctx_flush_payload(
             ctx, torch.cuda.current_stream(self.device).cuda_stream), "pcgmix_ctx_flush_payload")
         if plan.fired and plan.mix_all:                 # float blend of the one-hot rows
-            t_ohe = F.one_hot(target, args.num_classes).to(self.device, non_blocking=True)
+            if t_ohe is None:
+                t_ohe = F.one_hot(target, args.num_classes).to(self.device, non_blocking=True)
             self.t.copy_(augmentations.blend_targets(t_ohe, plan))
 
     def launch(self, step_counter, stats: Optional[dict] = None):
         """Second half: replay the captured forward + backward (+ update), the gradient all-reduce
         and update graph under torch.distributed, scheduler, step counter, statistics."""
-        B = self._batch_size
         if self.tape is not None:
             import ctypes
             st = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -925,18 +989,14 @@ class GraphedTrainStep:
         elif not self.adam_in_graph:
             if self.sync is not None:
                 self.sync.reduce_and_bind()
-                if self.args.grad_clip and not isinstance(self.opt, ClipAdam):
+                if clips_outside_optimizer(self.args, self.opt):
                     nn.utils.clip_grad_value_(self.sync.params, clip_value=self.args.grad_clip)
             self.opt.step()
         if self.sched is not None:
             self.sched.step()
         step_counter.add()
         if stats is not None:
-            with torch.no_grad():
-                stats["loss_sum"] += self.loss
-                truth = self.t_u8 if self.labels_mode else self.t.argmax(1)
-                stats["hits"] += (self.out.argmax(1) == truth).sum()
-                stats["seen"] += B
+            add_stats(stats, self.loss, self.out, self.t_u8 if self.labels_mode else self.t)
         return self.loss
 
 
@@ -958,7 +1018,7 @@ class PipelinedTrainStep:
 
     Host order is unchanged — prepare(k+1) follows launch(k), so dropout keys, Adam scalars,
     scheduler and step counter advance exactly as in the sequential loop — only the STREAM of the
-    augmentation launches differs.  Buffer hazards: slot s's static input / ``aux`` are rewritten
+    augmentation launches differs.  Buffer hazards: slot s's static input / block are rewritten
     by prepare(k+2) only after the replay of batch k (same slot) has finished (event), and a replay
     waits for its slot's prepare (event).
 
@@ -1034,6 +1094,13 @@ class PipelinedTrainStep:
         return loss
 
 
+def captured_step_class(args, pipeline: bool = True):
+    """Two pipelined slots for the saliency-guided methods (297 -> 258 us per step), one slot for
+    the rest (plain splice: 148 -> 166 us if pipelined, profiles/r3_pipeline_ab.txt); the reasons
+    are in ``PipelinedTrainStep``'s docstring."""
+    return PipelinedTrainStep if pipeline and "(salopt" in args.method else GraphedTrainStep
+
+
 def _no_epoch_step():
     return None
 
@@ -1059,24 +1126,18 @@ def _epoch_graphed_step(args, model, optimizer, scheduler, criterion, device, ep
     what ``GraphedTrainStep`` needs; the graph is built at the first batch and kept for as long as
     model, optimiser, scheduler, criterion, method and batch shape stay the same objects/values
     (the reference creates them once per run, train_model.py:293-410).  ``args.hipgraph = False``
-    switches it off.  Eager: CPU, spectrogram datasets, 1D latentmixup (per-step partners and lambda
-    have no slot in the capture), wrapped (DataParallel/DDP) models, a
-    criterion other than ``SELCLoss``, epochs past its turning point, an active process group
-    (use ``train_model()`` / ``FlatGradSync`` there)."""
+    switches it off.  Eager: CPU, whatever ``capture_refusal`` names, wrapped (DataParallel/DDP)
+    models, a criterion other than ``SELCLoss``, epochs past its turning point, an active process
+    group (use ``train_model()`` / ``FlatGradSync`` there)."""
     if not getattr(args, "hipgraph", True) or device.type != "cuda":
         return None
-    if args.dataset in SPECTROGRAM_DATASETS or not isinstance(criterion, SELCLoss):
-        return None
-    if latent_method(args):                 # per-step partners and lambda: not captured (train_step)
-        return None
-    if cutpaste_method(args):               # per-step segment tables: not captured (train_step)
+    if capture_refusal(args) is not None or not isinstance(criterion, SELCLoss):
         return None
     if not isinstance(model, (models.CNN_potes, models.ResNet9_myrtle)):
         return None
     if epoch > criterion.es or getattr(args, "num_epochs", epoch) > criterion.es:
         return None
-    import torch.distributed as dist
-    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    if rank_and_world()[1] > 1:
         return None
     data = batch[0]
     if data.dim() != 3:
@@ -1086,12 +1147,47 @@ def _epoch_graphed_step(args, model, optimizer, scheduler, criterion, device, ep
     hit = model.__dict__.get("_pcgmix_epoch_step")      # kept ON the model: dies with it (a module-
     if hit is None or hit.key != key:                   # level table would keep model and graph alive)
         B, C, T = data.shape
-        # saliency-guided methods: two captured slots, the augmentation of the next batch on a side
-        # stream under the graph of this one (+15 % at BASELINE config 3); one slot otherwise
-        cls = PipelinedTrainStep if "(salopt" in args.method else GraphedTrainStep
+        cls = captured_step_class(args)
         hit = _EpochStep(key, cls(args, model, optimizer, scheduler, criterion, device, B, C, T))
         model.__dict__["_pcgmix_epoch_step"] = hit
     return hit.step
+
+
+def _run_epoch(args, model, batches, device, optimizer, scheduler, criterion, epoch, step_counter,
+               captured, eager, lrs: Optional[list] = None):
+    """The batches of one epoch (train_model.py:496-586) for ``train_epoch`` and ``train_model``.
+    ``captured(...same arguments as _epoch_graphed_step...)`` gives the captured step or None at the
+    first batch; it runs every batch of its static shape, with one batch of lookahead.  ``eager``
+    (``train_step`` or None) runs the others; None makes such a batch an error (``train_model``
+    under a captured step: an eager step there would skip ``FlatGradSync``'s gradient averaging).
+    ``lrs`` collects the learning rate in front of every step.  Returns (stats, steps run)."""
+    model.train()
+    torch.manual_seed(args.seed * 635410 + step_counter.count)      # :497 fixes this epoch's shuffle
+    stats = {"loss_sum": torch.zeros((), device=device),
+             "hits": torch.zeros((), device=device, dtype=torch.long), "seen": 0}
+    n_batches, graphed = 0, None
+
+    def fits(b):
+        return tuple(b[0].shape) == tuple(graphed.x.shape)
+
+    for batch, nxt in PipelinedTrainStep.pairs(batches):            # one batch of lookahead
+        if lrs is not None:
+            lrs.append(optimizer.param_groups[0]["lr"])
+        if n_batches == 0:
+            graphed = captured(args, model, optimizer, scheduler, criterion, device, epoch, batch)
+        if graphed is not None and fits(batch):
+            last = not step_counter.count + 1 < getattr(args, "num_steps", float("inf"))   # :584-586
+            ahead = nxt if (not last and nxt is not None and fits(nxt)) else None
+            graphed.step(batch, epoch, step_counter, stats, next_batch=ahead)
+        elif eager is not None:
+            eager(args, model, batch, device, optimizer, scheduler, criterion, epoch, step_counter, stats)
+        else:
+            raise RuntimeError(f"batch of shape {tuple(batch[0].shape)} does not fit the captured "
+                               f"step's {tuple(graphed.x.shape)}")
+        n_batches += 1
+        if not step_counter.count < args.num_steps:                  # :584-586
+            break
+    return stats, n_batches
 
 
 def train_epoch(args, model, train_loader, device, optimizer, scheduler, criterion, epoch,
@@ -1100,30 +1196,9 @@ def train_epoch(args, model, train_loader, device, optimizer, scheduler, criteri
     On a GPU the step is the captured one (``_epoch_graphed_step``): the same values as
     ``train_step`` at three times its rate; batches of another shape (a loader without
     drop_last) fall back to the eager step."""
-    model.train()
-    torch.manual_seed(args.seed * 635410 + step_counter.count)      # :497 fixes this epoch's shuffle
-    stats = {"loss_sum": torch.zeros((), device=device), "hits": torch.zeros((), device=device,
-                                                                         dtype=torch.long), "seen": 0}
-    lrs, n_batches = [], 0
-    graphed = None
-    for batch, nxt in PipelinedTrainStep.pairs(train_loader):          # one batch of lookahead
-        lrs.append(optimizer.param_groups[0]["lr"])
-        if n_batches == 0:
-            graphed = _epoch_graphed_step(args, model, optimizer, scheduler, criterion, device, epoch, batch)
-        if graphed is not None and tuple(batch[0].shape) == tuple(graphed.x.shape):
-            if isinstance(graphed, PipelinedTrainStep):
-                last = not step_counter.count + 1 < getattr(args, "num_steps", float("inf"))   # :584-586
-                ahead = nxt if (not last and nxt is not None
-                                and tuple(nxt[0].shape) == tuple(graphed.x.shape)) else None
-                graphed.step(batch, epoch, step_counter, stats, next_batch=ahead)
-            else:
-                graphed.step(batch, epoch, step_counter, stats)
-        else:
-            train_step(args, model, batch, device, optimizer, scheduler, criterion, epoch,
-                       step_counter, stats)
-        n_batches += 1
-        if not step_counter.count < args.num_steps:                  # :584-586
-            break
+    lrs = []
+    stats, n_batches = _run_epoch(args, model, train_loader, device, optimizer, scheduler, criterion,
+                                  epoch, step_counter, _epoch_graphed_step, train_step, lrs)
     loss = float(stats["loss_sum"]) / max(1, n_batches)              # the only host syncs
     acc = float(stats["hits"]) / max(1, stats["seen"])
     return loss, acc, lrs
@@ -1250,21 +1325,20 @@ def train_model(args, dataset, device, use_graph: bool = True, log=print, pipeli
     import random
     import time as _time
 
-    import torch.distributed as dist
     from . import dataloader_physionet as dlp
     from . import saliency as _sal
 
     spectro = args.dataset == "PhysioNet(spec128)"
     if args.dataset != "PhysioNet" and not spectro:
         raise NotImplementedError("train_model drives the PhysioNet time-series and spectrogram paths")
-    if spectro and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    rank, world = rank_and_world()
+    if spectro and world > 1:
         from . import hostprep
         if hostprep.select_method(args.method, is2d=True) == "latentmixup":
             # two half passes of the DDP-wrapped model in one iteration (augmentations2d.py:523 and
             # the training step's 'second' pass): refused rather than reduced twice or not at all
             raise NotImplementedError(LATENT_DDP_MESSAGE)
-    if not spectro and latent_method(args) and dist.is_available() and dist.is_initialized() \
-            and dist.get_world_size() > 1:
+    if not spectro and latent_method(args) and world > 1:
         raise NotImplementedError(LATENT_DDP_MESSAGE)
     seed_fix = 4                                                   # :217
     args.seed_fix = seed_fix
@@ -1284,27 +1358,21 @@ def train_model(args, dataset, device, use_graph: bool = True, log=print, pipeli
     args.sig_len = int(train_loader.data.shape[-1])
     torch.manual_seed(seed_fix)                                    # :293 initial weights
     model = build_model(args).to(device)
-    distributed = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-    rank, world = (dist.get_rank(), dist.get_world_size()) if distributed else (0, 1)
     args.num_steps = args.num_epochs * (len(train_loader.dataset) // args.batch_size)   # :390
     criterion = SELCLoss(train_labels, args.num_classes, es=selc_turning_point(args), device=device)
     # (the spectrogram step is 80 ms of MIOpen convolutions: nothing for a graph to win, it stays eager)
-    graphable = use_graph and device.type == "cuda" and args.num_epochs <= criterion.es and not spectro \
-        and not latent_method(args) and not cutpaste_method(args)   # eager step (not wired into the capture)
+    graphable = use_graph and device.type == "cuda" and args.num_epochs <= criterion.es \
+        and capture_refusal(args) is None
     if not graphable:
         model = wrap_distributed(model, device)
     optimizer, scheduler = make_optimizer(args, model)
     step_counter = step_counter_class()
     graphed = None
     if graphable:
-        # Saliency-guided methods: two captured slots, the augmentation of batch k+1 (as long as the
-        # training graph itself) overlaps the graph of batch k: 297 -> 258 us per step.  For the plain
-        # splice (10 us) the cross-stream hand-overs cost more than the overlap gains (148 -> 166 us,
-        # profiles/r3_pipeline_ab.txt): one slot.
-        cls = PipelinedTrainStep if pipeline and "(salopt" in args.method else GraphedTrainStep
-        graphed = cls(args, model, optimizer, scheduler, criterion, device,
-                      args.batch_size // world, args.num_channels, args.sig_len,
-                      sync=FlatGradSync(model, device) if distributed else None)
+        graphed = captured_step_class(args, pipeline)(
+            args, model, optimizer, scheduler, criterion, device,
+            args.batch_size // world, args.num_channels, args.sig_len,
+            sync=FlatGradSync(model, device) if world > 1 else None)
     performance = performance_metrics_class()                                           # :421
     perf = performance.dict
     plot_epochs = set(np.linspace(1, args.num_epochs, 11).astype("int").tolist())       # :424
@@ -1312,25 +1380,10 @@ def train_model(args, dataset, device, use_graph: bool = True, log=print, pipeli
     t_sum = 0.0
     for epoch in range(1, args.num_epochs + 1):
         t0 = _time.time()
-        model.train()
-        torch.manual_seed(args.seed * 635410 + step_counter.count)                      # :497
-        stats = {"loss_sum": torch.zeros((), device=device),
-                 "hits": torch.zeros((), device=device, dtype=torch.long), "seen": 0}
-        n_batches = 0
-        shard = (lambda b: shard_batch(b, rank, world)) if distributed else (lambda b: b)
-        pairs = PipelinedTrainStep.pairs(shard(b) for b in train_loader)
-        for batch, nxt in pairs:
-            if isinstance(graphed, PipelinedTrainStep):
-                last = not step_counter.count + 1 < args.num_steps        # :584-586 stops behind this one
-                graphed.step(batch, epoch, step_counter, stats, next_batch=None if last else nxt)
-            elif graphed is not None:
-                graphed.step(batch, epoch, step_counter, stats)
-            else:
-                train_step(args, model, batch, device, optimizer, scheduler, criterion, epoch,
-                           step_counter, stats)
-            n_batches += 1
-            if not step_counter.count < args.num_steps:
-                break
+        batches = (shard_batch(b, rank, world) for b in train_loader) if world > 1 else train_loader
+        stats, n_batches = _run_epoch(
+            args, model, batches, device, optimizer, scheduler, criterion, epoch, step_counter,
+            lambda *_: graphed, train_step if graphed is None else None)
         t_sum += _time.time() - t0
         if epoch in plot_epochs:
             performance.add("epochs", epoch)                                            # :447-455

@@ -500,7 +500,8 @@ def test_train_epoch_pipelines_the_saliency_guided_step(device, tmp_path):
 def test_direct_launches_equal_the_graph_replay(method, device, tmp_path):
     """The fused Potes step issued as its five recorded library launches (the default) == the same
     step replayed as a hipGraph (``GraphedTrainStep.use_tape = False``): every loss and every
-    parameter bit for bit over 8 steps, dropout on.  Another model keeps the graph."""
+    parameter bit for bit over 8 steps, dropout on.  ``next_batch`` (the pipelined step's lookahead)
+    is accepted and changes nothing.  Another model keeps the graph."""
     B, T = 32, 2500
     batches = []
     for i in range(8):
@@ -510,9 +511,9 @@ def test_direct_launches_equal_the_graph_replay(method, device, tmp_path):
     res = {}
     old = tm.GraphedTrainStep.use_tape
     try:
-        for use_tape in (True, False):
+        for use_tape, ahead in ((True, False), (False, False), (True, True)):
             tm.GraphedTrainStep.use_tape = use_tape
-            args = TC.salopt_traj_args(str(tmp_path / str(use_tape)))
+            args = TC.salopt_traj_args(str(tmp_path / f"{use_tape}{ahead}"))
             args.method, args.batch_size, args.seed_fix, args.num_steps = method, B, 4, 8
             torch.manual_seed(7)
             net = tm.build_model(args).to(device).train()
@@ -524,14 +525,19 @@ def test_direct_launches_equal_the_graph_replay(method, device, tmp_path):
             assert (g.tape is not None) == use_tape
             if use_tape:
                 assert [t[0] for t in g.tape] == list(tm.GraphedTrainStep._TAPE_LAUNCHES)
-            losses = [g.step(b, 1, sc).clone() for b in batches]
+            if ahead:
+                losses = [g.step(b, 1, sc, None, next_batch=b).clone() for b in batches]
+            else:
+                losses = [g.step(b, 1, sc).clone() for b in batches]
             torch.cuda.synchronize()
-            res[use_tape] = (torch.stack(losses).cpu(), [p.detach().cpu().clone() for p in net.parameters()])
+            res[use_tape, ahead] = (torch.stack(losses).cpu(),
+                                    [p.detach().cpu().clone() for p in net.parameters()])
     finally:
         tm.GraphedTrainStep.use_tape = old
-    assert torch.equal(res[True][0], res[False][0]), (res[True][0], res[False][0])
-    for a, b in zip(res[True][1], res[False][1]):
-        assert torch.equal(a, b)
+    for other in ((False, False), (True, True)):
+        assert torch.equal(res[True, False][0], res[other][0]), (other, res[True, False][0], res[other][0])
+        for a, b in zip(res[True, False][1], res[other][1]):
+            assert torch.equal(a, b)
     # ResNet9: torch/MIOpen kernels inside the capture — the graph is replayed
     args = TC.salopt_traj_args(str(tmp_path / "r9"))
     args.method, args.model, args.batch_size = "durratiomixup", "resnet9", 4
