@@ -729,6 +729,48 @@ int pcgmix_soft_ce_bwd_f32(const float* logits, const float* target, const float
                            float* dlogits, int B, int C, pcgmix_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * SELC loss past its turning point (train_model.py:56-80, SELCLoss.forward, 'train', epoch > es):
+ *   pred = softmax(logits)
+ *   soft_labels[index] = m * soft_labels[index] + (1 - m) * pred.detach()      (side effect)
+ *   loss = mean_b( -sum_c log(pred[b,c]) * soft_labels[index[b], c] )           [device]
+ *
+ * pcgmix_selc_fwd_f32: logits (B,C) float32; index (B) int64 on the device; soft_labels (N,C)
+ * float32, read and written; rows (B,C) out = the updated soft rows, kept for the backward; loss
+ * = device scalar.  One launch; the batch mean is summed in a fixed order (same inputs, same bits).
+ *   keep = (float)m and take = (float)(1.0 - m) with the subtraction done in DOUBLE on the host:
+ *   that is how torch casts the Python scalars of `m * a + (1 - m) * b`.  1.f - 0.9f in float is a
+ *   different number (0x3DCCCCD0, not 0x3DCCCCCD).  keep*soft + take*pred is evaluated unfused.
+ *   The row loss is -sum_c logp_c * s_c with logp = z - max - log(sum exp(z - max)): a deliberate
+ *   deviation from the reference's log(softmax(z)) where pred underflows to 0 — there the reference
+ *   returns inf and a nan gradient, this stays finite.  Elsewhere the two agree to rounding.
+ *   A row whose index is outside [0,N) makes no update, gets a zero row in `rows` and contributes
+ *   zero loss and zero gradient (the mean still divides by B); nothing outside soft_labels is ever
+ *   written.  Precondition: the indices of one batch are distinct (torch's indexed assignment is
+ *   undefined otherwise too; the reference's loaders sample without replacement).
+ * pcgmix_selc_bwd_f32: dlogits[b,c] = gout[0] / B * (softmax[b,c] * sum_c' rows[b,c'] - rows[b,c]).
+ *   It reads `rows`, not soft_labels: a later step may have moved those already.
+ */
+int pcgmix_selc_fwd_f32(const float* logits, const long long* index, float* soft_labels, int N,
+                        float keep, float take, float* rows, float* loss, int B, int C,
+                        pcgmix_stream_t stream);
+int pcgmix_selc_bwd_f32(const float* logits, const float* rows, const float* gout, float* dlogits,
+                        int B, int C, pcgmix_stream_t stream);
+/* pcgmix_potes_head_loss_fwd_f32 with the SELC loss in place of CELoss: index, soft_labels, N, keep,
+ * take (as above, same rules for a bad index and for duplicates) take the place of target /
+ * target_kind; the tail kernel forms each row's target from the row's own logits and writes the
+ * soft row back.  Everything behind it — dz, small, ws, defer_finalize, and the backward
+ * pcgmix_potes_head_loss_bwd_f32 — is unchanged.  C <= 8.                                        */
+int pcgmix_potes_head_loss_selc_fwd_f32(const float* x, const uint8_t* mask1, float scale1, int thr1,
+                                        int bits1, const float* w1, const float* b1,
+                                        const uint8_t* mask2, float scale2, int thr2,
+                                        const float* w2, const float* b2, const long long* index,
+                                        float* soft_labels, int N, float keep, float take,
+                                        float* partial, float* z, float* logits, float* dz,
+                                        float* loss, float* small, float* ws, float* dw1_zero,
+                                        int defer_finalize, int B, int K, int C,
+                                        pcgmix_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * One-call step of the plain PCGmix methods (durratiomixup / durmixmagwarp, same-label partners,
  * no '(rand)', no saliency): everything augmentations.py:941, 962-977 (and :874, 906-928) do
  * between the probability gate and the returned tensor.                      [host + device]

@@ -122,6 +122,13 @@ SIGNATURES = {
                                                 _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _ptr]),
     "pcgmix_soft_ce_fwd_f32": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _ptr]),
     "pcgmix_soft_ce_bwd_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr]),
+    "pcgmix_selc_fwd_f32": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_float, _c_float, _ptr, _ptr, _c_int, _c_int,
+                                     _ptr]),
+    "pcgmix_selc_bwd_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _ptr]),
+    "pcgmix_potes_head_loss_selc_fwd_f32": (_c_int, [_ptr, _ptr, _c_float, _c_int, _c_int, _ptr, _ptr, _ptr,
+                                                     _c_float, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int,
+                                                     _c_float, _c_float] + [_ptr] * 8 +
+                                            [_c_int, _c_int, _c_int, _c_int, _ptr]),
     "pcgmix_splice_same_label_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, ctypes.c_uint64, _c_float, _ptr,
                                               _ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int,
                                               _ptr]),

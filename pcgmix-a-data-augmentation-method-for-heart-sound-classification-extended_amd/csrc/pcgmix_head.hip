@@ -20,7 +20,10 @@
 //
 // and, in front of the same backward, the fused tail + loss pair
 //   potes_tail_loss_kernel / potes_tail_loss_latent_kernel (1D latentmixup: the hidden features are
-//   blended with the partners' inside the kernel) + potes_tail_loss_finalize_kernel
+//   blended with the partners' inside the kernel) / potes_tail_loss_selc_kernel (SELCLoss past its
+//   turning point, train_model.py:56-80: the target is the row's self-ensembled soft label)
+//   + potes_tail_loss_finalize_kernel
+// and the SELC loss on its own for every other model: selc_fwd_kernel / selc_bwd_kernel
 //
 // Dropout: the caller hands over bytes (same shape as what they mask) and a threshold; an element
 // is kept iff its byte >= thr.  thr = 1 reads a 0/1 mask; thr = 256*p reads uniformly random
@@ -407,6 +410,86 @@ __global__ __launch_bounds__(256) void soft_ce_bwd_kernel(const float* __restric
     dlogits[(size_t)b * C + c] = g * (expf(x[c] - m - lse) * ts - t[c]);
 }
 
+// ------------------------------------------------------------------------------ SELC loss
+// SELCLoss past its turning point (train_model.py:56-80):
+//   pred = softmax(logits);  soft[index] = m*soft[index] + (1-m)*pred.detach();
+//   loss = mean_b(-sum_c log(pred[b,c]) * soft[index[b],c])
+// One row of it, shared by the generic kernel and the fused Potes tail: x = the row's C logits,
+// sl = its row of the soft labels (NULL: the index was outside [0,N) — no update, target 0, so the
+// row gives zero loss and zero gradient).  Writes the updated row to sl and to s[], the softmax to
+// p[] (unless NULL), and returns -sum_c logp_c * s_c with logp = x - max - log(sum): finite where pred underflows
+// (the reference's log(softmax) is -inf there).  keep*soft + take*p stays unfused (-ffp-contract=off),
+// as torch evaluates it.
+template <typename L>
+__device__ __forceinline__ float selc_row(const L& x, int C, float* __restrict__ sl, float keep,
+                                          float take, float* __restrict__ s, float* __restrict__ p) {
+  float m = x[0];
+  for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
+  float se = 0.f;
+  for (int c = 0; c < C; ++c) se += expf(x[c] - m);
+  const float lse = logf(se);
+  float rl = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float logp = x[c] - m - lse, pc = expf(logp);
+    float sc = 0.f;
+    if (sl) {
+      sc = keep * sl[c] + take * pc;
+      sl[c] = sc;
+    }
+    s[c] = sc;
+    if (p) p[c] = pc;
+    rl -= logp * sc;
+  }
+  return rl;
+}
+
+// The soft-label row of batch row b, or NULL when its index is outside [0,N).
+__device__ __forceinline__ float* selc_soft_row(const long long* __restrict__ index, int b,
+                                                float* __restrict__ soft, int N, int C) {
+  const long long idx = index[b];
+  return idx >= 0 && idx < (long long)N ? soft + (size_t)idx * C : nullptr;
+}
+
+// One block, thread t takes rows t, t+256, ... and the row losses are summed in soft_ce_fwd_kernel's
+// fixed order.  rows (B,C) = the updated soft rows (zeros for a skipped row), kept for the backward.
+__global__ __launch_bounds__(256) void selc_fwd_kernel(const float* __restrict__ logits,
+                                                       const long long* __restrict__ index,
+                                                       float* __restrict__ soft, int N, float keep,
+                                                       float take, float* __restrict__ rows,
+                                                       float* __restrict__ loss, int B, int C) {
+  __shared__ float red[4];
+  float acc = 0.f;
+  for (int b = threadIdx.x; b < B; b += 256) {
+    acc += selc_row(logits + (size_t)b * C, C, selc_soft_row(index, b, soft, N, C), keep, take,
+                    rows + (size_t)b * C, nullptr);
+  }
+  const float tot = block_sum_256(acc, red);
+  if (threadIdx.x == 0) loss[0] = tot / (float)B;
+}
+
+// dlogits[b][c] = gout / B * (softmax[b][c] * sum_c' rows[b][c'] - rows[b][c]): soft_ce_bwd_kernel
+// with the rows the forward stored as the target.
+__global__ __launch_bounds__(256) void selc_bwd_kernel(const float* __restrict__ logits,
+                                                       const float* __restrict__ rows,
+                                                       const float* __restrict__ gout,
+                                                       float* __restrict__ dlogits, int B, int C) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const float g = gout[0] / (float)B;
+  const float* x = logits + (size_t)b * C;
+  const float* t = rows + (size_t)b * C;
+  float m = x[0];
+  for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
+  float se = 0.f, ts = 0.f;
+  for (int c = 0; c < C; ++c) {
+    se += expf(x[c] - m);
+    ts += t[c];
+  }
+  const float lse = logf(se);
+  for (int c = 0; c < C; ++c)
+    dlogits[(size_t)b * C + c] = g * (expf(x[c] - m - lse) * ts - t[c]);
+}
+
 // ------------------------------------------------------------------------------ tail + loss, fused
 // potes_tail_fwd_kernel, soft_ce_fwd_kernel, soft_ce_bwd_kernel and potes_tail_bwd_kernel are four
 // launches of 4.6-7.2 us for a few KB of data; everything they compute is local to a batch row
@@ -496,6 +579,118 @@ __global__ __launch_bounds__(kTailRows* kHeadO * 4) void potes_tail_loss_kernel(
         loss_r -= (lg[t][c] - m - lse) * tg[c];
         dl[t][c] = inv_b * (expf(lg[t][c] - m - lse) * ts - tg[c]);
       }
+    } else {
+      for (int c = 0; c < C; ++c) dl[t][c] = 0.f;
+    }
+    rl[t] = loss_r;
+  }
+  __syncthreads();
+  if (q == 0) {                    // dz = (z > 0) * m2 * (dlogits W2), for d loss = 1
+    float sacc = 0.f;
+    for (int c = 0; c < C; ++c) sacc = fmaf(dl[r][c], w2[c * kHeadO + o], sacc);
+    const float d = sacc * fac[r][o];
+    dzl[r][o] = d;
+    if (row < B) dz[i] = d;
+  }
+  __syncthreads();
+  float* out = ws + (size_t)blockIdx.x * kTlStride;
+  if (t < kHeadMaxC * kHeadO) {    // dW2[c][o] contribution of these rows
+    const int c = t / kHeadO, oo = t - c * kHeadO;
+    float a = 0.f;
+    if (c < C)
+      for (int rr = 0; rr < kTailRows; ++rr) a = fmaf(dl[rr][c], h[rr][oo], a);
+    out[t] = a;
+  } else if (t < kHeadMaxC * kHeadO + kHeadMaxC) {
+    const int c = t - kHeadMaxC * kHeadO;
+    float a = 0.f;
+    if (c < C)
+      for (int rr = 0; rr < kTailRows; ++rr) a += dl[rr][c];
+    out[t] = a;
+  } else if (t < kHeadMaxC * kHeadO + kHeadMaxC + kHeadO) {
+    const int oo = t - kHeadMaxC * kHeadO - kHeadMaxC;
+    float a = 0.f;
+    for (int rr = 0; rr < kTailRows; ++rr) a += dzl[rr][oo];
+    out[t] = a;
+  } else if (t == kHeadMaxC * kHeadO + kHeadMaxC + kHeadO) {
+    out[t] = (rl[0] + rl[1]) + (rl[2] + rl[3]);
+  }
+}
+
+// ------------------------------------------------------------------------------ tail + loss, SELC
+// potes_tail_loss_kernel for SELCLoss past its turning point (train_model.py:56-80): the row's
+// target is not handed in but formed from the row's own logits — selc_row: softmax, the momentum
+// update of soft[index[row]] (written back), the loss against the updated row — and dlogits
+// follow as in the plain kernel with that row as the target.  z, logits, dz and the per-block
+// contributions are laid out as there: finalize kernel and backward follow unchanged.  A sibling,
+// not a third target kind: the plain kernel keeps its code, its name and its results.
+__global__ __launch_bounds__(kTailRows* kHeadO * 4) void potes_tail_loss_selc_kernel(
+    const float* __restrict__ partial, int KS, const float* __restrict__ b1,
+    const uint8_t* __restrict__ mask2, float scale2, int thr2, const float* __restrict__ w2,
+    const float* __restrict__ b2, const long long* __restrict__ index, float* __restrict__ soft,
+    int N, float keep, float take, float* __restrict__ z, float* __restrict__ logits,
+    float* __restrict__ dz, float* __restrict__ ws, float* __restrict__ zero, long long n_zero,
+    int B, int C, int nrb) {
+  if ((int)blockIdx.x >= nrb) {    // the other blocks clear the buffer head_bwd accumulates dW1 into
+    const int nz = (int)gridDim.x - nrb;
+    const long long per = (n_zero + nz - 1) / nz;
+    const long long lo = (long long)((int)blockIdx.x - nrb) * per;
+    const long long hi = lo + per < n_zero ? lo + per : n_zero;
+    for (long long i = lo + threadIdx.x; i < hi; i += blockDim.x) zero[i] = 0.f;
+    return;
+  }
+  __shared__ float h[kTailRows][kHeadO], fac[kTailRows][kHeadO], dzl[kTailRows][kHeadO];
+  __shared__ float lg[kTailRows][kHeadMaxC], dl[kTailRows][kHeadMaxC], rl[kTailRows];
+  const int t = threadIdx.x, q = t & 3, e = t >> 2;            // e = r * kHeadO + o
+  const int r = e / kHeadO, o = e - r * kHeadO;
+  const int row = blockIdx.x * kTailRows + r;
+  const size_t i = (size_t)(row < B ? row : 0) * kHeadO + o;
+  const size_t plane = (size_t)B * kHeadO;
+  float v = 0.f;
+  int ks = q;
+  for (; ks + 12 < KS; ks += 16) {                  // four independent loads in flight
+    const float t0 = partial[(size_t)ks * plane + i], t1 = partial[(size_t)(ks + 4) * plane + i],
+                t2 = partial[(size_t)(ks + 8) * plane + i], t3 = partial[(size_t)(ks + 12) * plane + i];
+    v += t0; v += t1; v += t2; v += t3;
+  }
+  for (; ks < KS; ks += 4) v += partial[(size_t)ks * plane + i];
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  if (q == 0) {
+    float hv = 0.f, f = 0.f;
+    if (row < B) {
+      v += b1 ? b1[o] : 0.f;
+      z[i] = v;
+      f = v > 0.f ? 1.f : 0.f;
+      if (mask2) f = (int)mask2[i] >= thr2 ? f * scale2 : 0.f;
+      hv = v * f;
+    }
+    h[r][o] = hv;
+    fac[r][o] = f;
+  }
+  __syncthreads();
+  if (t < kTailRows * C) {
+    const int rr = t / C, c = t - rr * C;
+    const int row2 = blockIdx.x * kTailRows + rr;
+    float a = 0.f;
+    if (row2 < B) {
+      a = b2 ? b2[c] : 0.f;
+#pragma unroll
+      for (int k = 0; k < kHeadO; ++k) a = fmaf(h[rr][k], w2[c * kHeadO + k], a);
+      logits[(size_t)row2 * C + c] = a;
+    }
+    lg[rr][c] = a;
+  }
+  __syncthreads();
+  if (t < kTailRows) {             // the row's SELC target, loss and dlogits
+    const int row2 = blockIdx.x * kTailRows + t;
+    float loss_r = 0.f;
+    if (row2 < B) {
+      float tg[kHeadMaxC], p[kHeadMaxC];
+      loss_r = selc_row(lg[t], C, selc_soft_row(index, row2, soft, N, C), keep, take, tg, p);
+      float ts = 0.f;
+      for (int c = 0; c < C; ++c) ts += tg[c];
+      const float inv_b = 1.f / (float)B;
+      for (int c = 0; c < C; ++c) dl[t][c] = inv_b * (p[c] * ts - tg[c]);
     } else {
       for (int c = 0; c < C; ++c) dl[t][c] = 0.f;
     }
@@ -748,6 +943,26 @@ extern "C" int pcgmix_soft_ce_bwd_f32(const float* logits, const float* target, 
   return (int)hipGetLastError();
 }
 
+extern "C" int pcgmix_selc_fwd_f32(const float* logits, const long long* index, float* soft_labels,
+                                  int N, float keep, float take, float* rows, float* loss, int B,
+                                  int C, pcgmix_stream_t stream) {
+  using namespace pcgmix;
+  if (!logits || !index || !soft_labels || !rows || !loss || N <= 0 || B <= 0 || C <= 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(selc_fwd_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                     logits, index, soft_labels, N, keep, take, rows, loss, B, C);
+  return (int)hipGetLastError();
+}
+
+extern "C" int pcgmix_selc_bwd_f32(const float* logits, const float* rows, const float* gout,
+                                  float* dlogits, int B, int C, pcgmix_stream_t stream) {
+  using namespace pcgmix;
+  if (!logits || !rows || !gout || !dlogits || B <= 0 || C <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(selc_bwd_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0,
+                     reinterpret_cast<hipStream_t>(stream), logits, rows, gout, dlogits, B, C);
+  return (int)hipGetLastError();
+}
+
 extern "C" int pcgmix_potes_head_fwd_f32(const float* x, const uint8_t* mask1, float scale1,
                                          int thr1, int bits1, const float* w1, const float* b1,
                                          const uint8_t* mask2, float scale2, int thr2,
@@ -879,6 +1094,33 @@ extern "C" int pcgmix_potes_head_loss_latent_fwd_f32(
                      lam);
   hipLaunchKernelGGL(potes_tail_loss_finalize_kernel, dim3(1), dim3(kTlStride * kTlSeg), 0, s, ws,
                      nrb, loss, small, B, C);
+  return (int)hipGetLastError();
+}
+
+extern "C" int pcgmix_potes_head_loss_selc_fwd_f32(
+    const float* x, const uint8_t* mask1, float scale1, int thr1, int bits1, const float* w1,
+    const float* b1, const uint8_t* mask2, float scale2, int thr2, const float* w2, const float* b2,
+    const long long* index, float* soft_labels, int N, float keep, float take, float* partial,
+    float* z, float* logits, float* dz, float* loss, float* small, float* ws, float* dw1_zero,
+    int defer_finalize, int B, int K, int C, pcgmix_stream_t stream) {
+  using namespace pcgmix;
+  if (!w2 || !index || !soft_labels || N <= 0 || !z || !logits || !dz || !loss || !small || !ws ||
+      B <= 0 || C <= 0 || C > kHeadMaxC || (reinterpret_cast<uintptr_t>(dz) & 15))
+    return hipErrorInvalidValue;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const hipError_t e =
+      launch_skinny_partial(x, w1, partial, B, K, kHeadO, s, mask1, scale1, thr1, bits1);
+  if (e != hipSuccess) return (int)e;
+  const int KS = pcgmix_skinny_linear_splits(B, K);
+  const int nrb = (B + kTailRows - 1) / kTailRows;
+  const long long n_zero = dw1_zero ? (long long)kHeadO * K : 0;
+  const unsigned zero_blocks = (unsigned)((n_zero + 4095) / 4096);
+  hipLaunchKernelGGL(potes_tail_loss_selc_kernel, dim3((unsigned)nrb + zero_blocks),
+                     dim3(kTailRows * kHeadO * 4), 0, s, partial, KS, b1, mask2, scale2, thr2, w2, b2,
+                     index, soft_labels, N, keep, take, z, logits, dz, ws, dw1_zero, n_zero, B, C, nrb);
+  if (!defer_finalize)
+    hipLaunchKernelGGL(potes_tail_loss_finalize_kernel, dim3(1), dim3(kTlStride * kTlSeg), 0, s, ws,
+                       nrb, loss, small, B, C);
   return (int)hipGetLastError();
 }
 

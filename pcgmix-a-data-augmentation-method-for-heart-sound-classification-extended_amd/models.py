@@ -362,7 +362,12 @@ class PotesHeadLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, w1, b1, w2, b2, target, p1, p2, training, rnd=None, defer=False,
-                latent=None):
+                latent=None, selc=None):
+        # selc = (index_dev, soft_labels, momentum): SELCLoss past its turning point
+        # (train_model.py:56-80) in place of CELoss — the tail kernel forms every row's target from
+        # the row's own logits and writes soft_labels[index] back
+        # (``pcgmix_potes_head_loss_selc_fwd_f32``); ``target`` is not read.  Not together with
+        # ``latent``.  Same launches as the plain step, same backward.
         # latent = (mix_dev, inv_dev, lam): manifold mixup at the hidden layer (1D latentmixup at
         # depth 1) inside the tail kernel — the 20 hidden features of every row, behind ReLU and
         # Dropout(p2), are blended with those of row mix[b] in front of Linear(20->C)
@@ -379,6 +384,8 @@ class PotesHeadLossFunction(torch.autograd.Function):
         lib = _lib.load()
         x = feat.contiguous()
         # hard targets may come as uint8 class labels (B,): one byte per row instead of C floats
+        if selc is not None and latent is not None:
+            raise ValueError("selc and latent exclude each other")
         hard = target.dtype == torch.uint8 and target.dim() == 1
         if hard and target.shape[0] != B:
             raise ValueError("labels do not match the batch size")
@@ -413,7 +420,27 @@ class PotesHeadLossFunction(torch.autograd.Function):
         opt = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
         defer = bool(defer and latent is None
                      and (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]))
-        if latent is not None:
+        if selc is not None:
+            index, soft, momentum = selc
+            if index.dtype != torch.int64 or index.shape != (B,) or index.device != dev \
+                    or not index.is_contiguous():
+                raise ValueError("selc: index must be a contiguous int64 (B,) tensor on the features' "
+                                 "device")
+            if soft.dtype != torch.float32 or soft.dim() != 2 or soft.shape[1] != C \
+                    or soft.device != dev or not soft.is_contiguous():
+                raise ValueError("selc: soft_labels must be a contiguous float32 (N, classes) tensor "
+                                 "on the features' device")
+            # float32(m) and float32(1.0 - m), the subtraction in double: torch's scalar rule
+            keep, take = ctypes.c_float(momentum), ctypes.c_float(1.0 - momentum)
+            _lib.check(lib.pcgmix_potes_head_loss_selc_fwd_f32(
+                x.data_ptr(), opt(mask1), ctypes.c_float(s1), thr1, bits1, w1c.data_ptr(),
+                b1.detach().data_ptr() if b1 is not None else None, opt(mask2), ctypes.c_float(s2),
+                thr2, w2c.data_ptr(), b2.detach().data_ptr() if b2 is not None else None,
+                index.data_ptr(), soft.data_ptr(), soft.shape[0], keep, take, partial.data_ptr(),
+                z.data_ptr(), logits.data_ptr(), dz.data_ptr(), loss.data_ptr(), small.data_ptr(),
+                ws.data_ptr(), opt(dw1), int(defer), B, K, C, stream),
+                "pcgmix_potes_head_loss_selc_fwd_f32")
+        elif latent is not None:
             mix_dev, inv_dev, lam = latent
             for v in (mix_dev, inv_dev):
                 if v.dtype != torch.int32 or v.shape != (B,) or v.device != dev or not v.is_contiguous():
@@ -451,7 +478,7 @@ class PotesHeadLossFunction(torch.autograd.Function):
         x, w1, dz, small, mask1, dw1 = ctx.saved_tensors
         ws, loss = ctx.deferred
         if gloss is None:                       # nothing upstream of the loss
-            return (None,) * 12
+            return (None,) * 13
         # dW1 is accumulated (two row halves, atomicAdd) into the buffer the FORWARD zeroed and is
         # returned as the gradient: a second backward over the same graph would add onto the first
         # result — which may already be p.grad — without an error.  Refuse it.
@@ -476,7 +503,7 @@ class PotesHeadLossFunction(torch.autograd.Function):
         dw2 = small_out[:C * 20].view(C, 20)
         db2 = small_out[C * 20:C * 20 + C] if ctx.has_b2 else None
         db1 = small_out[C * 20 + C:] if ctx.has_b1 else None
-        return dx, dw1, db1, dw2, db2, None, None, None, None, None, None, None
+        return dx, dw1, db1, dw2, db2, None, None, None, None, None, None, None, None
 
 
 def _potes_block(c_in: int, c_out: int, dropout: float = 0.0) -> nn.Sequential:
@@ -582,14 +609,17 @@ class CNN_potes(nn.Module):
                                        float(drop.p) if drop is not None else 0.0,
                                        float(self.dropout.p), self.training, rnd)
 
-    def loss_and_logits(self, x: torch.Tensor, target: torch.Tensor, latent=None):
+    def loss_and_logits(self, x: torch.Tensor, target: torch.Tensor, latent=None, selc=None):
         """(soft-target cross entropy, logits) of the whole network in one chain of HIP kernels
         — the conv stack, then head and loss as ONE autograd node (``PotesHeadLossFunction``).
         Needs ``_fused_head(x)``; ``target`` is the (B, classes) one-hot / soft target matrix, or
         — hard targets — a uint8 (B,) tensor of class labels.  ``latent = (mix_dev, inv_dev, lam)``:
         the step is a 1D ``latentmixup`` one at depth 1 — the hidden features are blended with the
         partners' inside the head's tail kernel (``PotesHeadLossFunction``); what
-        ``model(x, 1, 'first')`` -> blend -> ``model(h, 1, 'second')`` -> CELoss computes."""
+        ``model(x, 1, 'first')`` -> blend -> ``model(h, 1, 'second')`` -> CELoss computes.
+        ``selc = (index_dev, soft_labels, momentum)`` (not together with ``latent``): the loss is
+        SELCLoss past its turning point (train_model.py:56-80) — ``soft_labels[index_dev]`` is
+        updated in place by the tail kernel, ``target`` is not read."""
         B, C, T = x.shape
         c1, c2 = self.cnn1[0][0], self.cnn1[1][0]
         rows = x[:, :4, :].reshape(B * 4, T)
@@ -602,7 +632,8 @@ class CNN_potes(nn.Module):
         return PotesHeadLossFunction.apply(z.reshape(B, -1), self.dimreduc.weight, self.dimreduc.bias,
                                            self.linear.weight, self.linear.bias, target,
                                            float(drop.p) if drop is not None else 0.0,
-                                           float(self.dropout.p), self.training, rnd, defer, latent)
+                                           float(self.dropout.p), self.training, rnd, defer, latent,
+                                           selc)
 
     def features(self, x: torch.Tensor) -> torch.Tensor:
         B, C, T = x.shape

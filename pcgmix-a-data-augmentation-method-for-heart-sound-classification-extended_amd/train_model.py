@@ -74,11 +74,69 @@ class CELoss(nn.Module):
         return -(F.log_softmax(logits, dim=1) * target_ohe).sum(dim=1).mean()
 
 
+def selc_keep_take(momentum: float):
+    """The two float32 factors of ``m * soft + (1 - m) * pred`` as torch forms them from the Python
+    scalar ``m``: ``1 - m`` is taken in double and THEN cast, so for m = 0.9 the second factor is
+    ``float32(0.1)`` and not ``float32(1) - float32(0.9)`` (one ulp more)."""
+    return np.float32(momentum), np.float32(1.0 - momentum)
+
+
+class SELCFunction(torch.autograd.Function):
+    """SELCLoss past its turning point (train_model.py:56-80) on a HIP device as one kernel each way
+    (``pcgmix_selc_{fwd,bwd}_f32``): softmax, the momentum update of ``soft_labels[index]`` (in
+    place, as the reference's side effect) and the loss against the updated rows; the backward
+    reads the rows the forward stored, not ``soft_labels``.  ``index``: int64 (B,) on the device,
+    distinct values; a value outside [0, N) leaves its row out (no update, zero loss and gradient)."""
+
+    @staticmethod
+    def forward(ctx, logits, index, soft_labels, momentum):
+        import ctypes
+        from . import _lib
+        lib = _lib.load()
+        logits = logits.contiguous()
+        B, C = logits.shape
+        if index.dtype != torch.int64 or index.shape != (B,) or index.device != logits.device \
+                or not index.is_contiguous():
+            raise ValueError("index must be a contiguous int64 (B,) tensor on the logits' device")
+        if soft_labels.dtype != torch.float32 or soft_labels.dim() != 2 or soft_labels.shape[1] != C \
+                or soft_labels.device != logits.device or not soft_labels.is_contiguous():
+            raise ValueError("soft_labels must be a contiguous float32 (N, classes) tensor on the "
+                             "logits' device")
+        keep, take = selc_keep_take(momentum)
+        rows = torch.empty_like(logits)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
+        _lib.check(lib.pcgmix_selc_fwd_f32(logits.data_ptr(), index.data_ptr(), soft_labels.data_ptr(),
+                                           soft_labels.shape[0], ctypes.c_float(keep),
+                                           ctypes.c_float(take), rows.data_ptr(), loss.data_ptr(),
+                                           B, C, stream), "pcgmix_selc_fwd_f32")
+        ctx.save_for_backward(logits, rows)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gout):
+        import ctypes
+        from . import _lib
+        lib = _lib.load()
+        logits, rows = ctx.saved_tensors
+        gout = gout.to(torch.float32).contiguous()
+        d = torch.empty_like(logits)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)
+        _lib.check(lib.pcgmix_selc_bwd_f32(logits.data_ptr(), rows.data_ptr(), gout.data_ptr(),
+                                           d.data_ptr(), logits.shape[0], logits.shape[1], stream),
+                   "pcgmix_selc_bwd_f32")
+        return d, None, None, None
+
+
 class SELCLoss(nn.Module):
     """train_model.py:56-80.  Plain CE until epoch ``es``; afterwards the self-ensembled soft
     labels.  With the reference's default (``es = num_epochs + 1`` unless the method contains
     'SELC', :394-402) it is CELoss.  Soft labels live on ``device`` (the reference hard-codes
-    ``.cuda()``, :60)."""
+    ``.cuda()``, :60).  On a HIP device the SELC phase is ``SELCFunction``; ``use_kernel = False``
+    keeps the torch formulation (which is also what a CPU tensor gets)."""
+
+    use_kernel = True     # SELC phase through the HIP kernels (False: torch ops; train_step then
+                          # also leaves the fused Potes head + SELC node)
 
     def __init__(self, labels, num_classes: int, es: int = 10, momentum: float = 0.9,
                  device: Optional[torch.device] = None):
@@ -90,11 +148,26 @@ class SELCLoss(nn.Module):
         self.num_classes, self.es, self.momentum = num_classes, es, momentum
         self.CEloss = CELoss(num_classes)
 
+    def device_index(self, index) -> torch.Tensor:
+        """``index`` as an int64 tensor next to the soft labels.  An index that arrives on the host
+        (every loader hands over a host tensor) is checked there: outside [0, N) is an IndexError,
+        before anything is launched.  A device tensor is taken as it is — the kernels leave a row
+        with a bad index out, they never write outside ``soft_labels``."""
+        if not (torch.is_tensor(index) and index.is_cuda):
+            index = torch.as_tensor(index, dtype=torch.long).reshape(-1)
+            n = self.soft_labels.shape[0]
+            if index.numel() and (int(index.min()) < 0 or int(index.max()) >= n):
+                raise IndexError(f"SELCLoss: sample index outside [0, {n})")
+        return index.to(self.soft_labels.device, dtype=torch.long, non_blocking=True)
+
     def forward(self, logits, labels, index, epoch, mode):
         if mode == "test" or epoch <= self.es:
             return self.CEloss(logits, labels)
+        index = self.device_index(index)
+        if self.use_kernel and logits.is_cuda and logits.dtype == torch.float32 \
+                and logits.dim() == 2 and logits.shape[0] > 0:
+            return SELCFunction.apply(logits, index.contiguous(), self.soft_labels, self.momentum)
         pred = F.softmax(logits, dim=1)
-        index = torch.as_tensor(index, device=self.soft_labels.device)
         with torch.no_grad():
             self.soft_labels[index] = (self.momentum * self.soft_labels[index]
                                        + (1 - self.momentum) * pred.detach())
@@ -553,6 +626,20 @@ def latent_host_step(args, data, target, target_ohe, step: int):
     return mix_dev, inv_dev, float(plan.lam32)
 
 
+def selc_phase(criterion, epoch) -> bool:
+    """True when ``criterion`` is a SELCLoss past its turning point at ``epoch`` (train_model.py:72-80)."""
+    return isinstance(criterion, SELCLoss) and epoch is not None and epoch > criterion.es
+
+
+def selc_fused_model(model, criterion, data, target_ohe, epoch):
+    """The CNN_potes that takes a SELC-phase step as head + SELC loss in one autograd node
+    (``loss_and_logits(..., selc=...)``): the model ``fused_loss_model`` accepts in the CE phase,
+    with ``SELCLoss.use_kernel`` on.  None otherwise (``criterion(...)`` then runs ``SELCFunction``)."""
+    if not (selc_phase(criterion, epoch) and criterion.use_kernel):
+        return None
+    return fused_loss_model(model, criterion.CEloss, data, target_ohe, None)
+
+
 def clips_outside_optimizer(args, optimizer) -> bool:
     """``clip_grad_value_`` as a pass of its own: ClipAdam clips in its kernel."""
     return bool(args.grad_clip) and not isinstance(optimizer, ClipAdam)
@@ -588,8 +675,14 @@ def train_step(args, model, batch, device, optimizer, scheduler, criterion, epoc
                                              host_labels=target.numpy() if not target.is_cuda else None)
         fused = fused_loss_model(model, criterion, data, target_ohe, epoch) \
             if getattr(args, "depth", 0) == 0 else None
+    selc_fused = selc_fused_model(model, criterion, data, target_ohe, epoch) \
+        if fused is None and getattr(args, "depth", 0) == 0 else None
     if fused is not None:                   # head + loss as one autograd node (two launches, not four)
         loss, out = fused.loss_and_logits(data, target_ohe, latent=latent)
+    elif selc_fused is not None:            # the same node with the SELC loss in the tail kernel
+        loss, out = selc_fused.loss_and_logits(
+            data, target_ohe,
+            selc=(criterion.device_index(indices), criterion.soft_labels, criterion.momentum))
     else:
         out = model(data, depth=getattr(args, "depth", 0), pass_part="second")
         loss = criterion(out, target_ohe, indices, epoch, "train")
@@ -663,7 +756,13 @@ class GraphedTrainStep:
     step's payload).  Under torch.distributed pass the UNWRAPPED model: gradients are packed into
     one flat buffer inside the graph, averaged by one eager all-reduce after the replay
     (``FlatGradSync``) — DDP's hooks cannot be captured — and the update is a SECOND small graph
-    replayed behind the collective.  Needs static shapes (the loaders use drop_last=True)."""
+    replayed behind the collective.  Needs static shapes (the loaders use drop_last=True).
+
+    A step is captured for ONE phase of a ``SELCLoss``: ``selc=False`` (default) the plain-CE one,
+    ``selc=True`` the phase past the turning point (train_model.py:72-80) — the fused Potes head with
+    the SELC tail kernel, ``SELCFunction`` behind every other model.  The batch's sample indices go
+    to a static int64 buffer before every replay (a copy of their own; the static block keeps its
+    layout).  ``prepare`` refuses an epoch of the other phase."""
 
     use_tape = True      # direct launches instead of the graph replay where the step allows it
     _TAPE_LAUNCHES = ("pcgmix_potes_stack_fwd_save_f32", "pcgmix_potes_head_loss_fwd_f32",
@@ -671,11 +770,16 @@ class GraphedTrainStep:
                       "pcgmix_adam_clip_multi_reduce_dev_f32")
 
     def __init__(self, args, model, optimizer, scheduler, criterion, device, batch_size, channels,
-                 sig_len, sync: Optional[FlatGradSync] = None):
+                 sig_len, sync: Optional[FlatGradSync] = None, *, selc: bool = False):
         refusal = capture_refusal(args)
         if refusal is not None:
             raise NotImplementedError(refusal)
+        if selc and not hasattr(criterion, "soft_labels"):
+            raise ValueError("selc=True needs a criterion with soft_labels (SELCLoss)")
         self.args, self.model, self.opt, self.sched = args, model, optimizer, scheduler
+        self.selc, self.crit = bool(selc), criterion
+        # placeholder indices of the warm-up; every step's own arrive in ``prepare``
+        self.index = torch.arange(batch_size, device=criterion.soft_labels.device) if selc else None
         self.ce = criterion.CEloss if hasattr(criterion, "CEloss") else criterion
         self.es = getattr(criterion, "es", None)
         self.device = device
@@ -736,6 +840,8 @@ class GraphedTrainStep:
         import warnings
         device, sync = self.device, self.sync
         buffers = [(b, b.detach().clone()) for b in self.model.buffers()]
+        if self.selc:                                   # the warm-up passes move the soft labels
+            buffers.append((self.crit.soft_labels, self.crit.soft_labels.detach().clone()))
         rng = torch.cuda.get_rng_state(device)
         side = torch.cuda.Stream(device)
         side.wait_stream(torch.cuda.current_stream(device))
@@ -872,7 +978,14 @@ class GraphedTrainStep:
     def _fwd_bwd(self):
         fused = fused_loss_model(self.model, self.ce, self.x, self.t, None) \
             if isinstance(self.ce, CELoss) else None
-        if fused is not None:
+        if self.selc:
+            selc = (self.index, self.crit.soft_labels, self.crit.momentum)
+            if fused is not None:
+                loss, out = fused.loss_and_logits(self.x, self.t, selc=selc)
+            else:
+                out = self.model(self.x, depth=0, pass_part="second")
+                loss = SELCFunction.apply(out, *selc)
+        elif fused is not None:
             loss, out = fused.loss_and_logits(self.x, self.t_u8 if self.labels_mode else self.t)
         else:
             out = self.model(self.x, depth=0, pass_part="second")
@@ -905,11 +1018,15 @@ class GraphedTrainStep:
         CURRENT stream.  ``PipelinedTrainStep`` runs it on a side stream for batch k+1 while the
         graph of batch k replays."""
         from . import hostprep, _lib, saliency as _saliency
-        data, target, frames, wav, _sq, _idx = batch
-        if self.es is not None and epoch > self.es:
-            raise NotImplementedError("SELC phase is not captured; use train_step")
+        data, target, frames, wav, _sq, idx = batch
+        if (self.es is not None and epoch > self.es) != self.selc:
+            raise NotImplementedError(
+                f"this step was captured for the {'SELC' if self.selc else 'plain-CE'} phase and epoch "
+                f"{epoch} belongs to the other one; capture a step with selc={not self.selc}")
         args, block = self.args, self.block
         data = data.to(self.device, non_blocking=True)
+        if self.selc:                                   # host-checked, then one copy of its own
+            self.index.copy_(self.crit.device_index(idx), non_blocking=True)
         frames_np = augmentations._as_numpy_frames(frames)
         B, C, T = data.shape
         step = int(augmentation_counter(args, step_counter).count)
@@ -1127,28 +1244,31 @@ def _epoch_graphed_step(args, model, optimizer, scheduler, criterion, device, ep
     model, optimiser, scheduler, criterion, method and batch shape stay the same objects/values
     (the reference creates them once per run, train_model.py:293-410).  ``args.hipgraph = False``
     switches it off.  Eager: CPU, whatever ``capture_refusal`` names, wrapped (DataParallel/DDP)
-    models, a criterion other than ``SELCLoss``, epochs past its turning point, an active process
-    group (use ``train_model()`` / ``FlatGradSync`` there)."""
+    models, a criterion other than ``SELCLoss``, an active process group (use ``train_model()`` /
+    ``FlatGradSync`` there).  The step belongs to one phase of the criterion: at the first epoch past
+    ``criterion.es`` the plain-CE step is dropped and a SELC-phase one is captured in its place
+    (``ClipAdam.prepare_capture`` carries the live step count across)."""
     if not getattr(args, "hipgraph", True) or device.type != "cuda":
         return None
     if capture_refusal(args) is not None or not isinstance(criterion, SELCLoss):
         return None
     if not isinstance(model, (models.CNN_potes, models.ResNet9_myrtle)):
         return None
-    if epoch > criterion.es or getattr(args, "num_epochs", epoch) > criterion.es:
-        return None
     if rank_and_world()[1] > 1:
         return None
     data = batch[0]
     if data.dim() != 3:
         return None
+    phase = epoch > criterion.es
     key = (id(optimizer), id(scheduler), id(criterion), tuple(data.shape), args.method,
-           args.num_classes, device)
+           args.num_classes, device, phase)
     hit = model.__dict__.get("_pcgmix_epoch_step")      # kept ON the model: dies with it (a module-
     if hit is None or hit.key != key:                   # level table would keep model and graph alive)
         B, C, T = data.shape
         cls = captured_step_class(args)
-        hit = _EpochStep(key, cls(args, model, optimizer, scheduler, criterion, device, B, C, T))
+        model.__dict__["_pcgmix_epoch_step"] = hit = None   # the other phase's graph goes first
+        hit = _EpochStep(key, cls(args, model, optimizer, scheduler, criterion, device, B, C, T,
+                                  selc=phase))
         model.__dict__["_pcgmix_epoch_step"] = hit
     return hit.step
 
@@ -1361,24 +1481,32 @@ def train_model(args, dataset, device, use_graph: bool = True, log=print, pipeli
     args.num_steps = args.num_epochs * (len(train_loader.dataset) // args.batch_size)   # :390
     criterion = SELCLoss(train_labels, args.num_classes, es=selc_turning_point(args), device=device)
     # (the spectrogram step is 80 ms of MIOpen convolutions: nothing for a graph to win, it stays eager)
-    graphable = use_graph and device.type == "cuda" and args.num_epochs <= criterion.es \
-        and capture_refusal(args) is None
+    # Under torch.distributed a run that reaches the SELC phase stays eager: every rank owns a copy of
+    # the soft labels and sees its shard's indices only.
+    graphable = use_graph and device.type == "cuda" and capture_refusal(args) is None \
+        and (world == 1 or args.num_epochs <= criterion.es)
     if not graphable:
         model = wrap_distributed(model, device)
     optimizer, scheduler = make_optimizer(args, model)
     step_counter = step_counter_class()
-    graphed = None
-    if graphable:
-        graphed = captured_step_class(args, pipeline)(
+    graphed, graphed_selc = None, None
+
+    def capture_step(selc):
+        return captured_step_class(args, pipeline)(
             args, model, optimizer, scheduler, criterion, device,
             args.batch_size // world, args.num_channels, args.sig_len,
-            sync=FlatGradSync(model, device) if world > 1 else None)
+            sync=FlatGradSync(model, device) if world > 1 else None, selc=selc)
     performance = performance_metrics_class()                                           # :421
     perf = performance.dict
     plot_epochs = set(np.linspace(1, args.num_epochs, 11).astype("int").tolist())       # :424
     args.depth = 0
     t_sum = 0.0
     for epoch in range(1, args.num_epochs + 1):
+        if graphable and graphed_selc != (epoch > criterion.es):     # first epoch, and the first past es
+            graphed = None                                           # (the old graph goes first)
+            graphed_selc = epoch > criterion.es
+            model.train()                    # the evaluation of the epoch before left it in eval mode
+            graphed = capture_step(graphed_selc)
         t0 = _time.time()
         batches = (shard_batch(b, rank, world) for b in train_loader) if world > 1 else train_loader
         stats, n_batches = _run_epoch(
