@@ -294,6 +294,13 @@ __global__ __launch_bounds__(kHbWaves * 64) void potes_head_bwd_kernel(
     wcol[o] = w1[(size_t)o * K + (valid ? k : 0)];     // clamped, not predicated
     acc[o] = 0.f;
   }
+  // Dropout bits: element e = row*K + k owns the bits1 bits at bit offset e*bits1, which start at bit
+  // (e*bits1) & 7 of their byte — the ELEMENT's offset, not the column's: with bits1 == 1 and
+  // K % 8 == 4 every odd row starts in the middle of a byte.  This lane's rows are row_lo + wave +
+  // kHbWaves*m, and kHbWaves*K*bits1 is a multiple of 8 (K % 4 == 0), so one shift serves them all.
+  // Only the low three bits of the product matter: 32-bit arithmetic may wrap.
+  static_assert(kHbWaves % 2 == 0 && kHbRows % kHbWaves == 0, "rows of a lane must be kHbWaves apart, kHbWaves even");
+  const unsigned sh = (((unsigned)(row_lo + wave) * (unsigned)K + (unsigned)k) * (unsigned)bits1) & 7u;
   for (int b0 = row_lo; b0 < row_hi; b0 += kHbRows) {
     const int nb = row_hi - b0 < kHbRows ? row_hi - b0 : kHbRows;
     __syncthreads();
@@ -319,9 +326,8 @@ __global__ __launch_bounds__(kHbWaves * 64) void potes_head_bwd_kernel(
       const int r = wave + kHbWaves * j;
       if (r < nb) {                                 // wave-uniform
         // x holds the features BEFORE the dropout: what the forward multiplied is mask*scale*x
-        // element (row, k) owns bits1 random bits at bit offset (row*K + k)*bits1; K % 4 == 0
-        const bool kept = !MASKED ||
-            (int)((mb[j] >> ((k * bits1) & 7)) & ((1u << bits1) - 1u)) >= thr1;
+        // element (row, k) owns bits1 random bits at bit offset (row*K + k)*bits1: `sh` inside mb[j]
+        const bool kept = !MASKED || (int)((mb[j] >> sh) & ((1u << bits1) - 1u)) >= thr1;
         const float xm = MASKED ? (kept ? xv[j] * scale1 : 0.f) : xv[j];
         float s = 0.f;
 #pragma unroll

@@ -21,7 +21,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // uses the f32-input matrix instruction, v_mfma_f32_32x32x2_f32 (exact f32, same peak as the f32
 // VALU but none of its issue slots and no LDS in the inner loop):
 //   D[o][b] += W[o][k] * h[b][k]      A = W (rows o >= O are zero lanes), B = h^T, 32 x 32 x 2
-// Block = 32 batch rows x one 1024-wide K chunk, 4 waves x 256 columns.  Per 64 columns a lane
+// Block = 32 batch rows x one 512-wide K chunk, 4 waves x 128 columns.  Per 64 columns a lane
 // (r = lane & 31, half = lane >> 5) takes the 32 consecutive floats h[row r][k0 + 32 half ..]
 // and the same span of W[r][..] (through LDS, see the kernel); MFMA step j multiplies element
 // j of both (the k index may be permuted freely inside a reduction as long as A and B agree).
@@ -54,8 +54,8 @@ __global__ __launch_bounds__(kSkinnyWaves * 64) void skinny_linear_partial_kerne
   constexpr int kWRows = (O + 3) / 4 * 4;                                // W tile rows in LDS
   constexpr int kWaveFloats = (32 + kWRows) * kSkStride;
   __shared__ __align__(16) float smem[kSkinnyWaves * kWaveFloats];
-  constexpr int kPerWave = kSkinnyChunk / kSkinnyWaves;                  // 256 columns
-  constexpr int kSteps = kPerWave / kSkStep;                             // 4
+  constexpr int kPerWave = kSkinnyChunk / kSkinnyWaves;                  // 128 columns
+  constexpr int kSteps = kPerWave / kSkStep;                             // 2
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 31, half = lane >> 5;
   const int row_base = blockIdx.x * kSkinnyRows, ks = blockIdx.y;
