@@ -639,6 +639,52 @@ int pcgmix_potes_head_bwd_f32(const float* dlogits, const float* z, const uint8_
                               int B, int K, int C, pcgmix_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluation pass.                                                                    [device]
+ *
+ * The reference's test_data_accuracy (train_model.py:591-670): per batch of heart cycles the
+ * softmax of the logits (:602) and the criterion (:608-609), per recording the mean of its cycles'
+ * softmax rows (np.mean(arr, axis=0), :627) or, under '(class_majority)', the bincount of their
+ * arg-max votes (:634-647).  No atomics; every sum in a stated order; 1 <= C <= 8.
+ *
+ * Row rule (one device function behind both forward entry points), for logits l[0..C):
+ *   m = max_c l_c;  e_c = expf(l_c - m);  s = sum_c e_c (c ascending);  p_c = e_c / s
+ *   loss = -((l_y - m) - logf(s)) for the label byte y (CELoss with a one-hot target, :45-54)
+ *   vote = lowest index of the maximum of the float32 p (np.argmax of the softmax OUTPUT, :637)
+ *
+ * pcgmix_eval_rows_f32: logits (B,C) of any model -> prob (B,C), loss_rows (B) (0 when labels is
+ *   NULL), vote (B) bytes.  labels: (B) bytes or NULL; a byte >= C gives loss 0 (the host refuses
+ *   such labels).  B == 0 returns 0 and launches nothing; C outside 1..8: hipErrorInvalidValue.
+ *
+ * pcgmix_potes_head_eval_f32: the Potes head in eval mode (no dropout) — the split-K partial launch
+ *   of pcgmix_potes_head_fwd_f32, then ONE tail launch that sums the partials in that entry point's
+ *   order, adds the bias, applies ReLU and the fmaf chain over the 20 features, then the row rule.
+ *   The logits (optional output, may be NULL) are bit-identical to pcgmix_potes_head_fwd_f32 with
+ *   both masks NULL; prob, loss_rows and vote are those of pcgmix_eval_rows_f32 on them.  x, w1, b1,
+ *   w2, b2, partial: as for pcgmix_potes_head_fwd_f32 (K % 4 == 0, x and w1 16-byte aligned, partial
+ *   pcgmix_skinny_linear_splits(B,K) * B * 20 floats).
+ *
+ * pcgmix_eval_segments_f32: the per-recording reduction of N rows into R recordings.
+ *   order     (N) int32: the cycle rows grouped by recording, within a recording in loader order
+ *   rec_start (R+1) int32 CSR offsets into order
+ *   mean_p    (R,C): the recording's rows added SEQUENTIALLY in float32, divided by float(n) —
+ *             bit for bit np.mean(list_of_rows, axis=0) (:627)
+ *   votes     (R,C) int32: how many of the recording's vote bytes equal c (np.bincount, :638)
+ *   loss_rec  (R) float64 (8-byte aligned): the recording's row losses added sequentially in double
+ *   One thread per (recording, class).  The caller validates order and rec_start; the kernel
+ *   additionally clamps every index it reads into range.  R == 0 returns 0 and launches nothing.
+ */
+int pcgmix_eval_rows_f32(const float* logits, const uint8_t* labels, float* prob, float* loss_rows,
+                         uint8_t* vote, int B, int C, pcgmix_stream_t stream);
+int pcgmix_potes_head_eval_f32(const float* x, const float* w1, const float* b1, const float* w2,
+                               const float* b2, const uint8_t* labels, float* partial, float* logits,
+                               float* prob, float* loss_rows, uint8_t* vote, int B, int K, int C,
+                               pcgmix_stream_t stream);
+int pcgmix_eval_segments_f32(const float* prob, const float* loss_rows, const uint8_t* vote,
+                             const int32_t* order, const int32_t* rec_start, float* mean_p,
+                             int32_t* votes, double* loss_rec, int N, int R, int C,
+                             pcgmix_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Potes classifier head + soft-target cross entropy, fused.                           [device]
  *
  * The head above followed by CELoss (train_model.py:45-54: mean_b(-sum_c log_softmax(logits)[b,c]

@@ -129,6 +129,9 @@ SIGNATURES = {
                                                      _c_float, _c_int, _ptr, _ptr, _ptr, _ptr, _c_int,
                                                      _c_float, _c_float] + [_ptr] * 8 +
                                             [_c_int, _c_int, _c_int, _c_int, _ptr]),
+    "pcgmix_eval_rows_f32": (_c_int, [_ptr] * 5 + [_c_int, _c_int, _ptr]),
+    "pcgmix_potes_head_eval_f32": (_c_int, [_ptr] * 11 + [_c_int, _c_int, _c_int, _ptr]),
+    "pcgmix_eval_segments_f32": (_c_int, [_ptr] * 8 + [_c_int, _c_int, _c_int, _ptr]),
     "pcgmix_splice_same_label_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, ctypes.c_uint64, _c_float, _ptr,
                                               _ptr, _c_int, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int,
                                               _ptr]),

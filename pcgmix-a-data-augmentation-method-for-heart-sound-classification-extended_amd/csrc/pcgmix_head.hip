@@ -12,6 +12,8 @@
 //
 //   potes_tail_fwd_kernel   split-K partials of dimreduc -> +bias -> ReLU -> dropout mask ->
 //                           Linear(20->C): z (kept for backward) and logits
+//   potes_tail_eval_kernel  the same sums in eval mode, then the evaluation's row rule: softmax,
+//                           cross entropy against a label byte, vote (train_model.py:591-670)
 //   soft_ce_fwd_kernel      loss scalar, one block
 //   soft_ce_bwd_kernel      dlogits
 //   potes_tail_bwd_kernel   dlogits -> dW2, db2, dz (through dropout and ReLU), db1; one block
@@ -124,6 +126,65 @@ __global__ __launch_bounds__(kTailRows* kHeadO * 4) void potes_tail_saliency_ker
     float sacc = 0.f;
     for (int c = 0; c < C; ++c) sacc = fmaf(seed[(size_t)row * C + c], w2[c * kHeadO + o], sacc);
     dz[i] = sacc * fac;
+  }
+}
+
+// ------------------------------------------------------------------------------ tail, evaluation
+// Eval mode (no dropout), nothing kept for a backward: potes_tail_fwd_kernel's sums — the split-K
+// partials in its order, + bias, ReLU, its fmaf chain over the 20 features, so the logits are the
+// same bits — followed by the evaluation's row rule (eval_row, pcgmix_kernels.h; train_model.py:
+// 591-670): the row's softmax, its cross entropy against the label byte and its vote.  One launch
+// where the torch path issues the tail, a softmax, the loss chain and an arg-max.
+__global__ __launch_bounds__(kTailRows* kHeadO * 4) void potes_tail_eval_kernel(
+    const float* __restrict__ partial, int KS, const float* __restrict__ b1,
+    const float* __restrict__ w2, const float* __restrict__ b2, const uint8_t* __restrict__ labels,
+    float* __restrict__ logits, float* __restrict__ prob, float* __restrict__ loss_rows,
+    uint8_t* __restrict__ vote, int B, int C) {
+  __shared__ float h[kTailRows][kHeadO];
+  __shared__ float lg[kTailRows][kHeadMaxC];
+  const int t = threadIdx.x, q = t & 3, e = t >> 2;            // e = r * kHeadO + o
+  const int r = e / kHeadO, o = e - r * kHeadO;
+  const int row = blockIdx.x * kTailRows + r;
+  const size_t i = (size_t)(row < B ? row : 0) * kHeadO + o;
+  const size_t plane = (size_t)B * kHeadO;
+  float v = 0.f;
+  int ks = q;
+  for (; ks + 12 < KS; ks += 16) {                  // four independent loads in flight
+    const float t0 = partial[(size_t)ks * plane + i], t1 = partial[(size_t)(ks + 4) * plane + i],
+                t2 = partial[(size_t)(ks + 8) * plane + i], t3 = partial[(size_t)(ks + 12) * plane + i];
+    v += t0; v += t1; v += t2; v += t3;
+  }
+  for (; ks < KS; ks += 4) v += partial[(size_t)ks * plane + i];
+  v += __shfl_xor(v, 1, 64);
+  v += __shfl_xor(v, 2, 64);
+  float hv = 0.f;
+  if (row < B && q == 0) {
+    v += b1 ? b1[o] : 0.f;
+    hv = v > 0.f ? v : 0.f;
+  }
+  if (q == 0) h[r][o] = hv;
+  __syncthreads();
+  if (t < kTailRows * C) {
+    const int rr = t / C, c = t - rr * C;
+    const int row2 = blockIdx.x * kTailRows + rr;
+    float a = 0.f;
+    if (row2 < B) {
+      a = b2 ? b2[c] : 0.f;
+#pragma unroll
+      for (int k = 0; k < kHeadO; ++k) a = fmaf(h[rr][k], w2[c * kHeadO + k], a);
+      if (logits) logits[(size_t)row2 * C + c] = a;
+    }
+    lg[rr][c] = a;
+  }
+  __syncthreads();
+  if (t < kTailRows) {
+    const int row2 = blockIdx.x * kTailRows + t;
+    if (row2 < B) {
+      float loss;
+      const int vt = eval_row(lg[t], C, labels ? (int)labels[row2] : -1, prob + (size_t)row2 * C, loss);
+      loss_rows[row2] = loss;
+      vote[row2] = (uint8_t)vt;
+    }
   }
 }
 
@@ -985,6 +1046,24 @@ extern "C" int pcgmix_potes_head_fwd_f32(const float* x, const uint8_t* mask1, f
   hipLaunchKernelGGL(potes_tail_fwd_kernel, dim3((unsigned)((B + kTailRows - 1) / kTailRows)),
                      dim3(kTailRows * kHeadO * 4), 0, s, partial, KS, b1, mask2, scale2, thr2, w2, b2,
                      z, logits, B, C);
+  return (int)hipGetLastError();
+}
+
+extern "C" int pcgmix_potes_head_eval_f32(const float* x, const float* w1, const float* b1,
+                                          const float* w2, const float* b2, const uint8_t* labels,
+                                          float* partial, float* logits, float* prob,
+                                          float* loss_rows, uint8_t* vote, int B, int K, int C,
+                                          pcgmix_stream_t stream) {
+  using namespace pcgmix;
+  static_assert(kEvalMaxC == kHeadMaxC, "eval_row and the head agree on the class limit");
+  if (!w2 || !prob || !loss_rows || !vote || C <= 0 || C > kHeadMaxC) return hipErrorInvalidValue;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const hipError_t e = launch_skinny_partial(x, w1, partial, B, K, kHeadO, s, nullptr, 1.0f, 0, 8);
+  if (e != hipSuccess) return (int)e;
+  const int KS = pcgmix_skinny_linear_splits(B, K);
+  hipLaunchKernelGGL(potes_tail_eval_kernel, dim3((unsigned)((B + kTailRows - 1) / kTailRows)),
+                     dim3(kTailRows * kHeadO * 4), 0, s, partial, KS, b1, w2, b2, labels, logits, prob,
+                     loss_rows, vote, B, C);
   return (int)hipGetLastError();
 }
 

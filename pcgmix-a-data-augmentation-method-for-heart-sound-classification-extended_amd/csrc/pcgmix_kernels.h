@@ -358,5 +358,43 @@ inline bool dropout_fill_args_ok(const void* rnd_out, long long rnd_bytes, int N
                        (reinterpret_cast<uintptr_t>(rnd_out) & 15) || N == 0);
 }
 
+// ---- evaluation (pcgmix_eval.hip, pcgmix_head.hip): the row rule of train_model.py:591-670
+// One row of logits l[0..C), 1 <= C <= kEvalMaxC: the softmax the reference votes with (:602) and,
+// for a label byte y < C, the row's cross entropy as potes_tail_loss_kernel forms it for a one-hot
+// target (train_model.py:45-54).  m = max l; e_c = expf(l_c - m); s = sum e_c, c ascending;
+// p_c = e_c / s; loss = -((l_y - m) - logf(s)) (0 without a label); the returned vote is the lowest
+// index of the maximum of the float32 p — np.argmax of the softmax OUTPUT (:637), not of the logits.
+constexpr int kEvalMaxC = 8;
+template <typename L>
+__device__ __forceinline__ int eval_row(const L& l, int C, int y, float* __restrict__ p, float& loss) {
+  float m = l[0];
+  for (int c = 1; c < C; ++c) m = fmaxf(m, l[c]);
+  float e[kEvalMaxC];
+  float s = 0.f, ly = 0.f;
+#pragma unroll
+  for (int c = 0; c < kEvalMaxC; ++c) {
+    if (c < C) {
+      e[c] = expf(l[c] - m);
+      s += e[c];
+      ly = c == y ? l[c] : ly;
+    }
+  }
+  int vote = 0;
+  float best = 0.f;
+#pragma unroll
+  for (int c = 0; c < kEvalMaxC; ++c) {
+    if (c < C) {
+      const float pc = e[c] / s;
+      p[c] = pc;
+      if (c == 0 || pc > best) {
+        best = pc;
+        vote = c;
+      }
+    }
+  }
+  loss = (y >= 0 && y < C) ? -((ly - m) - logf(s)) : 0.f;
+  return vote;
+}
+
 }  // namespace pcgmix
 #endif

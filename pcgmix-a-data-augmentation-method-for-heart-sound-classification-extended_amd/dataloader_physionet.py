@@ -186,6 +186,8 @@ class ResidentLoader:
         self.sig_qual = torch.from_numpy(np.asarray(sig_qual, dtype=np.int64))
         self.batch_size, self.shuffle, self.drop_last = batch_size, shuffle, drop_last
         self.dataset = range(len(self.label))             # len(loader.dataset), train_model.py:390
+        self.eval_plan = None        # train_model.EvalPlan of this loader, cached by predict_recordings
+                                     # (shuffle=False only: the order is then the same every time)
 
     def __len__(self):
         n = len(self.label)

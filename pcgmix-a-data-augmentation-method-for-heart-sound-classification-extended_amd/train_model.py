@@ -13,6 +13,7 @@ model zoo / plotting / pickling around the loop (out of scope).
 from __future__ import annotations
 
 import os
+import types
 from typing import Optional
 
 import numpy as np
@@ -1338,26 +1339,231 @@ class performance_metrics_class:
         self.dict[string].append(value)
 
 
+FUSED_EVAL = True    # evaluation through the HIP eval kernels (predict_recordings) where they apply
+                     # (False: the torch formulation below, for A/B; a switch like models.FUSED_BN)
+EVAL_MAX_CLASSES = 8
+
+
+class EvalPlan:
+    """Host-side plan of one evaluation pass (train_model.py:615-632): from the recording name and
+    the label of every heart cycle, in the order the loader yields them, the recordings numbered by
+    first appearance (``names``), the label of each recording's FIRST cycle (``labels``), its cycle
+    count (``counts``), and the CSR pair the segments kernel walks: ``order`` (N) int32 — the cycle
+    rows grouped by recording, within a recording in loader order (a stable permutation) — and
+    ``rec_start`` (R+1) int32.  ``cycle_labels`` (N) uint8 are the per-cycle label bytes of the loss.
+
+    ``device_side(device, C)`` holds the device copies of ``order``, ``rec_start`` and the label bytes
+    and the (N,C) / (N) / (R,C) buffers of the pass: uploaded or allocated once per (device, C),
+    counted in ``uploads``.  ``ResidentLoader(shuffle=False)`` is immutable and yields the same order
+    every time: its plan is cached on the loader (``loader.eval_plan``)."""
+
+    def __init__(self, names, labels):
+        names = np.asarray(list(names), dtype=object)
+        lab = np.asarray(labels, dtype=np.int64).reshape(-1)
+        if len(names) != len(lab):
+            raise ValueError("EvalPlan: one label per recording name")
+        if len(lab) and (lab.min() < 0 or lab.max() > 255):
+            raise ValueError("EvalPlan: labels must fit a byte")
+        self.n = int(len(lab))
+        if self.n:
+            _uniq, first, inv = np.unique(names.astype(str), return_index=True, return_inverse=True)
+            by_first = np.argsort(first, kind="stable")          # recording id = rank of its first cycle
+            rank = np.empty(len(first), dtype=np.int64)
+            rank[by_first] = np.arange(len(first))
+            ids = rank[np.asarray(inv).reshape(-1)]
+            first = first[by_first]
+        else:
+            ids, first = np.zeros(0, np.int64), np.zeros(0, np.int64)
+        self.ids = ids
+        self.names = [str(names[i]) for i in first]
+        self.labels = lab[first]
+        self.counts = np.bincount(ids, minlength=len(first)).astype(np.int64)
+        self.order = np.argsort(ids, kind="stable").astype(np.int32)
+        self.rec_start = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int32)
+        self.cycle_labels = lab.astype(np.uint8)
+        self.validate()
+        self.uploads = 0
+        self._device = {}
+
+    @property
+    def recordings(self) -> int:
+        return len(self.names)
+
+    def validate(self) -> None:
+        """What the segments kernel relies on (it clamps besides): ``order`` a permutation of the N
+        rows, ``rec_start`` non-decreasing from 0 to N."""
+        if not np.array_equal(np.sort(self.order), np.arange(self.n)):
+            raise ValueError("EvalPlan: order is not a permutation of the cycle rows")
+        rs = self.rec_start
+        if rs[0] != 0 or rs[-1] != self.n or (np.diff(rs) < 0).any():
+            raise ValueError("EvalPlan: rec_start is not a CSR offset vector over the cycle rows")
+
+    def device_side(self, device, C: int):
+        key = (str(device), int(C))
+        side = self._device.get(key)
+        if side is None:
+            N, R = self.n, self.recordings
+            side = types.SimpleNamespace(
+                order=torch.from_numpy(self.order).to(device),
+                rec_start=torch.from_numpy(self.rec_start).to(device),
+                labels=torch.from_numpy(self.cycle_labels).to(device),
+                prob=torch.empty((N, C), dtype=torch.float32, device=device),
+                loss_rows=torch.empty(N, dtype=torch.float32, device=device),
+                vote=torch.empty(N, dtype=torch.uint8, device=device),
+                # [loss_rec f64 (R) | mean_p f32 (R,C) | votes i32 (R,C)]: one buffer, one copy to the host
+                out=torch.empty(8 * R + 8 * R * C, dtype=torch.uint8, device=device))
+            self.uploads += 3
+            self._device[key] = side
+        return side
+
+
+def _eval_labels_ok(labels, C: int) -> None:
+    labels = np.asarray(labels)
+    if labels.size and (labels.min() < 0 or labels.max() >= C):
+        raise ValueError(f"predict_recordings: label outside [0, {C})")
+
+
+def fused_eval_applies(args, device, criterion) -> bool:
+    """Whether ``test_data_accuracy`` builds its metrics from ``predict_recordings``: a GPU, at most
+    eight classes, and a loss the row rule computes — none, ``CELoss``, or ``SELCLoss`` (whose
+    'test' mode is its ``CEloss``)."""
+    return (FUSED_EVAL and torch.device(device).type == "cuda" and 1 <= args.num_classes <= EVAL_MAX_CLASSES
+            and (criterion is None or type(criterion) in (CELoss, SELCLoss)))
+
+
 @torch.no_grad()
-def test_data_accuracy(args, model, test_loader, device, criterion=None, epoch=None,
-                       performance=None):
-    """Evaluation as train_model.py:591-670, reference signature ``(args, model, test_loader,
-    device, criterion, epoch, performance)`` (called that way at :455): per recording, average
-    the softmax of its heart cycles and take the argmax (:623-633); with '(class_majority)' in
-    ``args.method`` the recording's class is the majority of its cycles' arg-max votes, a 0/1 tie
-    going to class 1 (:634-647).  Accuracy / sensitivity / specificity / precision / recall / F1
-    over recordings, ROC-AUC of the mean class-1 probability.  The per-recording sums are
-    segmented sums on the device (index_add), not a Python dict of ``.item()`` values.
+def predict_recordings(args, model, loader, device, criterion=None):
+    """Recording-level inference (train_model.py:591-647) through the HIP eval kernels: per batch the
+    model's logits -> softmax, row loss and vote in the launch that forms them
+    (``pcgmix_potes_head_eval_f32`` behind the conv stack for an unwrapped ``CNN_potes`` on its fused
+    path, ``pcgmix_eval_rows_f32`` behind ``model(data)`` for everything else), rows landing at the
+    batch's offset in the plan's buffers; then ONE ``pcgmix_eval_segments_f32`` launch and ONE copy to
+    the host.  Nothing synchronises per batch.  The per-recording sums run in loader order: the same
+    bits on every call.
 
-    With a ``performance`` object (anything with the reference's ``add(key, value)``,
-    :194-195) the eight ``test_*`` values are appended to it in the reference's order
-    (:651-669) and the function returns None, as the reference does.  Without one it returns
-    the same numbers as a dict.  ``epoch`` is accepted and unused, as in the reference.
+    Returns a dict: ``names`` (recordings by first appearance), ``labels`` (first cycle's label),
+    ``counts``, ``mean_proba`` (R,C) float32, ``votes`` (R,C) int32, ``loss_sum`` (sum of the row
+    cross entropies, recordings added in order; None without a criterion), ``n`` (cycles seen).
+    ``criterion``: None, ``CELoss`` or ``SELCLoss``.  The model is put in eval mode; the loader is
+    iterated exactly once.  A label >= ``args.num_classes`` is a ValueError before the batch that
+    carries it launches anything (with a cached plan: before any launch)."""
+    import ctypes
+    from . import _lib
+    device = torch.device(device)
+    C = int(args.num_classes)
+    if device.type != "cuda":
+        raise ValueError("predict_recordings runs on a HIP device (test_data_accuracy covers the CPU)")
+    if not 1 <= C <= EVAL_MAX_CLASSES:
+        raise ValueError(f"predict_recordings: 1..{EVAL_MAX_CLASSES} classes, got {C}")
+    if not (criterion is None or type(criterion) in (CELoss, SELCLoss)):
+        raise ValueError("predict_recordings computes the cross entropy of CELoss / SELCLoss('test'); "
+                         f"got {type(criterion).__name__}")
+    model.eval()
+    lib = _lib.load()
+    want_loss = criterion is not None
+    cacheable = hasattr(loader, "eval_plan") and not getattr(loader, "shuffle", True)
+    plan = loader.eval_plan if cacheable else None
+    if cacheable and plan is None:
+        plan = loader.eval_plan = EvalPlan(loader.wav, loader.label.numpy())
+    batches = loader
+    if plan is None and not hasattr(loader, "dataset"):
+        batches = list(loader)                     # (the one iteration: how many rows there are)
+        cap = sum(len(b[1]) for b in batches)
+    elif plan is None:
+        cap = len(loader.dataset)
+    if plan is not None:
+        if want_loss:
+            _eval_labels_ok(plan.cycle_labels, C)
+        side = plan.device_side(device, C)
+        prob, loss_rows, vote = side.prob, side.loss_rows, side.vote
+    else:
+        prob = torch.empty((cap, C), dtype=torch.float32, device=device)
+        loss_rows = torch.empty(cap, dtype=torch.float32, device=device)
+        vote = torch.empty(cap, dtype=torch.uint8, device=device)
+        seen_wav, seen_lab = [], []
+    potes = isinstance(model, models.CNN_potes)
+    n = 0
+    for data, target, _frames, wav, _sq, _idx in batches:
+        b = int(data.shape[0])
+        if b == 0:
+            continue
+        if plan is not None:
+            if n + b > plan.n:
+                raise ValueError("predict_recordings: the loader yields more rows than its cached plan")
+            lab_ptr = side.labels.data_ptr() + n if want_loss else None
+        else:
+            if n + b > cap or len(wav) != b or len(target) != b:
+                raise ValueError("predict_recordings: the loader yields more rows than len(loader.dataset)")
+            lab_host = target.detach().to("cpu", torch.int64).reshape(-1)
+            if want_loss:
+                _eval_labels_ok(lab_host.numpy(), C)
+            seen_wav.extend(wav)
+            seen_lab.append(lab_host)
+            lab_dev = lab_host.to(torch.uint8).to(device, non_blocking=True) if want_loss else None
+            lab_ptr = lab_dev.data_ptr() if want_loss else None
+        data = data.to(device)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        outs = (prob.data_ptr() + 4 * n * C, loss_rows.data_ptr() + 4 * n, vote.data_ptr() + n)
+        if potes and data.dim() == 3 and model._fused_head(data):
+            c1, c2 = model.cnn1[0][0], model.cnn1[1][0]
+            rows = data[:, :4, :].reshape(b * 4, data.shape[2]).contiguous()
+            # detached weights: ``ctx.needs_input_grad`` follows the inputs' ``requires_grad`` even under
+            # no_grad, and the conv stack would take its routing-saving forward for a backward nobody runs
+            feat = models.PotesStackFunction.apply(rows, c1.weight.detach(), c1.bias.detach(),
+                                                   c2.weight.detach(), c2.bias.detach()).reshape(b, -1)
+            K = int(feat.shape[1])
+            w1, w2 = model.dimreduc.weight.detach().contiguous(), model.linear.weight.detach().contiguous()
+            b1, b2 = model.dimreduc.bias, model.linear.bias
+            partial = torch.empty((lib.pcgmix_skinny_linear_splits(b, K), b, 20), dtype=torch.float32,
+                                  device=device)
+            _lib.check(lib.pcgmix_potes_head_eval_f32(
+                feat.data_ptr(), w1.data_ptr(), b1.detach().data_ptr() if b1 is not None else None,
+                w2.data_ptr(), b2.detach().data_ptr() if b2 is not None else None, lab_ptr,
+                partial.data_ptr(), None, *outs, b, K, C, stream), "pcgmix_potes_head_eval_f32")
+        else:
+            out = model(data)
+            if out.dim() != 2 or out.shape != (b, C):
+                raise ValueError(f"predict_recordings: the model returned {tuple(out.shape)}, "
+                                 f"expected ({b}, {C})")
+            out = out.to(torch.float32).contiguous()
+            _lib.check(lib.pcgmix_eval_rows_f32(out.data_ptr(), lab_ptr, *outs, b, C, stream),
+                       "pcgmix_eval_rows_f32")
+        n += b
+    if plan is None:
+        plan = EvalPlan(seen_wav, torch.cat(seen_lab).numpy() if seen_lab else [])
+        order = torch.from_numpy(plan.order).to(device)
+        rec_start = torch.from_numpy(plan.rec_start).to(device)
+        R = plan.recordings
+        out_buf = torch.empty(8 * R + 8 * R * C, dtype=torch.uint8, device=device)
+    else:
+        if n != plan.n:
+            raise ValueError("predict_recordings: the loader yields fewer rows than its cached plan")
+        order, rec_start, out_buf, R = side.order, side.rec_start, side.out, plan.recordings
+    if R:
+        stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        base = out_buf.data_ptr()
+        _lib.check(lib.pcgmix_eval_segments_f32(
+            prob.data_ptr(), loss_rows.data_ptr(), vote.data_ptr(), order.data_ptr(),
+            rec_start.data_ptr(), base + 8 * R, base + 8 * R + 4 * R * C, base, n, R, C, stream),
+            "pcgmix_eval_segments_f32")
+    host = out_buf.cpu().numpy()                       # the pass's one copy to the host (and its sync)
+    loss_rec = host[:8 * R].view(np.float64)
+    mean_p = host[8 * R:8 * R + 4 * R * C].view(np.float32).reshape(R, C)
+    votes = host[8 * R + 4 * R * C:].view(np.int32).reshape(R, C)
+    loss_sum = None
+    if want_loss:
+        loss_sum = 0.0
+        for v in loss_rec.tolist():                    # recordings in order, in double
+            loss_sum += v
+    return {"names": list(plan.names), "labels": plan.labels.copy(), "counts": plan.counts.copy(),
+            "mean_proba": mean_p, "votes": votes, "loss_sum": loss_sum, "n": n}
 
-    Under '(class_majority)' the reference never collects the mean probabilities, so its own
-    ``roc_auc_score`` line (:667) raises IndexError after the other seven values have been
-    appended: with ``performance`` this function does exactly that; the dict form carries
-    ``rocauc = None`` on that branch."""
+
+@torch.no_grad()
+def _collect_recordings_torch(args, model, test_loader, device, criterion, majority):
+    """The torch formulation of the per-recording collection (the CPU, other criteria, more than
+    eight classes, ``FUSED_EVAL = False``): per-recording sums as segmented sums on the device
+    (index_add).  Returns (mean_p, votes or None, recording labels, loss sum or None, cycles)."""
     model.eval()
     rec_ids: dict = {}
     rec_label: dict = {}
@@ -1377,7 +1583,6 @@ def test_data_accuracy(args, model, test_loader, device, criterion=None, epoch=N
                                   None, None, "test").double() * len(target)
         n += len(target)
     R = len(rec_ids)
-    majority = "(class_majority)" in getattr(args, "method", "")
     acc_p = torch.zeros(R, args.num_classes, device=device)
     acc_n = torch.zeros(R, device=device)
     votes = torch.zeros(R, args.num_classes, device=device, dtype=torch.long)
@@ -1387,14 +1592,49 @@ def test_data_accuracy(args, model, test_loader, device, criterion=None, epoch=N
         if majority:
             votes.index_add_(0, ids, F.one_hot(prob.argmax(1), args.num_classes))
     mean_p = (acc_p / acc_n[:, None]).cpu().numpy()
+    lab = np.asarray([rec_label[i] for i in range(R)])
+    return (mean_p, votes.cpu().numpy() if majority else None, lab,
+            float(loss_sum) if criterion is not None else None, n)
+
+
+@torch.no_grad()
+def test_data_accuracy(args, model, test_loader, device, criterion=None, epoch=None,
+                       performance=None):
+    """Evaluation as train_model.py:591-670, reference signature ``(args, model, test_loader,
+    device, criterion, epoch, performance)`` (called that way at :455): per recording, average
+    the softmax of its heart cycles and take the argmax (:623-633); with '(class_majority)' in
+    ``args.method`` the recording's class is the majority of its cycles' arg-max votes, a 0/1 tie
+    going to class 1 (:634-647).  Accuracy / sensitivity / specificity / precision / recall / F1
+    over recordings, ROC-AUC of the mean class-1 probability.  On a GPU, with at most eight classes
+    and no criterion, ``CELoss`` or ``SELCLoss``, the per-recording numbers come from
+    ``predict_recordings`` (HIP eval kernels, fixed-order sums; ``FUSED_EVAL``); otherwise from
+    the torch formulation (``_collect_recordings_torch``).
+
+    With a ``performance`` object (anything with the reference's ``add(key, value)``,
+    :194-195) the eight ``test_*`` values are appended to it in the reference's order
+    (:651-669) and the function returns None, as the reference does.  Without one it returns
+    the same numbers as a dict.  ``epoch`` is accepted and unused, as in the reference.
+
+    Under '(class_majority)' the reference never collects the mean probabilities, so its own
+    ``roc_auc_score`` line (:667) raises IndexError after the other seven values have been
+    appended: with ``performance`` this function does exactly that; the dict form carries
+    ``rocauc = None`` on that branch."""
+    majority = "(class_majority)" in getattr(args, "method", "")
+    if fused_eval_applies(args, device, criterion):
+        rec = predict_recordings(args, model, test_loader, device, criterion)
+        mean_p, votes, lab, loss_sum, n = (rec["mean_proba"], rec["votes"], np.asarray(rec["labels"]),
+                                           rec["loss_sum"], rec["n"])
+    else:
+        mean_p, votes, lab, loss_sum, n = _collect_recordings_torch(args, model, test_loader, device,
+                                                                     criterion, majority)
+    R = len(lab)
     if majority:
         pred = np.zeros(R, dtype=np.int64)
-        for r, c in enumerate(votes.cpu().numpy()):
+        for r, c in enumerate(votes):
             c = np.trim_zeros(c, "b") if c.any() else c[:1]          # what np.bincount returns
             pred[r] = 1 if (len(c) == 2 and c[0] == c[1]) else int(np.argmax(c))
     else:
         pred = mean_p.argmax(1)
-    lab = np.asarray([rec_label[i] for i in range(R)])
     tp = int(((pred == 1) & (lab == 1)).sum()); tn = int(((pred == 0) & (lab == 0)).sum())
     fp = int(((pred == 1) & (lab == 0)).sum()); fn = int(((pred == 0) & (lab == 1)).sum())
     prec = tp / max(1, tp + fp)
@@ -1415,7 +1655,7 @@ def test_data_accuracy(args, model, test_loader, device, criterion=None, epoch=N
     ev = {"accuracy": 100.0 * float((pred == lab).sum()) / max(1, R), "sensitivity": 100.0 * rec,
           "specificity": 100.0 * tn / max(1, tn + fp), "precision": prec, "recall": rec,
           "f1": 2 * prec * rec / max(1e-12, prec + rec), "rocauc": auc, "recordings": R,
-          "loss": float(loss_sum) / max(1, n_total) if criterion is not None else None}
+          "loss": loss_sum / max(1, n_total) if criterion is not None else None}
     if performance is None:
         return ev
     for key in ("accuracy", "loss", "specificity", "sensitivity", "f1", "precision", "recall"):
