@@ -1029,7 +1029,10 @@ int pcgmix_mix_kernel_name(int B, int C, int T, int n_knots, int zero_rect, int 
  *   backward: dz (shape of z) -> dx (shape of y), dgamma, dbeta (C each).  The ReLU mask and the
  *             pooling arg-max (first maximum) are recomputed from y.
  * workspace: pcgmix_bnrp_workspace_floats(B, H, W, C) floats.  All pointers 16-byte aligned
- * (8-byte for C = 2).
+ * (8-byte for C = 2), the workspace included; a misaligned one is refused (hipErrorInvalidValue).
+ * Non-finite input (forward): the ReLU and the window maximum keep a NaN as torch's relu and
+ * max_pool do, so a NaN in y — which in training mode makes the whole channel's statistics NaN —
+ * reaches z instead of turning into zeros.  The backward of a non-finite y is not specified.
  * Each direction reads y twice and writes its output once; reductions are fixed-order.
  */
 /* 1 for the channel counts the kernels take, else 0.  Host only: no device is touched. */

@@ -8,7 +8,7 @@
 // (pool, ReLU, two BatchNorm kernels) — nine to ten passes over the activation per block, each
 // through HBM.  Here, with y = conv output (rows x C, channels innermost):
 //
-//   forward   bn_stats_kernel        one read of y  -> per-block (sum, sum of squares) per channel
+//   forward   bn_stats_kernel        one read of y  -> per-block (sum, sum of squares) of y - y[0, c] per channel
 //             bn_finalize_kernel     mean, 1/std, running-stat update (float64 combination)
 //             bnrp_fwd_kernel        one read of y  -> z = maxpool(relu(gamma * xhat + beta)) [+ skip]
 //   backward  bnrp_bwd_reduce_kernel one read of y, dz -> sums of dy and dy * xhat per channel
@@ -109,15 +109,18 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_kernel(const V* __restric
   V s = vsplat<V>(0.f), ss = vsplat<V>(0.f);
   const long long stride = (long long)gridDim.x * A;              // multiple of Q
   long long i = (long long)blockIdx.x * A + threadIdx.x;
+  // Sums of y - K and (y - K)^2 about the pivot K_c = y[0, c] (the thread's channel group of row 0):
+  // var = E[(y-K)^2] - E[y-K]^2 then cancels digits in proportion to |mean - K| / std, not |mean| / std.
+  const V K = y[threadIdx.x % Q];
   for (; i + 3 * stride < n4; i += 4 * stride) {   // four loads in flight per lane (a pure reader
-    const V v0 = y[i], v1 = y[i + stride], v2 = y[i + 2 * stride], v3 = y[i + 3 * stride];
+    const V v0 = y[i] - K, v1 = y[i + stride] - K, v2 = y[i + 2 * stride] - K, v3 = y[i + 3 * stride] - K;
     s += v0; ss = vfma(v0, v0, ss);                 // has no store to hide a load-wait-load chain behind)
     s += v1; ss = vfma(v1, v1, ss);
     s += v2; ss = vfma(v2, v2, ss);
     s += v3; ss = vfma(v3, v3, ss);
   }
   for (; i < n4; i += stride) {
-    const V v = y[i];
+    const V v = y[i] - K;
     s += v;
     ss = vfma(v, v, ss);
   }
@@ -168,8 +171,8 @@ __device__ __forceinline__ void partial_sums(const float* __restrict__ partial, 
 // var is the biased batch variance (normalisation); the running variance gets the unbiased one,
 // as torch.nn.BatchNorm does.  Block = 16 channels x 16 lanes.
 __global__ __launch_bounds__(kFinCh * 16) void bn_finalize_kernel(
-    const float* __restrict__ partial, int nblk, int C, double n_rows, float eps, float momentum,
-    float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ running_mean,
+    const float* __restrict__ partial, const float* __restrict__ pivot, int nblk, int C, double n_rows,
+    float eps, float momentum, float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ running_mean,
     float* __restrict__ running_var, const float* __restrict__ mean_shift,
     long long* __restrict__ batches_tracked) {
   // mean_shift: a per-channel constant that was left out of y (the convolution's bias, which the
@@ -180,8 +183,9 @@ __global__ __launch_bounds__(kFinCh * 16) void bn_finalize_kernel(
   double s, ss;
   partial_sums(partial, nblk, C, c, lane, lds, &s, &ss);
   if (c >= C || lane != 0) return;
-  const double m = s / n_rows;
-  double var = ss / n_rows - m * m;
+  const double d = s / n_rows;                       // mean of y - K, K = pivot[c] = y[0, c] (bn_stats_kernel)
+  const double m = (double)pivot[c] + d;
+  double var = ss / n_rows - d * d;
   if (var < 0.0) var = 0.0;
   mean[c] = (float)m;
   invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
@@ -281,6 +285,10 @@ __device__ __forceinline__ PoolPos pool_pos(const BnShape& s, long long orow) {
   return p;
 }
 
+// ReLU that keeps a NaN (torch.relu does): a diverged activation must reach the loss, not turn
+// into zeros.  -0.0 and everything below give +0.0.
+__device__ __forceinline__ float relu_nan(float a) { return a <= 0.f ? 0.f : a; }
+
 // relu(scale * y + shift) at the ph x pw window of pooled position (b, ho, wo), channel group q;
 // returns the maximum and (through *arg) the index i * pw + j of its FIRST occurrence.
 // If `raw` is given it receives y itself at that first maximum (what the backward's xhat needs:
@@ -299,8 +307,8 @@ __device__ __forceinline__ V window_max(const V* __restrict__ y, const BnShape& 
       const int idx = i * s.pw + j;
 #pragma unroll
       for (int e = 0; e < kLanes<V>; ++e) {
-        const float r = a[e] > 0.f ? a[e] : 0.f;
-        if (r > best[e]) {
+        const float r = relu_nan(a[e]);
+        if (r > best[e] || r != r) {                  // a NaN wins and stays, as in torch's max_pool
           best[e] = r;
           arg[e] = idx;
           vb[e] = v[e];
@@ -365,8 +373,8 @@ __device__ __forceinline__ V window_best(const V (&v)[N], V scale, V shift, int 
     const V a = vfma(v[k], scale, shift);
 #pragma unroll
     for (int e = 0; e < kLanes<V>; ++e) {
-      const float r = a[e] > 0.f ? a[e] : 0.f;
-      if (r > best[e]) {
+      const float r = relu_nan(a[e]);
+      if (r > best[e] || r != r) {
         best[e] = r;
         arg[e] = k;
         vb[e] = v[k][e];
@@ -709,7 +717,7 @@ extern "C" int pcgmix_bnrp_fwd_f32(const float* y, const float* gamma, const flo
   BnShape s;
   if (!y || !gamma || !beta || !z || !mean || !invstd || !workspace || !bn_shape(&s, B, H, W, C, ph, pw))
     return hipErrorInvalidValue;
-  if (!bn_aligned(C, {y, z, skip, gamma, beta, mean, invstd})) return hipErrorInvalidValue;
+  if (!bn_aligned(C, {y, z, skip, gamma, beta, mean, invstd, workspace})) return hipErrorInvalidValue;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long long rows = (long long)B * H * W, n4 = rows * s.Q;
   const int nblk = bn_blocks(n4);
@@ -718,7 +726,7 @@ extern "C" int pcgmix_bnrp_fwd_f32(const float* y, const float* gamma, const flo
     hipLaunchKernelGGL(bn_stats_kernel<V>, dim3(nblk), dim3(s.A), 0, st, reinterpret_cast<const V*>(y), n4, s.Q, s.A,
                        workspace, C);
   });
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * 16), 0, st, workspace, nblk, C,
+  hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + kFinCh - 1) / kFinCh), dim3(kFinCh * 16), 0, st, workspace, y, nblk, C,
                      (double)rows, eps, momentum, mean, invstd, running_mean, running_var, mean_shift,
                      batches_tracked);
   launch_fwd(y, TrainStats{gamma, beta, mean, invstd}, skip, z, s, st);

@@ -2,7 +2,9 @@
 against the torch composition in float64.  Tolerances are those of test_bnrp_gpu.py: forward
 rtol 1e-4 / atol 2e-5, running statistics rtol 1e-5 / atol 1e-6, gradients beyond
 1e-4 * max|ref| + 1e-6 in at most 1e-4 of the elements (ReLU / arg-max decisions within rounding of
-a tie; torch's own float32 composition shows none on these shapes)."""
+a tie; torch's own float32 composition shows none on these shapes).  The check without that
+allowance — every element, ties decided by value, guarded buffers, the block edges — is
+tests/test_bnrp_edges_gpu.py."""
 import argparse
 import copy
 import warnings
