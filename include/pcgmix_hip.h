@@ -607,6 +607,45 @@ int pcgmix_adam_clip_multi_reduce_dev_f32(int n_tensors, float* const* p, const 
 int pcgmix_potes_reduce_f32(const float* partial, float* grads, int G, pcgmix_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Gradient value clipping + SGD update of all parameter tensors of a model.          [device]
+ *
+ * Replaces nn.utils.clip_grad_value_(…, grad_clip) followed by torch.optim.SGD.step()
+ * (train_model.py:404-405, 557-558, 566; dampening 0, no nesterov, no maximize) in one launch per
+ * 32 tensors, with torch's _single_tensor_sgd order of roundings:
+ *   g = clamp(g, -clip, clip)              (clip <= 0: no clipping)
+ *   g = fma(weight_decay, p, g)            (weight_decay != 0)
+ *   b = rn(momentum * b) + g;  g = b       (momentum != 0; two roundings, not an fma)
+ *   p = fma(-lr, g, p)
+ * A zero buffer b makes the first step torch's clone(grad).  p, g, m are HOST arrays of n_tensors
+ * device pointers (m: the momentum buffers), n the HOST array of element counts; p and m are
+ * updated in place, g is read only.  With momentum == 0 the buffers are neither read nor written
+ * and m (or any m[i]) may be NULL; with momentum != 0 a NULL m[i] of a non-empty tensor is
+ * hipErrorInvalidValue.  Negative n[i], NULL tables: hipErrorInvalidValue; empty tensors are skipped.
+ */
+int pcgmix_sgd_clip_multi_f32(int n_tensors, float* const* p, const float* const* g,
+                              float* const* m, const long long* n, float clip, float lr,
+                              float momentum, float weight_decay, pcgmix_stream_t stream);
+
+/* The same update with its scalars in DEVICE memory, for a launch captured in a hipGraph: with
+ * OneCycleLR the reference's SGD runs move lr AND momentum on every step (train_model.py:404-405,
+ * 557-558, 566).  pcgmix_sgd_hyper writes the eight floats {clip, weight_decay, momentum, lr, 0, 0,
+ * 0, 0} (the size of pcgmix_adam_hyper's block; the last four are not read).  The table m must be
+ * given; a NULL m[i] is legal only while the momentum word stays 0 — the kernel updates such a
+ * tensor without momentum whatever the word says.                                              */
+int pcgmix_sgd_hyper(float clip, float lr, float momentum, float weight_decay, float* out8);
+int pcgmix_sgd_clip_multi_dev_f32(int n_tensors, float* const* p, const float* const* g,
+                                  float* const* m, const long long* n, const float* hyper_dev,
+                                  pcgmix_stream_t stream);
+/* ... and with the Potes conv stack's gradient reduction folded in, exactly as
+ * pcgmix_adam_clip_multi_reduce_dev_f32 does it (train_model.py:404-405, 557-558, 566): 212 extra
+ * blocks sum the partial columns in pcgmix_potes_reduce_f32's order (same bits), store grads[e] and
+ * update the element that owns it.  n_tensors <= 32, G >= 1.                                    */
+int pcgmix_sgd_clip_multi_reduce_dev_f32(int n_tensors, float* const* p, const float* const* g,
+                                         float* const* m, const long long* n,
+                                         const float* hyper_dev, const float* partial, float* grads,
+                                         int G, pcgmix_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Potes classifier head, forward and backward.                                       [device]
  *
  * Replaces CNN_potes' Dropout(.25) -> Flatten/concat -> dimreduc Linear(K->20) -> ReLU ->

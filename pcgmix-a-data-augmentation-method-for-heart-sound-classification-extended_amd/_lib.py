@@ -104,6 +104,12 @@ SIGNATURES = {
     "pcgmix_adam_clip_multi_reduce_dev_f32": (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
                                                        _c_int, _ptr]),
     "pcgmix_potes_reduce_f32": (_c_int, [_ptr, _ptr, _c_int, _ptr]),
+    "pcgmix_sgd_hyper": (_c_int, [_c_float] * 4 + [_ptr]),
+    "pcgmix_sgd_clip_multi_f32": (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _c_float, _c_float, _c_float,
+                                           _c_float, _ptr]),
+    "pcgmix_sgd_clip_multi_dev_f32": (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "pcgmix_sgd_clip_multi_reduce_dev_f32": (_c_int, [_c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                                      _c_int, _ptr]),
     "pcgmix_potes_head_fwd_f32": (_c_int, [_ptr, _ptr, _c_float, _c_int, _c_int, _ptr, _ptr, _ptr, _c_float,
                                            _c_int, _ptr, _ptr, _ptr, _ptr, _ptr, _c_int, _c_int, _c_int,
                                            _ptr]),

@@ -5,6 +5,7 @@
 //   adam_clip_kernel        clip_grad_value_ + Adam for one tensor
 //   adam_clip_multi_kernel  the same for every tensor of a model in one launch, optionally with
 //                           that reduce folded in as extra blocks
+//   sgd_clip_multi_kernel   clip_grad_value_ + momentum SGD, the same launch shape
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -146,6 +147,69 @@ __global__ __launch_bounds__(256) void adam_clip_multi_kernel(AdamTable tab, flo
   }
 }
 
+// clip_grad_value_ + torch.optim.SGD (momentum, L2 weight decay; dampening 0, no nesterov) for one
+// element (train_model.py:557-558, 404-405, 566), in torch's _single_tensor_sgd order of roundings:
+//   g = clamp(g, -clip, clip);  g = fma(wd, p, g);  b = rn(mom * b) + g;  p = fma(-lr, b, p)
+// The momentum line is buf.mul_(mom).add_(grad): a rounded product, then a rounded sum — not an
+// fma (the file is compiled with -ffp-contract=off, so the compiler forms none either).  A zero
+// buffer makes the first step torch's clone(grad): mom * 0 + g == g.  m == nullptr or mom == 0:
+// no momentum, the buffer is neither read nor written.
+__device__ __forceinline__ void sgd_clip_update(float& p, float* m, float gi, float clip, float wd,
+                                                float mom, float lr) {
+  if (clip > 0.f) gi = fminf(fmaxf(gi, -clip), clip);
+  const float pi = p;
+  if (wd != 0.f) gi = fmaf(wd, pi, gi);              // grad.add(param, alpha=wd)
+  if (m != nullptr && mom != 0.f) {
+    gi = __fmul_rn(mom, *m) + gi;                     // buf.mul_(mom).add_(grad)
+    *m = gi;
+  }
+  p = fmaf(-lr, gi, pi);                             // param.add_(grad, alpha=-lr)
+}
+
+// The SGD twin of adam_clip_multi_kernel: same table (v unused), same block ownership, same
+// optional kNGrad reduction blocks behind the table's own.  hyper != nullptr: {clip, wd, momentum,
+// lr} are read from device memory (pcgmix_sgd_hyper's layout) — OneCycleLR moves lr AND momentum
+// between the replays of a captured launch.
+__global__ __launch_bounds__(256) void sgd_clip_multi_kernel(AdamTable tab, float clip, float wd,
+                                                             float mom, float lr,
+                                                             const float* __restrict__ hyper,
+                                                             const float* __restrict__ partial,
+                                                             float* __restrict__ grads, int G,
+                                                             int red_first) {
+  if (hyper) {
+    clip = hyper[0]; wd = hyper[1]; mom = hyper[2]; lr = hyper[3];
+  }
+  if (partial && (int)blockIdx.x >= red_first) {
+    __shared__ float red[kPotThreads];
+    const int e = (int)blockIdx.x - red_first;
+    const float gi = potes_reduce_column(partial, G, e, red);
+    if (threadIdx.x != 0) return;
+    grads[e] = gi;
+    const float* ge = grads + e;
+    for (int t = 0; t < tab.count; ++t) {
+      if (ge >= tab.g[t] && ge < tab.g[t] + tab.n[t]) {
+        const long long i = ge - tab.g[t];
+        sgd_clip_update(tab.p[t][i], tab.m[t] ? tab.m[t] + i : nullptr, gi, clip, wd, mom, lr);
+        return;
+      }
+    }
+    return;
+  }
+  int t = 0;
+  while (t + 1 < tab.count && (int)blockIdx.x >= tab.blk_start[t + 1]) ++t;
+  float* __restrict__ p = tab.p[t];
+  const float* __restrict__ g = tab.g[t];
+  float* __restrict__ m = tab.m[t];
+  const long long n = tab.n[t];
+  const long long base = (long long)((int)blockIdx.x - tab.blk_start[t]) * kAdamEPB;
+#pragma unroll
+  for (int j = 0; j < kAdamEPB / 256; ++j) {
+    const long long i = base + j * 256 + threadIdx.x;
+    if (i >= n) break;
+    sgd_clip_update(p[i], m ? m + i : nullptr, g[i], clip, wd, mom, lr);
+  }
+}
+
 }  // namespace pcgmix
 
 extern "C" int pcgmix_adam_hyper(float clip, float lr, float beta1, float beta2, float eps,
@@ -257,4 +321,88 @@ extern "C" int pcgmix_adam_clip_f32(float* p, const float* g, float* m, float* v
                      reinterpret_cast<hipStream_t>(stream), p, g, m, v, n, h8[0], h8[1], h8[2],
                      h8[3], h8[4], h8[5], h8[6], h8[7]);
   return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------- SGD
+extern "C" int pcgmix_sgd_hyper(float clip, float lr, float momentum, float weight_decay,
+                                float* out8) {
+  if (!out8) return hipErrorInvalidValue;
+  out8[0] = clip;
+  out8[1] = weight_decay;
+  out8[2] = momentum;
+  out8[3] = lr;
+  out8[4] = out8[5] = out8[6] = out8[7] = 0.f;
+  return hipSuccess;
+}
+
+// adam_multi_launch's table fill for the SGD kernel.  m == nullptr, or a null m[i]: that tensor
+// has no momentum buffer (need_m: refuse it, the momentum is known to be non-zero).
+static int sgd_multi_launch(int n_tensors, float* const* p, const float* const* g, float* const* m,
+                            const long long* n, const float* h8, const float* hyper_dev, bool need_m,
+                            hipStream_t stream, const float* partial = nullptr,
+                            float* grads = nullptr, int G = 0) {
+  using namespace pcgmix;
+  if (partial && n_tensors > kAdamMaxTensors) return hipErrorInvalidValue;   // one table, one launch
+  for (int first = 0; first < n_tensors; first += kAdamMaxTensors) {
+    AdamTable tab;
+    tab.count = 0;
+    int blocks = 0;
+    const int last = first + kAdamMaxTensors < n_tensors ? first + kAdamMaxTensors : n_tensors;
+    for (int i = first; i < last; ++i) {
+      float* const mi = m ? m[i] : nullptr;
+      if (n[i] < 0 || (n[i] > 0 && (!p[i] || !g[i] || (need_m && !mi)))) return hipErrorInvalidValue;
+      if (n[i] == 0) continue;
+      // tensors whose gradient lives in grads[0 .. kNGrad) are updated by the reduction blocks
+      const bool deferred = partial && g[i] >= grads && g[i] < grads + kNGrad;
+      const long long nb = deferred ? 0 : (n[i] + kAdamEPB - 1) / kAdamEPB;
+      if (nb > (1ll << 30) - blocks) return hipErrorInvalidValue;
+      const int k = tab.count++;
+      tab.p[k] = p[i]; tab.g[k] = g[i]; tab.m[k] = mi; tab.v[k] = nullptr; tab.n[k] = n[i];
+      tab.blk_start[k] = blocks;
+      blocks += (int)nb;
+    }
+    if (tab.count == 0) continue;
+    tab.blk_start[tab.count] = blocks;
+    const int red_first = blocks;
+    if (partial) blocks += kNGrad;
+    hipLaunchKernelGGL(sgd_clip_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tab,
+                       h8[0], h8[1], h8[2], h8[3], hyper_dev, partial, grads, G, red_first);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return (int)err;
+  }
+  return hipSuccess;
+}
+
+extern "C" int pcgmix_sgd_clip_multi_f32(int n_tensors, float* const* p, const float* const* g,
+                                         float* const* m, const long long* n, float clip, float lr,
+                                         float momentum, float weight_decay,
+                                         pcgmix_stream_t stream) {
+  if (n_tensors < 0 || (n_tensors > 0 && (!p || !g || !n || (!m && momentum != 0.f))))
+    return hipErrorInvalidValue;
+  float h8[8];
+  pcgmix_sgd_hyper(clip, lr, momentum, weight_decay, h8);
+  return sgd_multi_launch(n_tensors, p, g, momentum != 0.f ? m : nullptr, n, h8, nullptr,
+                          momentum != 0.f, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pcgmix_sgd_clip_multi_dev_f32(int n_tensors, float* const* p, const float* const* g,
+                                             float* const* m, const long long* n,
+                                             const float* hyper_dev, pcgmix_stream_t stream) {
+  if (n_tensors < 0 || !hyper_dev || (n_tensors > 0 && (!p || !g || !m || !n)))
+    return hipErrorInvalidValue;
+  const float zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  return sgd_multi_launch(n_tensors, p, g, m, n, zero8, hyper_dev, false,
+                          reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" int pcgmix_sgd_clip_multi_reduce_dev_f32(int n_tensors, float* const* p,
+                                                    const float* const* g, float* const* m,
+                                                    const long long* n, const float* hyper_dev,
+                                                    const float* partial, float* grads, int G,
+                                                    pcgmix_stream_t stream) {
+  if (n_tensors <= 0 || !hyper_dev || !p || !g || !m || !n || !partial || !grads || G <= 0)
+    return hipErrorInvalidValue;
+  const float zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  return sgd_multi_launch(n_tensors, p, g, m, n, zero8, hyper_dev, false,
+                          reinterpret_cast<hipStream_t>(stream), partial, grads, G);
 }

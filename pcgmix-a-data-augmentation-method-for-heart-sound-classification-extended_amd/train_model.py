@@ -347,6 +347,156 @@ class ClipAdam(torch.optim.Adam):
         return super().state_dict()
 
 
+class ClipSGD(torch.optim.SGD):
+    """``clip_grad_value_(clip)`` + ``torch.optim.SGD`` (momentum, L2 weight decay) as one HIP launch
+    for all parameters of a group (``pcgmix_sgd_clip_multi_f32``; train_model.py:404-405, 557-558,
+    566).  Same state (``momentum_buffer``) and param-group keys as torch's SGD, so OneCycleLR cycles
+    ``lr`` and ``momentum`` on it unchanged and checkpoints interchange.  With momentum 0 no buffers
+    exist and the state stays empty, as torch's does.  Gradients are NOT modified.  ``dampening``,
+    ``nesterov`` and ``maximize`` are refused: the kernel implements the reference's defaults."""
+
+    REDUCE_LAUNCH = "pcgmix_sgd_clip_multi_reduce_dev_f32"    # the tape's fifth launch (GraphedTrainStep)
+
+    def __init__(self, params, lr, weight_decay=0.0, clip_value=0.0, momentum=0.0, dampening=0.0,
+                 nesterov=False, maximize=False):
+        self._refuse(dict(dampening=dampening, nesterov=nesterov, maximize=maximize))
+        super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self.clip_value = float(clip_value or 0.0)
+        self._tables = {}
+        self._cap_params, self._cap_grads, self._cap_buffers = None, None, False
+
+    @staticmethod
+    def _refuse(group):
+        if group.get("dampening", 0) != 0 or group.get("nesterov") or group.get("maximize"):
+            raise NotImplementedError("ClipSGD: dampening, nesterov and maximize are not implemented "
+                                      "(the reference trains with torch.optim.SGD's defaults)")
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._tables = {}                      # the buffers were replaced
+        for group in self.param_groups:
+            self._refuse(group)
+            for p in group["params"]:          # torch's buffer is a clone of the GRADIENT: its layout
+                buf = self._buf(p)
+                if buf is not None and buf.stride() != p.stride():
+                    self.state[p]["momentum_buffer"] = torch.empty_like(p).copy_(buf)
+        if getattr(self, "_cap_params", None):
+            raise RuntimeError("ClipSGD: load the state before the step is captured (the graph "
+                               "holds the addresses of the old momentum buffers)")
+
+    def _buf(self, p):
+        return self.state.get(p, {}).get("momentum_buffer")     # (no state entry is created by asking)
+
+    def _init_state(self, params):
+        for p in params:
+            if self._buf(p) is None:
+                self.state[p]["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+
+    def _table(self, gi, live, grads, with_m):
+        """Host pointer tables of the group's static tensors (rebuilt when a tensor moved or a
+        buffer appeared): (key, p, m or None, n, g)."""
+        import ctypes
+        bufs = [self._buf(p) for p in live] if with_m else []
+        key = tuple(p.data_ptr() for p in live) + tuple(0 if b is None else b.data_ptr() for b in bufs)
+        tab = self._tables.get(gi)
+        if tab is None or tab[0] != key:
+            n = len(live)
+            arr = ctypes.c_void_p * n
+            tab = (key, arr(*key[:n]), arr(*[b or None for b in key[n:]]) if with_m else None,
+                   (ctypes.c_longlong * n)(*[p.numel() for p in live]), arr())
+            self._tables[gi] = tab
+        gptr = tab[4]
+        for i, g in enumerate(grads):
+            gptr[i] = g.data_ptr()
+        return tab
+
+    _dense_grads = staticmethod(ClipAdam._dense_grads)
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        import ctypes
+        from . import _lib
+        lib = _lib.load()
+        for gi, group in enumerate(self.param_groups):
+            self._refuse(group)
+            live = [p for p in group["params"] if p.grad is not None]
+            if not live:
+                continue
+            mom = float(group["momentum"])
+            if mom != 0.0:
+                self._init_state(live)
+            tab = self._table(gi, live, self._dense_grads(live), mom != 0.0)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(live[0].device).cuda_stream)
+            _lib.check(lib.pcgmix_sgd_clip_multi_f32(
+                len(live), tab[1], tab[4], tab[2], tab[3], ctypes.c_float(self.clip_value),
+                ctypes.c_float(float(group["lr"])), ctypes.c_float(mom),
+                ctypes.c_float(group["weight_decay"]), stream), "pcgmix_sgd_clip_multi_f32")
+        return None
+
+    # ---- the update as a node of a captured training step: ClipAdam's protocol -----------------
+    # OneCycleLR moves lr AND momentum every step, so the captured launch reads {clip, wd, momentum,
+    # lr} from device memory (``pcgmix_sgd_clip_multi_dev_f32``); ``next_hyper`` writes them on the
+    # host for the coming replay.  SGD has no step count: nothing to carry between captures.
+    def can_capture(self) -> bool:
+        return len(self.param_groups) == 1
+
+    def prepare_capture(self, params):
+        """Before the capture: allocate the momentum buffers of ``params`` when the group's momentum
+        is not 0 (an allocation inside the capture would be re-zeroed by every replay)."""
+        params = list(params)
+        self._refuse(self.param_groups[0])
+        if float(self.param_groups[0]["momentum"]) != 0.0:
+            self._init_state(params)
+        self._cap_params = params
+        self._cap_buffers = all(self._buf(p) is not None for p in params)
+
+    @torch.no_grad()
+    def capture_update(self, hyper_dev: torch.Tensor, deferred: Optional[dict] = None):
+        """Inside the capture, after backward: the update of all ``prepare_capture`` tensors, with
+        the Potes conv stack's deferred gradient reduction folded in under ClipAdam's conditions
+        (see ``ClipAdam.capture_update``), else launched on its own first."""
+        import ctypes
+        from . import _lib
+        lib = _lib.load()
+        live = self._cap_params
+        if any(p.grad is None for p in live):
+            raise RuntimeError("ClipSGD.capture_update: a prepared parameter has no gradient")
+        self._cap_grads = self._dense_grads(live)            # keep graph memory referenced
+        tab = self._table(0, live, self._cap_grads, True)    # (NULL entries: captured without momentum)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(live[0].device).cuda_stream)
+        if deferred and "partial" in deferred:
+            grads, partial, G = deferred["grads"], deferred["partial"], int(deferred["G"])
+            lo, hi = grads.data_ptr(), grads.data_ptr() + grads.numel() * 4
+            covered = sum(g.numel() for g in self._cap_grads if lo <= g.data_ptr() < hi)
+            self._cap_deferred = (partial, grads)            # referenced by the graph
+            if covered == grads.numel() and len(live) <= 32:
+                _lib.check(lib.pcgmix_sgd_clip_multi_reduce_dev_f32(
+                    len(live), tab[1], tab[4], tab[2], tab[3], hyper_dev.data_ptr(),
+                    partial.data_ptr(), grads.data_ptr(), G, stream), self.REDUCE_LAUNCH)
+                return
+            _lib.check(lib.pcgmix_potes_reduce_f32(partial.data_ptr(), grads.data_ptr(), G, stream),
+                       "pcgmix_potes_reduce_f32")
+        _lib.check(lib.pcgmix_sgd_clip_multi_dev_f32(
+            len(live), tab[1], tab[4], tab[2], tab[3], hyper_dev.data_ptr(), stream),
+            "pcgmix_sgd_clip_multi_dev_f32")
+
+    def next_hyper(self, out8) -> None:
+        """Host: the scalars of the NEXT update into ``out8`` (float32[8], numpy), from the param
+        group as the scheduler left it."""
+        import ctypes
+        from . import _lib
+        g = self.param_groups[0]
+        self._refuse(g)
+        if float(g["momentum"]) != 0.0 and not self._cap_buffers:
+            raise RuntimeError("ClipSGD: momentum became non-zero on a step that was captured without "
+                               "momentum buffers; capture the step again")
+        self._opt_called = True                  # what LRScheduler's wrapper of step() records
+        _lib.check(_lib.load().pcgmix_sgd_hyper(
+            ctypes.c_float(self.clip_value), ctypes.c_float(float(g["lr"])),
+            ctypes.c_float(float(g["momentum"])), ctypes.c_float(g["weight_decay"]),
+            out8.ctypes.data), "pcgmix_sgd_hyper")
+
+
 def selc_turning_point(args) -> int:
     """train_model.py:394-402."""
     if "SELC" in args.method and ("mixup" in args.method or "base" in args.method):
@@ -410,16 +560,26 @@ def build_model(args) -> nn.Module:
     raise NotImplementedError(f"model {args.model!r} is outside the PCGmix hot path")
 
 
+FUSED_SGD = True     # op='SGD' through ClipSGD where it applies; False: torch.optim.SGD (A/B timing, tests)
+
+
 def make_optimizer(args, model: nn.Module):
     """train_model.py:404-410."""
     params = [p for p in model.parameters() if p.requires_grad]
+
+    def dense(p):       # any non-overlapping dense layout: the kernel walks raw memory
+        order = sorted(range(p.dim()), key=lambda d: (-p.stride(d), -p.size(d)))
+        return p.numel() == 0 or p.permute(order).is_contiguous()
+    hip_path = all(p.is_cuda and p.dtype == torch.float32 and dense(p) for p in params)
     if args.op == "SGD":
-        opt = torch.optim.SGD(params, lr=args.lr_max, weight_decay=args.weight_decay)
+        if FUSED_SGD and hip_path:
+            # clip + SGD in one HIP launch (train_step then skips clip_grad_value_)
+            opt = ClipSGD(params, lr=args.lr_max, weight_decay=args.weight_decay,
+                          clip_value=args.grad_clip)
+        else:
+            opt = torch.optim.SGD(params, lr=args.lr_max, weight_decay=args.weight_decay)
     elif args.op == "adam":
-        def dense(p):       # any non-overlapping dense layout: the kernel walks raw memory
-            order = sorted(range(p.dim()), key=lambda d: (-p.stride(d), -p.size(d)))
-            return p.numel() == 0 or p.permute(order).is_contiguous()
-        if all(p.is_cuda and p.dtype == torch.float32 and dense(p) for p in params):
+        if hip_path:
             # clip + Adam in one HIP pass per tensor (train_step then skips clip_grad_value_)
             opt = ClipAdam(params, lr=args.lr_max, weight_decay=args.weight_decay,
                            clip_value=args.grad_clip)
@@ -642,8 +802,8 @@ def selc_fused_model(model, criterion, data, target_ohe, epoch):
 
 
 def clips_outside_optimizer(args, optimizer) -> bool:
-    """``clip_grad_value_`` as a pass of its own: ClipAdam clips in its kernel."""
-    return bool(args.grad_clip) and not isinstance(optimizer, ClipAdam)
+    """``clip_grad_value_`` as a pass of its own: ClipAdam and ClipSGD clip in their kernels."""
+    return bool(args.grad_clip) and not isinstance(optimizer, (ClipAdam, ClipSGD))
 
 
 def add_stats(stats: dict, loss, out, truth) -> None:
@@ -718,7 +878,7 @@ class _StaticBlock:
 
         words 0-1     dropout key (bits)
         words 2-3     unused
-        words 4-11    the eight Adam scalars (``ClipAdam.next_hyper``)
+        words 4-11    the optimiser's eight scalars (``ClipAdam.next_hyper`` / ``ClipSGD.next_hyper``)
         from word 12  the class labels, one byte each, padded to a 16-byte granule
         behind them   the float targets (B, classes), padded to 4 words
 
@@ -754,7 +914,7 @@ class GraphedTrainStep:
     splices, and the saliency-guided ones around the frozen model's own captured pass) and the
     scheduler.  The ClipAdam update is the graph's last node: OneCycleLR moves lr AND beta1 every
     step, so the captured launch reads its eight scalars from device memory (they travel with the
-    step's payload).  Under torch.distributed pass the UNWRAPPED model: gradients are packed into
+    step's payload); with op='SGD' ClipSGD takes the same place (lr and momentum move).  Under torch.distributed pass the UNWRAPPED model: gradients are packed into
     one flat buffer inside the graph, averaged by one eager all-reduce after the replay
     (``FlatGradSync``) — DDP's hooks cannot be captured — and the update is a SECOND small graph
     replayed behind the collective.  Needs static shapes (the loaders use drop_last=True).
@@ -803,8 +963,9 @@ class GraphedTrainStep:
         self.rnd = self._dropout_buffer(batch_size)
         # The optimiser update is the graph's last node when nothing has to happen between
         # backward and update (no gradient all-reduce) and the optimiser can read its scalars
-        # from the static block (ClipAdam).
-        self.adam_in_graph = isinstance(optimizer, ClipAdam) and optimizer.can_capture() \
+        # from the static block (ClipAdam, ClipSGD).
+        # (``adam_in_graph``: the name is older than ClipSGD, which takes the same place)
+        self.adam_in_graph = isinstance(optimizer, (ClipAdam, ClipSGD)) and optimizer.can_capture() \
             and device.type == "cuda"
         self.graph_update = None        # with a sync: the update as a second graph behind the all-reduce
         self._warm_up()
@@ -929,7 +1090,9 @@ class GraphedTrainStep:
     def _adopt_tape(self, tape, fold) -> None:
         """``self.tape``: the recorded launches when they are the whole capture, else None."""
         self.tape = None
-        if tape is not None and [t[0] for t in tape] == list(self._TAPE_LAUNCHES) \
+        # the fifth launch is the optimiser's own: ClipAdam's (in _TAPE_LAUNCHES) or ClipSGD's
+        want = self._TAPE_LAUNCHES[:4] + (getattr(self.opt, "REDUCE_LAUNCH", self._TAPE_LAUNCHES[4]),)
+        if tape is not None and [t[0] for t in tape] == list(want) \
                 and self._tape_covers_capture(tape, fold):
             import ctypes
             # pointer tables are snapshotted: ClipAdam re-uses its ctypes arrays for the next capture
