@@ -1,7 +1,8 @@
 """The narrow Potes conv stacks (layers [1,1] and [2,1], csrc/pcgmix_potes_narrow.hip) against the
 same stack through torch/MIOpen ops on the same device (``m.fused = False``) in float32 — method and
 tolerances of tests/test_potes_gpu.py — plus the ABI's refusals, the dropout bytes, the training
-steps of 'Potes0.1' and the reference's recorded logits (tests/golden/model_sizes.npz)."""
+steps of 'Potes0.1' and the reference's recorded logits (tests/golden/model_sizes.npz).
+Tile edges, routing bytes and exact arithmetic against float64: tests/test_potes_narrow_edges_gpu.py."""
 import argparse
 import ctypes
 import os
