@@ -208,6 +208,34 @@ int pcgmix_saliency_post_f32(const float* grad, const int32_t* frames, float* sa
                              int ksize, double sigma, int B, int C, int T,
                              pcgmix_stream_t stream);
 
+/* saliency.saliency_map(), saliency.py:147-201, after the model's backward pass, for a batch in
+ * one launch (the reference: a Python loop over samples, four interpolate + repeat_interleave
+ * calls and a host copy per sample).  As pcgmix_saliency_post_f32 up to the Gaussian, then:
+ * the tail is NOT zeroed again (smoothed values up to ksize/2 samples past frames[b][4] stay and
+ * take part in the minimum and maximum) -> per row (s - min) / max(s - min), NaN -> 0 -> sal.
+ * The four heart states k, [lo, hi) = [f[k], f[k+1]) of length L, are then summarised in
+ * n = n_bins[k] values by torch's linear interpolation with align_corners=False (bin_tensor,
+ * saliency.py:118-130), all in float32:
+ *     scale = float(L) / float(n);  src = max(scale * (i + 0.5f) - 0.5f, 0)
+ *     i0 = (int)src;  i1 = min(i0 + 1, L - 1);  l1 = src - i0;  l0 = 1 - l1
+ *     value_i = fmaf(l0, s[lo + i0], l1 * s[lo + i1])
+ * and every value is held for spb = ceil(L / n) samples:
+ *
+ *   sal_bins    device, (B, T) out: value_{(t - lo) / spb} for lo <= t < hi, 0 outside [f[0], f[4])
+ *               (with L < n only the first L values appear here, all n are reported below)
+ *   bin_values  device, (B, N) out, N = n_bins[0] + .. + n_bins[3] (the reference: 1, 4, 1, 8)
+ *   bin_frames  device, (B, N + 1) int32 out: lo + i * spb per bin, then f[4]
+ *   n_bins      HOST, 4 values >= 1 with N <= 64
+ *   ksize       odd, <= 255 (the reference ends up with 57, sigma 7.54, saliency.py:156)
+ *
+ * grad, frames, sal, T and the refusals as for pcgmix_saliency_post_f32.  frames must be
+ * non-decreasing within [0, T] (they are clamped to that for memory safety); a state of length 0
+ * reports zeros — the reference's interpolate raises there, and so does the Python layer.
+ * The same bits on every call.                                                       [device] */
+int pcgmix_saliency_map_f32(const float* grad, const int32_t* frames, float* sal, float* sal_bins,
+                            float* bin_values, int32_t* bin_frames, int ksize, double sigma,
+                            const int32_t* n_bins, int B, int C, int T, pcgmix_stream_t stream);
+
 /* The spectrogram branch of the same function (saliency.py:93-113, dim = 2).  grad (B, F, W)
  * float32 (the single image channel folded away), frames (B,5) in spectrogram columns, sal (B, W):
  * |grad| -> columns t >= f[4] zeroed -> sum over the F frequency rows -> `ksize`-tap Gaussian along

@@ -41,6 +41,8 @@ SIGNATURES = {
                                      _ptr, _c_int, _c_int, _c_int, _ptr]),
     "pcgmix_saliency_post_f32": (_c_int, [_ptr, _ptr, _ptr, _c_int, ctypes.c_double, _c_int, _c_int,
                                           _c_int, _ptr]),
+    "pcgmix_saliency_map_f32": (_c_int, [_ptr] * 6 + [_c_int, ctypes.c_double, _ptr, _c_int, _c_int, _c_int,
+                                         _ptr]),
     "pcgmix_saliency_post2d_f32": (_c_int, [_ptr, _ptr, _ptr, _c_int, ctypes.c_double, _c_int, _c_int,
                                             _c_int, _ptr]),
     "pcgmix_potes_saliency_pass_f32": (_c_int, [_ptr] * 18 + [_c_int, ctypes.c_double, _c_int, _c_int, _c_int, _c_int,

@@ -2,6 +2,8 @@
 //
 //  saliency_post_kernel   saliency.py:63-91   |grad| -> zero tail -> sum channels -> Gaussian ->
 //                                             zero tail -> per-row min/max normalisation
+//    <KS, MAP = true>     saliency.py:147-201 the same without the second zeroing, plus the
+//                                             per-heart-state bins of saliency_map()
 //  salopt_disp_kernel     augmentations.py:60-128, 210-287   first strict argmax over the
 //                                             displacement d of a float32 objective summed in
 //                                             numpy's pairwise order
@@ -61,10 +63,25 @@ __device__ long long g_salpost_clock[1024 * 8];
 #define PCGMIX_SCLOCK(i) do { } while (0)
 #endif
 
-template <int KS>
+// MAP: saliency_map() of the reference (saliency.py:147-201) instead of get_saliency_maps(): the
+// smoothed row is NOT zeroed behind the cycle a second time, and the normalised row, which is in
+// LDS anyway, is summarised per heart state before the block ends: state k = [f[k], f[k+1]) of
+// length L is resampled to n[k] values by torch's linear interpolation (align_corners=False,
+// saliency.py:123) and every value is held for spb = ceil(L / n[k]) samples (:127).  The
+// n[0] + .. + n[3] <= kMaxBins values of a row are the only step that crosses lanes.
+constexpr int kMaxBins = 64;
+struct SalMapOut {
+  float* sal_bins;       // (B, T)
+  float* bin_values;     // (B, sum n)
+  int32_t* bin_frames;   // (B, sum n + 1)
+  int n[4];
+};
+struct SalNoMap { int unused; };
+
+template <int KS, bool MAP = false>
 __global__ __launch_bounds__(kSalThreads) void saliency_post_kernel(
     const float* __restrict__ grad, const int32_t* __restrict__ frames, float* __restrict__ sal,
-    Taps taps, int ksize, int B, int C, int T) {
+    Taps taps, int ksize, int B, int C, int T, const std::conditional_t<MAP, SalMapOut, SalNoMap> map) {
   extern __shared__ __align__(16) float smem[];
   __shared__ float red[kSalThreads / 64];
   const int b = blockIdx.x;
@@ -140,7 +157,7 @@ __global__ __launch_bounds__(kSalThreads) void saliency_post_kernel(
       for (int u = 0; u < 8; ++u) {
         const int t = t0 + u;
         if (t < T) {
-          const float v = t < f4 ? acc[u] : 0.f;   // saliency.py:78-79 zeroes the tail again
+          const float v = (MAP || t < f4) ? acc[u] : 0.f;   // saliency.py:78-79 zeroes the tail again
           s[t] = v;
           lmin = fminf(lmin, v);
         }
@@ -149,7 +166,7 @@ __global__ __launch_bounds__(kSalThreads) void saliency_post_kernel(
   } else {
     for (int t = threadIdx.x; t < T; t += kSalThreads) {
       float acc = 0.f;
-      if (t < f4)
+      if (MAP || t < f4)
         for (int j = 0; j < ksize; ++j) acc = fmaf(taps.w[j], a[t + j], acc);
       s[t] = acc;
       lmin = fminf(lmin, acc);
@@ -169,9 +186,69 @@ __global__ __launch_bounds__(kSalThreads) void saliency_post_kernel(
   for (int t = threadIdx.x; t < T; t += kSalThreads) {
     float v = __fdiv_rn(s[t], rmax);  // saliency.py:84; 0/0 -> NaN -> 0 (saliency.py:87)
     if (v != v) v = 0.f;
+    if (MAP) s[t] = v;
     __builtin_nontemporal_store(v, sal + (size_t)b * T + t);
   }
   PCGMIX_SCLOCK(5);
+  if constexpr (MAP) {
+    __shared__ float vals[kMaxBins];
+    // Per state, looked up by a run-time k (in LDS: a run-time index into the kernel arguments goes
+    // through scratch): first sample (sf[4]: the cycle's end), bin count, first bin, samples per
+    // bin.  The boundaries are clamped to a non-decreasing sequence inside the row (memory safety;
+    // the Python layer refuses anything else); an empty state reports zeros.
+    __shared__ int sf[5], sn[4], soff[4], sspb[4];
+    if (threadIdx.x < 4) {
+      const int k = threadIdx.x;
+      int prev = 0, lo = 0, hi = 0, n = 1, off = 0;
+#pragma unroll
+      for (int kk = 0; kk < 5; ++kk) {
+        const int v = frames[b * 5 + kk];
+        prev = v < prev ? prev : (v > T ? T : v);
+        if (kk == k) lo = prev;
+        if (kk == k + 1) hi = prev;
+        if (kk < 4 && kk < k) off += map.n[kk];
+        if (kk < 4 && kk == k) n = map.n[kk];
+      }
+      sf[k] = lo;
+      if (k == 3) sf[4] = hi;
+      sn[k] = n;
+      soff[k] = off;
+      sspb[k] = (hi - lo + n - 1) / n;                // saliency.py:121
+    }
+    const int ntot = map.n[0] + map.n[1] + map.n[2] + map.n[3];
+    __syncthreads();                                  // s[] holds the normalised row
+    if ((int)threadIdx.x < ntot) {
+      const int j = threadIdx.x;
+      const int k = (j >= soff[1]) + (j >= soff[2]) + (j >= soff[3]);
+      const int lo = sf[k], L = sf[k + 1] - lo, n = sn[k], spb = sspb[k];
+      const int i = j - soff[k];
+      float v = 0.f;
+      if (L > 0) {
+        // at::native area_pixel_compute_source_index / compute_indices_weights, float32
+        const float scale = __fdiv_rn((float)L, (float)n);
+        float src = __fsub_rn(__fmul_rn(scale, __fadd_rn((float)i, 0.5f)), 0.5f);
+        src = src < 0.f ? 0.f : src;
+        int i0 = (int)src;
+        i0 = i0 > L - 1 ? L - 1 : i0;
+        const int i1 = i0 + 1 > L - 1 ? L - 1 : i0 + 1;
+        const float l1 = __fsub_rn(src, (float)i0), l0 = __fsub_rn(1.f, l1);
+        v = fmaf(l0, s[lo + i0], __fmul_rn(l1, s[lo + i1]));
+      }
+      vals[j] = v;
+      map.bin_values[(size_t)b * ntot + j] = v;
+      map.bin_frames[(size_t)b * (ntot + 1) + j] = lo + i * spb;       // saliency.py:129
+      if (j == 0) map.bin_frames[(size_t)b * (ntot + 1) + ntot] = sf[4];  // saliency.py:196
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < T; t += kSalThreads) {
+      float v = 0.f;                                  // saliency.py:170: zeros outside the cycle
+      if (t >= sf[0] && t < sf[4]) {
+        const int k = (t >= sf[1]) + (t >= sf[2]) + (t >= sf[3]);   // skips empty states
+        v = vals[soff[k] + (t - sf[k]) / sspb[k]];    // repeat_interleave(spb)[:L], saliency.py:127
+      }
+      __builtin_nontemporal_store(v, map.sal_bins + (size_t)b * T + t);
+    }
+  }
 }
 
 // Spectrogram saliency (saliency.py:93-113, dim = 2): |grad| of a (F, W) image -> zero the columns
@@ -679,18 +756,9 @@ extern "C" int pcgmix_disp_phase_clock(long long* out, int n_blocks) {
 }
 #endif
 
-extern "C" int pcgmix_saliency_post_f32(const float* grad, const int32_t* frames, float* sal,
-                                        int ksize, double sigma, int B, int C, int T,
-                                        pcgmix_stream_t stream) {
-  using namespace pcgmix;
-  if (!grad || !frames || !sal) return hipErrorInvalidValue;
-  if (B < 0 || C <= 0 || T <= 0 || ksize < 1 || ksize > kMaxTaps || !(ksize & 1) || !(sigma > 0))
-    return hipErrorInvalidValue;
-  if (B == 0) return hipSuccess;
-  const size_t a_len = ((size_t)T + ksize - 1 + 8 + 3) & ~(size_t)3;
-  const size_t lds = sizeof(float) * (a_len + (size_t)T);
-  if (lds > 150 * 1024) return hipErrorInvalidValue;
-  // gaussian_kernel(), saliency.py:15-18: Python float64 arithmetic, then torch.FloatTensor
+namespace pcgmix {
+// gaussian_kernel(), saliency.py:15-18: Python float64 arithmetic, then torch.FloatTensor
+static Taps gaussian_taps(int ksize, double sigma) {
   Taps taps;
   const int half = ksize / 2;
   for (int j = 0; j < ksize; ++j) {
@@ -699,22 +767,67 @@ extern "C" int pcgmix_saliency_post_f32(const float* grad, const int32_t* frames
     taps.w[j] = (float)w;
   }
   for (int j = ksize; j < kMaxTaps; ++j) taps.w[j] = 0.f;
-  static unsigned long long lds_ok101 = 0, lds_ok0 = 0;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (ksize == 101) {             // the reference's gauss_k_n (augmentations.py:966)
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(saliency_post_kernel<101>),
-                                       &lds_ok101, 150 * 1024))
-      return (int)e;
-    hipLaunchKernelGGL(saliency_post_kernel<101>, dim3((unsigned)B), dim3(kSalThreads), lds, st, grad,
-                       frames, sal, taps, ksize, B, C, T);
-  } else {
-    if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(saliency_post_kernel<0>),
-                                       &lds_ok0, 150 * 1024))
-      return (int)e;
-    hipLaunchKernelGGL(saliency_post_kernel<0>, dim3((unsigned)B), dim3(kSalThreads), lds, st, grad,
-                       frames, sal, taps, ksize, B, C, T);
-  }
+  return taps;
+}
+
+static size_t sal_post_lds_bytes(int ksize, int T) {
+  const size_t a_len = ((size_t)T + ksize - 1 + 8 + 3) & ~(size_t)3;
+  return sizeof(float) * (a_len + (size_t)T);
+}
+
+static bool sal_post_args_ok(const float* grad, const int32_t* frames, const float* sal, int ksize,
+                             double sigma, int B, int C, int T) {
+  if (!grad || !frames || !sal) return false;
+  if (B < 0 || C <= 0 || T <= 0 || ksize < 1 || ksize > kMaxTaps || !(ksize & 1) || !(sigma > 0))
+    return false;
+  return sal_post_lds_bytes(ksize, T) <= 150 * 1024;
+}
+
+template <int KS, bool MAP>
+static int launch_saliency_post(const float* grad, const int32_t* frames, float* sal, int ksize,
+                                double sigma, int B, int C, int T, hipStream_t st,
+                                const std::conditional_t<MAP, SalMapOut, SalNoMap>& map) {
+  static unsigned long long lds_ok = 0;
+  auto kern = saliency_post_kernel<KS, MAP>;
+  if (hipError_t e = allow_large_lds(reinterpret_cast<const void*>(kern), &lds_ok, 150 * 1024))
+    return (int)e;
+  hipLaunchKernelGGL(kern, dim3((unsigned)B), dim3(kSalThreads), sal_post_lds_bytes(ksize, T), st, grad,
+                     frames, sal, gaussian_taps(ksize, sigma), ksize, B, C, T, map);
   return (int)hipGetLastError();
+}
+}  // namespace pcgmix
+
+extern "C" int pcgmix_saliency_post_f32(const float* grad, const int32_t* frames, float* sal,
+                                        int ksize, double sigma, int B, int C, int T,
+                                        pcgmix_stream_t stream) {
+  using namespace pcgmix;
+  if (!sal_post_args_ok(grad, frames, sal, ksize, sigma, B, C, T)) return hipErrorInvalidValue;
+  if (B == 0) return hipSuccess;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (ksize == 101)               // the reference's gauss_k_n (augmentations.py:966)
+    return launch_saliency_post<101, false>(grad, frames, sal, ksize, sigma, B, C, T, st, SalNoMap{0});
+  return launch_saliency_post<0, false>(grad, frames, sal, ksize, sigma, B, C, T, st, SalNoMap{0});
+}
+
+extern "C" int pcgmix_saliency_map_f32(const float* grad, const int32_t* frames, float* sal,
+                                       float* sal_bins, float* bin_values, int32_t* bin_frames,
+                                       int ksize, double sigma, const int32_t* n_bins, int B, int C,
+                                       int T, pcgmix_stream_t stream) {
+  using namespace pcgmix;
+  if (!sal_post_args_ok(grad, frames, sal, ksize, sigma, B, C, T)) return hipErrorInvalidValue;
+  if (!sal_bins || !bin_values || !bin_frames || !n_bins) return hipErrorInvalidValue;
+  SalMapOut map{sal_bins, bin_values, bin_frames, {n_bins[0], n_bins[1], n_bins[2], n_bins[3]}};
+  int ntot = 0;
+  for (int k = 0; k < 4; ++k) {
+    if (map.n[k] < 1 || map.n[k] > kMaxBins) return hipErrorInvalidValue;
+    ntot += map.n[k];
+  }
+  if (ntot > kMaxBins) return hipErrorInvalidValue;
+  if (B == 0) return hipSuccess;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (ksize == 57)                // the taps saliency_map() ends up with (saliency.py:156)
+    return launch_saliency_post<57, true>(grad, frames, sal, ksize, sigma, B, C, T, st, map);
+  return launch_saliency_post<0, true>(grad, frames, sal, ksize, sigma, B, C, T, st, map);
 }
 
 extern "C" int pcgmix_saliency_post2d_f32(const float* grad, const int32_t* frames, float* sal,
@@ -726,14 +839,7 @@ extern "C" int pcgmix_saliency_post2d_f32(const float* grad, const int32_t* fram
       !(sigma > 0))
     return hipErrorInvalidValue;
   if (B == 0) return hipSuccess;
-  Taps taps;
-  const int half = ksize / 2;
-  for (int j = 0; j < ksize; ++j) {                  // gaussian_kernel(), saliency.py:15-18
-    const double xr = (double)(j - half);
-    const double w = 1.0 / (sigma * sqrt(2.0 * M_PI)) * exp(-(xr * xr) / (2.0 * (sigma * sigma)));
-    taps.w[j] = (float)w;
-  }
-  for (int j = ksize; j < kMaxTaps; ++j) taps.w[j] = 0.f;
+  const Taps taps = gaussian_taps(ksize, sigma);
   const int G = W >= kSal2dThreads ? 1 : kSal2dThreads / W;
   const size_t lds = sizeof(float) * ((size_t)G * W + (size_t)W + ksize - 1 + (size_t)W);
   hipLaunchKernelGGL(saliency_post2d_kernel, dim3((unsigned)B), dim3(kSal2dThreads), lds,

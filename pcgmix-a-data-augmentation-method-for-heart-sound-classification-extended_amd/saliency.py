@@ -13,12 +13,18 @@ kernel, ``pcgmix_saliency_post_f32``.  Differences from the reference, all at th
   (SURVEY.md §8d cfg3: "saliency model = the model being trained, frozen copy");
 * the reference's '-1'/'-2' method suffixes (saliency.py:29-34) depend on a module that is not
   in its repository (``results_new``) and are refused.
+
+``saliency_map(data, target_ohe, frames, model, device)`` (saliency.py:132-202, with ``bin_tensor``
+and ``gaussian_kernel``) is the module's second entry point: the map of a given model plus the
+same map summarised per heart state, in the reference's return types; everything after the
+backward pass is one kernel, ``pcgmix_saliency_map_f32``, and one device-to-host copy.
 """
 from __future__ import annotations
 
 import contextlib
 import copy
 import ctypes
+import math
 import os
 from typing import Optional
 
@@ -414,6 +420,127 @@ def get_saliency_maps(args, device, data, target_ohe, frames, dim=1, gauss_k_n=1
         fr = upload_array(frames_np.astype(np.int32), data.device)
         grad = input_gradient(model, data, target_ohe)
         return saliency_post(grad, fr.data_ptr(), gauss_k_n)
+
+
+# ---- saliency_map(): the "explain" call (saliency.py:118-202) --------------------------------
+SALMAP_GAUSS = (57, 7.54)        # the last of the reference's three assignments (saliency.py:154-156)
+SALMAP_BINS = (1, 4, 1, 8)       # S1, systole, S2, diastole (saliency.py:177-192)
+
+
+def gaussian_kernel(n=11, sigma=1):
+    """``n`` (odd) Gaussian weights around 0 as Python floats, not renormalised (saliency.py:15-18);
+    float64 arithmetic in the order the library's host code uses for its taps."""
+    half = int(n / 2)
+    norm = 1 / (sigma * math.sqrt(2 * math.pi))
+    return [norm * math.exp(-(float(x) * float(x)) / (2 * (sigma * sigma))) for x in range(-half, half + 1)]
+
+
+def bin_tensor(tensor: torch.Tensor, bins: int, device):
+    """A (C, L) tensor summarised in ``bins`` values per channel (linear interpolation,
+    align_corners=False) and blown up again to L samples, every value held for ceil(L / bins)
+    samples (saliency.py:118-130).  Returns (the (C, L) float32 step function on ``device``,
+    channel 0's values as a list, the first sample of every bin as a list).  torch ops on
+    ``tensor``'s device; ``saliency_map`` does the same for a batch in one kernel."""
+    sig_len = int(tensor.shape[1])
+    spb = -(-sig_len // bins)
+    small = torch.nn.functional.interpolate(tensor.unsqueeze(0), size=(bins,), mode="linear").squeeze(0)
+    tensor_new = small.repeat_interleave(spb, dim=1)[:, :sig_len].to(device=device, dtype=torch.float32)
+    return tensor_new, small[0].detach().cpu().tolist(), list(np.arange(bins) * spb)
+
+
+def salmap_frames(frames, B: int, T: int) -> np.ndarray:
+    """The (B,5) boundaries of ``saliency_map`` as a host array, or ValueError: malformed ones as
+    everywhere in the package, and any heart state of length 0 (the reference's ``interpolate``
+    raises on an empty slice)."""
+    from .hostprep import validate_frames
+    fr = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+    validate_frames(fr, T)
+    if fr.shape[0] != B:
+        raise ValueError("frames do not match the batch size")
+    if B and int(np.diff(fr, axis=1).min()) < 1:
+        raise ValueError("a heart state of length 0 cannot be binned")
+    return fr
+
+
+def _salmap_launch(grad: torch.Tensor, frames, gauss, bins):
+    """Argument checks and the one launch of ``pcgmix_saliency_map_f32``.  Returns (sal (B,T),
+    pack, B, T, N): ``pack`` is ONE device buffer of 4-byte words holding sal_bins (B,T) float32,
+    then bin_values (B,N) float32, then bin_frames (B,N+1) int32 — everything the host side of
+    ``saliency_map`` reads, so that it arrives in one copy."""
+    if not isinstance(grad, torch.Tensor) or grad.dim() != 3 or grad.dtype != torch.float32 \
+            or not grad.is_contiguous() or not grad.is_cuda:
+        raise ValueError("expected a contiguous float32 (B, C, T) tensor on a HIP device")
+    B, C, T = grad.shape
+    ksize, sigma = int(gauss[0]), float(gauss[1])
+    if ksize < 1 or ksize > 255 or ksize % 2 == 0 or not sigma > 0:
+        raise ValueError("gauss must be (odd tap count <= 255, sigma > 0)")
+    nb = np.asarray(bins, dtype=np.int32)
+    if nb.shape != (4,) or int(nb.min()) < 1 or int(nb.sum()) > 64:
+        raise ValueError("bins must be four counts >= 1 with a sum of at most 64")
+    fr = salmap_frames(frames, B, T)
+    N = int(nb.sum())
+    sal = torch.empty((B, T), dtype=torch.float32, device=grad.device)
+    pack = torch.empty(B * (T + 2 * N + 1), dtype=torch.float32, device=grad.device)
+    if B == 0:
+        return sal, pack, B, T, N
+    from .augmentations import upload_array
+    with torch.cuda.device(grad.device):
+        fr_dev = upload_array(fr.astype(np.int32), grad.device)
+        stream = torch.cuda.current_stream(grad.device).cuda_stream
+        _lib.check(_lib.load().pcgmix_saliency_map_f32(
+            grad.data_ptr(), fr_dev.data_ptr(), sal.data_ptr(), pack.data_ptr(),
+            pack[B * T:].data_ptr(), pack[B * (T + N):].data_ptr(), ksize, ctypes.c_double(sigma),
+            nb.ctypes.data, B, C, T, ctypes.c_void_p(stream)), "pcgmix_saliency_map_f32")
+    return sal, pack, B, T, N
+
+
+def _salmap_unpack(pack: torch.Tensor, B: int, T: int, N: int):
+    return (pack[:B * T].view(B, T), pack[B * T:B * (T + N)].view(B, N),
+            pack[B * (T + N):].view(torch.int32).view(B, N + 1))
+
+
+def saliency_map_post(grad: torch.Tensor, frames, *, gauss=SALMAP_GAUSS, bins=SALMAP_BINS):
+    """Everything of ``saliency_map`` behind the backward pass (saliency.py:147-201) as one kernel
+    launch: ``grad`` (B,C,T) float32 on the device, ``frames`` (B,5) on the host ->
+    (sal (B,T), sal_bins (B,T), bin_values (B,N) float32, bin_frames (B,N+1) int32) on the device."""
+    sal, pack, B, T, N = _salmap_launch(grad, frames, gauss, bins)
+    return (sal,) + _salmap_unpack(pack, B, T, N)
+
+
+def saliency_map(data, target_ohe, frames, model, device, *, gauss=SALMAP_GAUSS, bins=SALMAP_BINS):
+    """The reference's ``saliency_map(data, target_ohe, frames, model, device)`` (saliency.py:132-202):
+    which part of the cycle drives the true-class score of ``model``.  Returns
+
+      saliency       (B,1,T) float32 on the device: smoothed |d score / d input|, per row in [0,1]
+      saliency_bins  (B,1,T) float32 on the CPU: the same per heart state, S1 in 1 bin, systole
+                     in 4, S2 in 1, diastole in 8, every bin value held over its samples
+      out            (B,classes) logits on the device (eval-mode forward, no autograd graph)
+      bin values     list of B float64 arrays of 14
+      bin frames     list of B int64 arrays of 15 (first sample of every bin, then frames[b][4])
+
+    The model is put in eval mode and left there, as the reference does.  Unlike the reference,
+    ``data.requires_grad`` and ``data.grad`` are left untouched (its callers pass clones).  The
+    gradient comes from ``input_gradient``; everything behind it is one kernel and one
+    device-to-host copy."""
+    if not isinstance(data, torch.Tensor) or data.dim() != 3 or data.dtype != torch.float32 \
+            or not data.is_contiguous() or not data.is_cuda:
+        raise ValueError("expected a contiguous float32 (B, C, T) tensor on a HIP device")
+    if torch.device(device).type != data.device.type:
+        raise ValueError("data must live on the device the call names")
+    model.eval()                                                            # saliency.py:137
+    m = model.module if isinstance(model, (torch.nn.DataParallel,
+                                           torch.nn.parallel.DistributedDataParallel)) else model
+    with torch.cuda.device(data.device):
+        x = data.detach()
+        with torch.no_grad():
+            out = m(x)
+        grad = input_gradient(m, x, target_ohe.to(data.device))
+        sal, pack, B, T, N = _salmap_launch(grad, frames, gauss, bins)
+        host = pack.cpu()                                                   # the one D2H copy
+    bins_h, values_h, frames_h = _salmap_unpack(host, B, T, N)
+    return (sal.view(B, 1, T), bins_h.view(B, 1, T), out,
+            [v.astype(np.float64) for v in values_h.numpy()],
+            [f.astype(np.int64) for f in frames_h.numpy()])
 
 
 def optimal_displacements(saliency_maps: torch.Tensor, frames_dev_ptr: int, mix_dev_ptr: int,
