@@ -3,9 +3,12 @@
 //   potes_reduce_kernel     fixed-order sum of the 8/4-channel conv stack's per-block gradient
 //                           partials (pcgmix_potes.hip writes them)
 //   adam_clip_kernel        clip_grad_value_ + Adam for one tensor
-//   adam_clip_multi_kernel  the same for every tensor of a model in one launch, optionally with
-//                           that reduce folded in as extra blocks
-//   sgd_clip_multi_kernel   clip_grad_value_ + momentum SGD, the same launch shape
+//   clip_multi_body         the update of every tensor of a model in one launch, optionally with
+//                           that reduce folded in as extra blocks; its two kernels differ only in
+//                           the rule they hand it:
+//   adam_clip_multi_kernel    AdamRule  clip_grad_value_ + Adam
+//   sgd_clip_multi_kernel     SgdRule   clip_grad_value_ + momentum SGD
+//   clip_multi_launch       the host side of both: table fill, block counts, launch
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -92,61 +95,6 @@ struct AdamTable {
   int count;
 };
 
-// hyper != nullptr: the eight scalars are read from device memory instead (clip, wd, 1-b1, b2,
-// 1-b2, step_size, 1/sqrt(bc2), eps — pcgmix_adam_hyper's layout): a launch captured in a
-// hipGraph then follows OneCycleLR's lr/beta1 and the bias corrections from replay to replay.
-// partial != nullptr: the launch carries kNGrad EXTRA blocks behind the table's own — block
-// red_first + e sums column e of the conv stack's per-block gradient partials exactly as
-// potes_reduce_kernel does (same order, same bits), stores it at grads[e] (what the parameters'
-// .grad tensors alias) and applies the update to the one element it belongs to: the tensor of the
-// table whose gradient pointer lies inside grads[0 .. kNGrad) (such tensors own no blocks of the
-// table).  One launch instead of two at the end of a captured training step.
-__global__ __launch_bounds__(256) void adam_clip_multi_kernel(AdamTable tab, float clip, float wd,
-                                                              float one_m_b1, float b2,
-                                                              float one_m_b2, float step_size,
-                                                              float inv_bc2_sqrt, float eps,
-                                                              const float* __restrict__ hyper,
-                                                              const float* __restrict__ partial,
-                                                              float* __restrict__ grads, int G,
-                                                              int red_first) {
-  if (hyper) {
-    clip = hyper[0]; wd = hyper[1]; one_m_b1 = hyper[2]; b2 = hyper[3];
-    one_m_b2 = hyper[4]; step_size = hyper[5]; inv_bc2_sqrt = hyper[6]; eps = hyper[7];
-  }
-  if (partial && (int)blockIdx.x >= red_first) {
-    __shared__ float red[kPotThreads];
-    const int e = (int)blockIdx.x - red_first;
-    const float gi = potes_reduce_column(partial, G, e, red);
-    if (threadIdx.x != 0) return;
-    grads[e] = gi;
-    const float* ge = grads + e;
-    for (int t = 0; t < tab.count; ++t) {
-      if (ge >= tab.g[t] && ge < tab.g[t] + tab.n[t]) {
-        const long long i = ge - tab.g[t];
-        adam_clip_update(tab.p[t][i], tab.m[t][i], tab.v[t][i], gi, clip, wd, one_m_b1, b2, one_m_b2,
-                         step_size, inv_bc2_sqrt, eps);
-        return;
-      }
-    }
-    return;
-  }
-  int t = 0;
-  while (t + 1 < tab.count && (int)blockIdx.x >= tab.blk_start[t + 1]) ++t;
-  float* __restrict__ p = tab.p[t];
-  const float* __restrict__ g = tab.g[t];
-  float* __restrict__ m = tab.m[t];
-  float* __restrict__ v = tab.v[t];
-  const long long n = tab.n[t];
-  const long long base = (long long)((int)blockIdx.x - tab.blk_start[t]) * kAdamEPB;
-#pragma unroll
-  for (int j = 0; j < kAdamEPB / 256; ++j) {
-    const long long i = base + j * 256 + threadIdx.x;
-    if (i >= n) break;
-    adam_clip_update(p[i], m[i], v[i], g[i], clip, wd, one_m_b1, b2, one_m_b2,
-                     step_size, inv_bc2_sqrt, eps);
-  }
-}
-
 // clip_grad_value_ + torch.optim.SGD (momentum, L2 weight decay; dampening 0, no nesterov) for one
 // element (train_model.py:557-558, 404-405, 566), in torch's _single_tensor_sgd order of roundings:
 //   g = clamp(g, -clip, clip);  g = fma(wd, p, g);  b = rn(mom * b) + g;  p = fma(-lr, b, p)
@@ -166,19 +114,46 @@ __device__ __forceinline__ void sgd_clip_update(float& p, float* m, float gi, fl
   p = fmaf(-lr, gi, pi);                             // param.add_(grad, alpha=-lr)
 }
 
-// The SGD twin of adam_clip_multi_kernel: same table (v unused), same block ownership, same
-// optional kNGrad reduction blocks behind the table's own.  hyper != nullptr: {clip, wd, momentum,
-// lr} are read from device memory (pcgmix_sgd_hyper's layout) — OneCycleLR moves lr AND momentum
-// between the replays of a captured launch.
-__global__ __launch_bounds__(256) void sgd_clip_multi_kernel(AdamTable tab, float clip, float wd,
-                                                             float mom, float lr,
-                                                             const float* __restrict__ hyper,
-                                                             const float* __restrict__ partial,
-                                                             float* __restrict__ grads, int G,
-                                                             int red_first) {
-  if (hyper) {
+// One launch body for both optimisers.  A rule is a plain struct of the update's scalars, held in
+// registers: the kernel builds it from its arguments, load() replaces them from device memory,
+// apply() updates element i of tensor t of the table with the gradient gi.
+// hyper != nullptr: the scalars are read from device memory instead (pcgmix_adam_hyper's /
+// pcgmix_sgd_hyper's layout): a launch captured in a hipGraph then follows OneCycleLR's lr and
+// beta1 / momentum, and Adam's bias corrections, from replay to replay.
+// partial != nullptr: the launch carries kNGrad EXTRA blocks behind the table's own — block
+// red_first + e sums column e of the conv stack's per-block gradient partials exactly as
+// potes_reduce_kernel does (same order, same bits), stores it at grads[e] (what the parameters'
+// .grad tensors alias) and applies the update to the one element it belongs to: the tensor of the
+// table whose gradient pointer lies inside grads[0 .. kNGrad) (such tensors own no blocks of the
+// table).  One launch instead of two at the end of a captured training step.
+struct AdamRule {      // clip, wd, 1-b1, b2, 1-b2, step_size, 1/sqrt(bc2), eps
+  float clip, wd, one_m_b1, b2, one_m_b2, step_size, inv_bc2_sqrt, eps;
+  __device__ __forceinline__ void load(const float* __restrict__ hyper) {
+    clip = hyper[0]; wd = hyper[1]; one_m_b1 = hyper[2]; b2 = hyper[3];
+    one_m_b2 = hyper[4]; step_size = hyper[5]; inv_bc2_sqrt = hyper[6]; eps = hyper[7];
+  }
+  __device__ __forceinline__ void apply(const AdamTable& tab, int t, long long i, float gi) const {
+    adam_clip_update(tab.p[t][i], tab.m[t][i], tab.v[t][i], gi, clip, wd, one_m_b1, b2, one_m_b2,
+                     step_size, inv_bc2_sqrt, eps);
+  }
+};
+
+struct SgdRule {       // the table's v is unused; OneCycleLR moves lr AND momentum
+  float clip, wd, mom, lr;
+  __device__ __forceinline__ void load(const float* __restrict__ hyper) {
     clip = hyper[0]; wd = hyper[1]; mom = hyper[2]; lr = hyper[3];
   }
+  __device__ __forceinline__ void apply(const AdamTable& tab, int t, long long i, float gi) const {
+    sgd_clip_update(tab.p[t][i], tab.m[t] ? tab.m[t] + i : nullptr, gi, clip, wd, mom, lr);
+  }
+};
+
+template <class Rule>
+__device__ __forceinline__ void clip_multi_body(const AdamTable& tab, Rule rule,
+                                                const float* __restrict__ hyper,
+                                                const float* __restrict__ partial,
+                                                float* __restrict__ grads, int G, int red_first) {
+  if (hyper) rule.load(hyper);
   if (partial && (int)blockIdx.x >= red_first) {
     __shared__ float red[kPotThreads];
     const int e = (int)blockIdx.x - red_first;
@@ -188,8 +163,7 @@ __global__ __launch_bounds__(256) void sgd_clip_multi_kernel(AdamTable tab, floa
     const float* ge = grads + e;
     for (int t = 0; t < tab.count; ++t) {
       if (ge >= tab.g[t] && ge < tab.g[t] + tab.n[t]) {
-        const long long i = ge - tab.g[t];
-        sgd_clip_update(tab.p[t][i], tab.m[t] ? tab.m[t] + i : nullptr, gi, clip, wd, mom, lr);
+        rule.apply(tab, t, ge - tab.g[t], gi);
         return;
       }
     }
@@ -197,17 +171,36 @@ __global__ __launch_bounds__(256) void sgd_clip_multi_kernel(AdamTable tab, floa
   }
   int t = 0;
   while (t + 1 < tab.count && (int)blockIdx.x >= tab.blk_start[t + 1]) ++t;
-  float* __restrict__ p = tab.p[t];
   const float* __restrict__ g = tab.g[t];
-  float* __restrict__ m = tab.m[t];
   const long long n = tab.n[t];
   const long long base = (long long)((int)blockIdx.x - tab.blk_start[t]) * kAdamEPB;
 #pragma unroll
   for (int j = 0; j < kAdamEPB / 256; ++j) {
     const long long i = base + j * 256 + threadIdx.x;
     if (i >= n) break;
-    sgd_clip_update(p[i], m ? m + i : nullptr, g[i], clip, wd, mom, lr);
+    rule.apply(tab, t, i, g[i]);
   }
+}
+
+__global__ __launch_bounds__(256) void adam_clip_multi_kernel(AdamTable tab, float clip, float wd,
+                                                              float one_m_b1, float b2,
+                                                              float one_m_b2, float step_size,
+                                                              float inv_bc2_sqrt, float eps,
+                                                              const float* __restrict__ hyper,
+                                                              const float* __restrict__ partial,
+                                                              float* __restrict__ grads, int G,
+                                                              int red_first) {
+  clip_multi_body(tab, AdamRule{clip, wd, one_m_b1, b2, one_m_b2, step_size, inv_bc2_sqrt, eps},
+                  hyper, partial, grads, G, red_first);
+}
+
+__global__ __launch_bounds__(256) void sgd_clip_multi_kernel(AdamTable tab, float clip, float wd,
+                                                             float mom, float lr,
+                                                             const float* __restrict__ hyper,
+                                                             const float* __restrict__ partial,
+                                                             float* __restrict__ grads, int G,
+                                                             int red_first) {
+  clip_multi_body(tab, SgdRule{clip, wd, mom, lr}, hyper, partial, grads, G, red_first);
 }
 
 }  // namespace pcgmix
@@ -229,10 +222,17 @@ extern "C" int pcgmix_adam_hyper(float clip, float lr, float beta1, float beta2,
   return hipSuccess;
 }
 
-static int adam_multi_launch(int n_tensors, float* const* p, const float* const* g, float* const* m,
-                             float* const* v, const long long* n, const float* h8,
-                             const float* hyper_dev, hipStream_t stream,
-                             const float* partial = nullptr, float* grads = nullptr, int G = 0) {
+// The host side of both multi kernels: table fill, block counts and launch, kAdamMaxTensors
+// tensors per launch.  Only two things are the optimiser's own: the kernel, and which state
+// columns must be there.  Adam needs m[i] and v[i].  SGD has no v (nullptr), and m == nullptr or a
+// null m[i] says that tensor has no momentum buffer (need_m: refuse it, the momentum is known to be
+// non-zero).
+enum class Optim { Adam, Sgd };
+static int clip_multi_launch(Optim opt, bool need_m, int n_tensors, float* const* p,
+                             const float* const* g, float* const* m, float* const* v,
+                             const long long* n, const float* h8, const float* hyper_dev,
+                             hipStream_t stream, const float* partial = nullptr,
+                             float* grads = nullptr, int G = 0) {
   using namespace pcgmix;
   if (partial && n_tensors > kAdamMaxTensors) return hipErrorInvalidValue;   // one table, one launch
   for (int first = 0; first < n_tensors; first += kAdamMaxTensors) {
@@ -241,14 +241,17 @@ static int adam_multi_launch(int n_tensors, float* const* p, const float* const*
     int blocks = 0;
     const int last = first + kAdamMaxTensors < n_tensors ? first + kAdamMaxTensors : n_tensors;
     for (int i = first; i < last; ++i) {
-      if (n[i] < 0 || (n[i] > 0 && (!p[i] || !g[i] || !m[i] || !v[i]))) return hipErrorInvalidValue;
+      float* const mi = m ? m[i] : nullptr;
+      float* const vi = v ? v[i] : nullptr;
+      if (n[i] < 0 || (n[i] > 0 && (!p[i] || !g[i] || (need_m && !mi) || (opt == Optim::Adam && !vi))))
+        return hipErrorInvalidValue;
       if (n[i] == 0) continue;
       // tensors whose gradient lives in grads[0 .. kNGrad) are updated by the reduction blocks
       const bool deferred = partial && g[i] >= grads && g[i] < grads + kNGrad;
       const long long nb = deferred ? 0 : (n[i] + kAdamEPB - 1) / kAdamEPB;
       if (nb > (1ll << 30) - blocks) return hipErrorInvalidValue;
       const int k = tab.count++;
-      tab.p[k] = p[i]; tab.g[k] = g[i]; tab.m[k] = m[i]; tab.v[k] = v[i]; tab.n[k] = n[i];
+      tab.p[k] = p[i]; tab.g[k] = g[i]; tab.m[k] = mi; tab.v[k] = vi; tab.n[k] = n[i];
       tab.blk_start[k] = blocks;
       blocks += (int)nb;
     }
@@ -256,9 +259,13 @@ static int adam_multi_launch(int n_tensors, float* const* p, const float* const*
     tab.blk_start[tab.count] = blocks;
     const int red_first = blocks;
     if (partial) blocks += kNGrad;
-    hipLaunchKernelGGL(adam_clip_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tab,
-                       h8[0], h8[1], h8[2], h8[3], h8[4], h8[5], h8[6], h8[7], hyper_dev, partial, grads, G,
-                       red_first);
+    if (opt == Optim::Adam)
+      hipLaunchKernelGGL(adam_clip_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tab,
+                         h8[0], h8[1], h8[2], h8[3], h8[4], h8[5], h8[6], h8[7], hyper_dev, partial,
+                         grads, G, red_first);
+    else
+      hipLaunchKernelGGL(sgd_clip_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tab,
+                         h8[0], h8[1], h8[2], h8[3], hyper_dev, partial, grads, G, red_first);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess) return (int)err;
   }
@@ -271,7 +278,7 @@ extern "C" int pcgmix_adam_clip_multi_dev_f32(int n_tensors, float* const* p, co
   if (n_tensors < 0 || !hyper_dev || (n_tensors > 0 && (!p || !g || !m || !v || !n)))
     return hipErrorInvalidValue;
   const float zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  return adam_multi_launch(n_tensors, p, g, m, v, n, zero8, hyper_dev,
+  return clip_multi_launch(Optim::Adam, true, n_tensors, p, g, m, v, n, zero8, hyper_dev,
                            reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -283,7 +290,7 @@ extern "C" int pcgmix_adam_clip_multi_reduce_dev_f32(int n_tensors, float* const
   if (n_tensors <= 0 || !hyper_dev || !p || !g || !m || !v || !n || !partial || !grads || G <= 0)
     return hipErrorInvalidValue;
   const float zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  return adam_multi_launch(n_tensors, p, g, m, v, n, zero8, hyper_dev,
+  return clip_multi_launch(Optim::Adam, true, n_tensors, p, g, m, v, n, zero8, hyper_dev,
                            reinterpret_cast<hipStream_t>(stream), partial, grads, G);
 }
 
@@ -303,7 +310,7 @@ extern "C" int pcgmix_adam_clip_multi_f32(int n_tensors, float* const* p, const 
     return hipErrorInvalidValue;
   float h8[8];
   pcgmix_adam_hyper(clip, lr, beta1, beta2, eps, weight_decay, step, h8);
-  return adam_multi_launch(n_tensors, p, g, m, v, n, h8, nullptr,
+  return clip_multi_launch(Optim::Adam, true, n_tensors, p, g, m, v, n, h8, nullptr,
                            reinterpret_cast<hipStream_t>(stream));
 }
 
@@ -335,44 +342,6 @@ extern "C" int pcgmix_sgd_hyper(float clip, float lr, float momentum, float weig
   return hipSuccess;
 }
 
-// adam_multi_launch's table fill for the SGD kernel.  m == nullptr, or a null m[i]: that tensor
-// has no momentum buffer (need_m: refuse it, the momentum is known to be non-zero).
-static int sgd_multi_launch(int n_tensors, float* const* p, const float* const* g, float* const* m,
-                            const long long* n, const float* h8, const float* hyper_dev, bool need_m,
-                            hipStream_t stream, const float* partial = nullptr,
-                            float* grads = nullptr, int G = 0) {
-  using namespace pcgmix;
-  if (partial && n_tensors > kAdamMaxTensors) return hipErrorInvalidValue;   // one table, one launch
-  for (int first = 0; first < n_tensors; first += kAdamMaxTensors) {
-    AdamTable tab;
-    tab.count = 0;
-    int blocks = 0;
-    const int last = first + kAdamMaxTensors < n_tensors ? first + kAdamMaxTensors : n_tensors;
-    for (int i = first; i < last; ++i) {
-      float* const mi = m ? m[i] : nullptr;
-      if (n[i] < 0 || (n[i] > 0 && (!p[i] || !g[i] || (need_m && !mi)))) return hipErrorInvalidValue;
-      if (n[i] == 0) continue;
-      // tensors whose gradient lives in grads[0 .. kNGrad) are updated by the reduction blocks
-      const bool deferred = partial && g[i] >= grads && g[i] < grads + kNGrad;
-      const long long nb = deferred ? 0 : (n[i] + kAdamEPB - 1) / kAdamEPB;
-      if (nb > (1ll << 30) - blocks) return hipErrorInvalidValue;
-      const int k = tab.count++;
-      tab.p[k] = p[i]; tab.g[k] = g[i]; tab.m[k] = mi; tab.v[k] = nullptr; tab.n[k] = n[i];
-      tab.blk_start[k] = blocks;
-      blocks += (int)nb;
-    }
-    if (tab.count == 0) continue;
-    tab.blk_start[tab.count] = blocks;
-    const int red_first = blocks;
-    if (partial) blocks += kNGrad;
-    hipLaunchKernelGGL(sgd_clip_multi_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tab,
-                       h8[0], h8[1], h8[2], h8[3], hyper_dev, partial, grads, G, red_first);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
-  }
-  return hipSuccess;
-}
-
 extern "C" int pcgmix_sgd_clip_multi_f32(int n_tensors, float* const* p, const float* const* g,
                                          float* const* m, const long long* n, float clip, float lr,
                                          float momentum, float weight_decay,
@@ -381,8 +350,9 @@ extern "C" int pcgmix_sgd_clip_multi_f32(int n_tensors, float* const* p, const f
     return hipErrorInvalidValue;
   float h8[8];
   pcgmix_sgd_hyper(clip, lr, momentum, weight_decay, h8);
-  return sgd_multi_launch(n_tensors, p, g, momentum != 0.f ? m : nullptr, n, h8, nullptr,
-                          momentum != 0.f, reinterpret_cast<hipStream_t>(stream));
+  return clip_multi_launch(Optim::Sgd, momentum != 0.f, n_tensors, p, g,
+                           momentum != 0.f ? m : nullptr, nullptr, n, h8, nullptr,
+                           reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int pcgmix_sgd_clip_multi_dev_f32(int n_tensors, float* const* p, const float* const* g,
@@ -391,8 +361,8 @@ extern "C" int pcgmix_sgd_clip_multi_dev_f32(int n_tensors, float* const* p, con
   if (n_tensors < 0 || !hyper_dev || (n_tensors > 0 && (!p || !g || !m || !n)))
     return hipErrorInvalidValue;
   const float zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  return sgd_multi_launch(n_tensors, p, g, m, n, zero8, hyper_dev, false,
-                          reinterpret_cast<hipStream_t>(stream));
+  return clip_multi_launch(Optim::Sgd, false, n_tensors, p, g, m, nullptr, n, zero8, hyper_dev,
+                           reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" int pcgmix_sgd_clip_multi_reduce_dev_f32(int n_tensors, float* const* p,
@@ -403,6 +373,6 @@ extern "C" int pcgmix_sgd_clip_multi_reduce_dev_f32(int n_tensors, float* const*
   if (n_tensors <= 0 || !hyper_dev || !p || !g || !m || !n || !partial || !grads || G <= 0)
     return hipErrorInvalidValue;
   const float zero8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  return sgd_multi_launch(n_tensors, p, g, m, n, zero8, hyper_dev, false,
-                          reinterpret_cast<hipStream_t>(stream), partial, grads, G);
+  return clip_multi_launch(Optim::Sgd, false, n_tensors, p, g, m, nullptr, n, zero8, hyper_dev,
+                           reinterpret_cast<hipStream_t>(stream), partial, grads, G);
 }

@@ -185,25 +185,117 @@ class step_counter_class:
         self.count += 1
 
 
-class ClipAdam(torch.optim.Adam):
-    """``clip_grad_value_(clip)`` + ``torch.optim.Adam`` (L2 weight decay) as one HIP pass per
-    parameter (``pcgmix_adam_clip_f32``).  Same state layout (``step``, ``exp_avg``,
-    ``exp_avg_sq``) and param-group keys as torch's Adam, so OneCycleLR cycles ``lr`` and
-    ``betas`` on it unchanged and checkpoints interchange.  Gradients are NOT modified (torch's
-    clip is in place; nothing downstream of the optimiser step reads them)."""
+class _ClipUpdate:
+    """What ClipAdam and ClipSGD share; the first base, in front of the torch optimiser.  The
+    multi-tensor launch of ``csrc/pcgmix_optim.hip`` takes host pointer tables (cached here) and
+    can be the last node of a captured training step (``GraphedTrainStep``): kernel arguments are
+    frozen at capture while OneCycleLR moves the group's scalars every step, so the captured launch
+    reads them from device memory and ``next_hyper`` writes them on the host for the coming replay.
+    A subclass names its three launches, says which state tensors are the tables' extra columns
+    (``_columns``) and keeps ``step``, ``prepare_capture`` (which sets ``_cap_params``) and
+    ``next_hyper``.  Gradients are NOT modified (torch's clip is in place; nothing downstream of
+    the optimiser step reads them)."""
 
-    def __init__(self, params, lr, weight_decay=0.0, clip_value=0.0, betas=(0.9, 0.999), eps=1e-8):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+    EAGER_LAUNCH = DEV_LAUNCH = REDUCE_LAUNCH = None    # REDUCE_LAUNCH: the tape's fifth launch
+    _STATE_WORDS = None                                 # what load_state_dict replaces, in words
+
+    def __init__(self, params, clip_value, **kw):
+        super().__init__(params, **kw)
         self.clip_value = float(clip_value or 0.0)
         self._tables = {}
-        self._cap_params, self._cap_grads, self._cap_step, self._cap_dirty = None, None, 0, False
+        self._cap_params = self._cap_grads = None
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
-        self._tables = {}                      # the moment tensors were replaced
+        self._tables = {}                      # the state tensors were replaced
+        self._adopt_loaded_state()
         if getattr(self, "_cap_params", None):
-            raise RuntimeError("ClipAdam: load the state before the step is captured (the graph "
-                               "holds the addresses of the old moment tensors)")
+            raise RuntimeError(f"{type(self).__name__}: load the state before the step is captured "
+                               f"(the graph holds the addresses of the old {self._STATE_WORDS})")
+
+    def _adopt_loaded_state(self):
+        pass
+
+    def _table(self, gi, live, grads):
+        """Host pointer tables of group ``gi`` in the order the entry points take them: (key, p, g,
+        *state columns, n).  Cached; rebuilt when a parameter moved (the key), and dropped where a
+        state tensor appears or is replaced (``_init_state``, ``load_state_dict``); an absent state
+        tensor is a NULL entry.  The gradient pointers are rewritten in place."""
+        import ctypes
+        key = [p.data_ptr() for p in live]
+        tab = self._tables.get(gi)
+        if tab is None or tab[0] != key:
+            arr = ctypes.c_void_p * len(live)
+            cols = [[None if t is None else t.data_ptr() for t in col] for col in self._columns(live)]
+            tab = (key, arr(*key), arr(), *[arr(*col) for col in cols],
+                   (ctypes.c_longlong * len(live))(*[p.numel() for p in live]))
+            self._tables[gi] = tab
+        gptr = tab[2]
+        for i, g in enumerate(grads):
+            gptr[i] = g.data_ptr()
+        return tab
+
+    @staticmethod
+    def _dense_grads(live):
+        # flat iteration over raw memory: p, grad and the state tensors must share one dense layout
+        return [p.grad if p.grad.stride() == p.stride() else torch.empty_like(p).copy_(p.grad)
+                for p in live]
+
+    def can_capture(self) -> bool:
+        return len(self.param_groups) == 1
+
+    @torch.no_grad()
+    def capture_update(self, hyper_dev: torch.Tensor, deferred: Optional[dict] = None):
+        """Inside the capture, after backward: the update of all ``prepare_capture`` tensors.
+
+        ``deferred`` (``models.PotesStackFunction.defer_reduce`` after the backward): the Potes conv
+        stack left its 212 gradient columns as G un-reduced partial rows.  When the stack's four
+        parameter gradients are views of ``deferred["grads"]`` (autograd keeps the tensors the
+        backward returned) the reduction runs as 212 extra blocks of this launch, each of which also
+        updates its element; otherwise it is launched on its own first."""
+        import ctypes
+        from . import _lib
+        lib = _lib.load()
+        live = self._cap_params
+        if any(p.grad is None for p in live):
+            raise RuntimeError(f"{type(self).__name__}.capture_update: a prepared parameter has no "
+                               "gradient")
+        self._cap_grads = self._dense_grads(live)            # keep graph memory referenced
+        self._opt_called = True      # the replays stand for step(): what LRScheduler's wrapper of it records
+        args = (len(live), *self._table(0, live, self._cap_grads)[1:], hyper_dev.data_ptr())
+        stream = ctypes.c_void_p(torch.cuda.current_stream(live[0].device).cuda_stream)
+        if deferred and "partial" in deferred:
+            grads, partial, G = deferred["grads"], deferred["partial"], int(deferred["G"])
+            lo, hi = grads.data_ptr(), grads.data_ptr() + grads.numel() * 4
+            covered = sum(g.numel() for g in self._cap_grads if lo <= g.data_ptr() < hi)
+            self._cap_deferred = (partial, grads)            # referenced by the graph
+            if covered == grads.numel() and len(live) <= 32:
+                _lib.check(getattr(lib, self.REDUCE_LAUNCH)(
+                    *args, partial.data_ptr(), grads.data_ptr(), G, stream), self.REDUCE_LAUNCH)
+                return
+            _lib.check(lib.pcgmix_potes_reduce_f32(partial.data_ptr(), grads.data_ptr(), G, stream),
+                       "pcgmix_potes_reduce_f32")
+        _lib.check(getattr(lib, self.DEV_LAUNCH)(*args, stream), self.DEV_LAUNCH)
+
+    def _captured(self):
+        """(parameter, the gradient tensor the captured update reads) pairs."""
+        return zip(self._cap_params, self._cap_grads)
+
+
+class ClipAdam(_ClipUpdate, torch.optim.Adam):
+    """``clip_grad_value_(clip)`` + ``torch.optim.Adam`` (L2 weight decay) as one HIP launch for all
+    parameters of a group (``pcgmix_adam_clip_multi_f32``).  Same state layout (``step``,
+    ``exp_avg``, ``exp_avg_sq``) and param-group keys as torch's Adam, so OneCycleLR cycles ``lr``
+    and ``betas`` on it unchanged and checkpoints interchange."""
+
+    EAGER_LAUNCH = "pcgmix_adam_clip_multi_f32"
+    DEV_LAUNCH = "pcgmix_adam_clip_multi_dev_f32"
+    REDUCE_LAUNCH = "pcgmix_adam_clip_multi_reduce_dev_f32"
+    _STATE_WORDS = "moment tensors"
+
+    def __init__(self, params, lr, weight_decay=0.0, clip_value=0.0, betas=(0.9, 0.999), eps=1e-8):
+        super().__init__(params, clip_value, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self._cap_step, self._cap_dirty = 0, False
 
     def _init_state(self, params):
         for p in params:
@@ -212,29 +304,10 @@ class ClipAdam(torch.optim.Adam):
                 st["step"] = torch.tensor(0.0)
                 st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                 st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                self._tables = {}
 
-    def _table(self, gi, live, grads):
-        """Host pointer tables of the group's static tensors (rebuilt when a tensor moved)."""
-        import ctypes
-        key = tuple(p.data_ptr() for p in live)
-        tab = self._tables.get(gi)
-        if tab is None or tab[0] != key:
-            n = len(live)
-            arr = ctypes.c_void_p * n
-            tab = (key, arr(*key), arr(*[self.state[p]["exp_avg"].data_ptr() for p in live]),
-                   arr(*[self.state[p]["exp_avg_sq"].data_ptr() for p in live]),
-                   (ctypes.c_longlong * n)(*[p.numel() for p in live]), arr())
-            self._tables[gi] = tab
-        gptr = tab[5]
-        for i, g in enumerate(grads):
-            gptr[i] = g.data_ptr()
-        return tab
-
-    @staticmethod
-    def _dense_grads(live):
-        # flat iteration over raw memory: p, grad, m, v must share one dense layout
-        return [p.grad if p.grad.stride() == p.stride() else torch.empty_like(p).copy_(p.grad)
-                for p in live]
+    def _columns(self, live):
+        return [self.state[p]["exp_avg"] for p in live], [self.state[p]["exp_avg_sq"] for p in live]
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -258,23 +331,15 @@ class ClipAdam(torch.optim.Adam):
                 # for the captured launches too: their bias corrections continue from here
                 self._cap_step = next(iter(steps))
             tab = self._table(gi, live, self._dense_grads(live))
-            dev = live[0].device
-            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _lib.check(lib.pcgmix_adam_clip_multi_f32(
-                len(live), tab[1], tab[5], tab[2], tab[3], tab[4], ctypes.c_float(self.clip_value),
+            stream = ctypes.c_void_p(torch.cuda.current_stream(live[0].device).cuda_stream)
+            _lib.check(getattr(lib, self.EAGER_LAUNCH)(
+                len(live), *tab[1:], ctypes.c_float(self.clip_value),
                 ctypes.c_float(float(group["lr"])), ctypes.c_float(b1), ctypes.c_float(b2),
                 ctypes.c_float(group["eps"]), ctypes.c_float(group["weight_decay"]),
-                steps.pop(), stream), "pcgmix_adam_clip_multi_f32")
+                steps.pop(), stream), self.EAGER_LAUNCH)
         return None
 
-    # ---- the update as a node of a captured training step (GraphedTrainStep) -----------------
-    # Kernel arguments are frozen at capture, OneCycleLR moves lr and beta1 every step and the
-    # bias corrections move with the step count: the captured launch reads its eight scalars from
-    # device memory (``pcgmix_adam_clip_multi_dev_f32``); ``next_hyper`` computes them on the host
-    # for the coming replay and advances the step count.
-    def can_capture(self) -> bool:
-        return len(self.param_groups) == 1
-
+    # ---- captured: the bias corrections move with the step count, which the host keeps ---------
     def prepare_capture(self, params):
         """Before the capture: allocate the moments of ``params`` (the tensors that will carry a
         gradient) — an allocation inside the capture would be re-zeroed by every replay."""
@@ -286,41 +351,6 @@ class ClipAdam(torch.optim.Adam):
         self._cap_params = list(params)
         self._cap_step = steps.pop()
 
-    @torch.no_grad()
-    def capture_update(self, hyper_dev: torch.Tensor, deferred: Optional[dict] = None):
-        """Inside the capture, after backward: the update of all ``prepare_capture`` tensors.
-
-        ``deferred`` (``models.PotesStackFunction.defer_reduce`` after the backward): the Potes conv
-        stack left its 212 gradient columns as G un-reduced partial rows.  When the stack's four
-        parameter gradients are views of ``deferred["grads"]`` (autograd keeps the tensors the
-        backward returned) the reduction runs as 212 extra blocks of this launch, each of which also
-        updates its element; otherwise it is launched on its own first."""
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        live = self._cap_params
-        if any(p.grad is None for p in live):
-            raise RuntimeError("ClipAdam.capture_update: a prepared parameter has no gradient")
-        self._cap_grads = self._dense_grads(live)            # keep graph memory referenced
-        tab = self._table(0, live, self._cap_grads)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(live[0].device).cuda_stream)
-        if deferred and "partial" in deferred:
-            grads, partial, G = deferred["grads"], deferred["partial"], int(deferred["G"])
-            lo, hi = grads.data_ptr(), grads.data_ptr() + grads.numel() * 4
-            covered = sum(g.numel() for g in self._cap_grads if lo <= g.data_ptr() < hi)
-            self._cap_deferred = (partial, grads)            # referenced by the graph
-            if covered == grads.numel() and len(live) <= 32:
-                _lib.check(lib.pcgmix_adam_clip_multi_reduce_dev_f32(
-                    len(live), tab[1], tab[5], tab[2], tab[3], tab[4], hyper_dev.data_ptr(),
-                    partial.data_ptr(), grads.data_ptr(), G, stream),
-                    "pcgmix_adam_clip_multi_reduce_dev_f32")
-                return
-            _lib.check(lib.pcgmix_potes_reduce_f32(partial.data_ptr(), grads.data_ptr(), G, stream),
-                       "pcgmix_potes_reduce_f32")
-        _lib.check(lib.pcgmix_adam_clip_multi_dev_f32(
-            len(live), tab[1], tab[5], tab[2], tab[3], tab[4], hyper_dev.data_ptr(), stream),
-            "pcgmix_adam_clip_multi_dev_f32")
-
     def next_hyper(self, out8) -> None:
         """Host: the eight scalars of the NEXT update into ``out8`` (float32[8], numpy), from the
         param group as the scheduler left it; counts the step.  ``state[p]['step']`` is brought
@@ -330,7 +360,6 @@ class ClipAdam(torch.optim.Adam):
         g = self.param_groups[0]
         self._cap_step += 1
         self._cap_dirty = True
-        self._opt_called = True                  # what LRScheduler's wrapper of step() records
         _lib.check(_lib.load().pcgmix_adam_hyper(
             ctypes.c_float(self.clip_value), ctypes.c_float(float(g["lr"])),
             ctypes.c_float(g["betas"][0]), ctypes.c_float(g["betas"][1]), ctypes.c_float(g["eps"]),
@@ -347,23 +376,24 @@ class ClipAdam(torch.optim.Adam):
         return super().state_dict()
 
 
-class ClipSGD(torch.optim.SGD):
+class ClipSGD(_ClipUpdate, torch.optim.SGD):
     """``clip_grad_value_(clip)`` + ``torch.optim.SGD`` (momentum, L2 weight decay) as one HIP launch
     for all parameters of a group (``pcgmix_sgd_clip_multi_f32``; train_model.py:404-405, 557-558,
     566).  Same state (``momentum_buffer``) and param-group keys as torch's SGD, so OneCycleLR cycles
     ``lr`` and ``momentum`` on it unchanged and checkpoints interchange.  With momentum 0 no buffers
-    exist and the state stays empty, as torch's does.  Gradients are NOT modified.  ``dampening``,
-    ``nesterov`` and ``maximize`` are refused: the kernel implements the reference's defaults."""
+    exist and the state stays empty, as torch's does.  ``dampening``, ``nesterov`` and ``maximize``
+    are refused: the kernel implements the reference's defaults."""
 
-    REDUCE_LAUNCH = "pcgmix_sgd_clip_multi_reduce_dev_f32"    # the tape's fifth launch (GraphedTrainStep)
+    EAGER_LAUNCH = "pcgmix_sgd_clip_multi_f32"
+    DEV_LAUNCH = "pcgmix_sgd_clip_multi_dev_f32"
+    REDUCE_LAUNCH = "pcgmix_sgd_clip_multi_reduce_dev_f32"
+    _STATE_WORDS = "momentum buffers"
 
     def __init__(self, params, lr, weight_decay=0.0, clip_value=0.0, momentum=0.0, dampening=0.0,
                  nesterov=False, maximize=False):
         self._refuse(dict(dampening=dampening, nesterov=nesterov, maximize=maximize))
-        super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
-        self.clip_value = float(clip_value or 0.0)
-        self._tables = {}
-        self._cap_params, self._cap_grads, self._cap_buffers = None, None, False
+        super().__init__(params, clip_value, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self._cap_buffers = False
 
     @staticmethod
     def _refuse(group):
@@ -371,18 +401,13 @@ class ClipSGD(torch.optim.SGD):
             raise NotImplementedError("ClipSGD: dampening, nesterov and maximize are not implemented "
                                       "(the reference trains with torch.optim.SGD's defaults)")
 
-    def load_state_dict(self, state_dict):
-        super().load_state_dict(state_dict)
-        self._tables = {}                      # the buffers were replaced
+    def _adopt_loaded_state(self):
         for group in self.param_groups:
             self._refuse(group)
             for p in group["params"]:          # torch's buffer is a clone of the GRADIENT: its layout
                 buf = self._buf(p)
                 if buf is not None and buf.stride() != p.stride():
                     self.state[p]["momentum_buffer"] = torch.empty_like(p).copy_(buf)
-        if getattr(self, "_cap_params", None):
-            raise RuntimeError("ClipSGD: load the state before the step is captured (the graph "
-                               "holds the addresses of the old momentum buffers)")
 
     def _buf(self, p):
         return self.state.get(p, {}).get("momentum_buffer")     # (no state entry is created by asking)
@@ -391,26 +416,10 @@ class ClipSGD(torch.optim.SGD):
         for p in params:
             if self._buf(p) is None:
                 self.state[p]["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                self._tables = {}
 
-    def _table(self, gi, live, grads, with_m):
-        """Host pointer tables of the group's static tensors (rebuilt when a tensor moved or a
-        buffer appeared): (key, p, m or None, n, g)."""
-        import ctypes
-        bufs = [self._buf(p) for p in live] if with_m else []
-        key = tuple(p.data_ptr() for p in live) + tuple(0 if b is None else b.data_ptr() for b in bufs)
-        tab = self._tables.get(gi)
-        if tab is None or tab[0] != key:
-            n = len(live)
-            arr = ctypes.c_void_p * n
-            tab = (key, arr(*key[:n]), arr(*[b or None for b in key[n:]]) if with_m else None,
-                   (ctypes.c_longlong * n)(*[p.numel() for p in live]), arr())
-            self._tables[gi] = tab
-        gptr = tab[4]
-        for i, g in enumerate(grads):
-            gptr[i] = g.data_ptr()
-        return tab
-
-    _dense_grads = staticmethod(ClipAdam._dense_grads)
+    def _columns(self, live):
+        return ([self._buf(p) for p in live],)   # (None: no momentum so far — a NULL entry)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -425,21 +434,15 @@ class ClipSGD(torch.optim.SGD):
             mom = float(group["momentum"])
             if mom != 0.0:
                 self._init_state(live)
-            tab = self._table(gi, live, self._dense_grads(live), mom != 0.0)
+            tab = self._table(gi, live, self._dense_grads(live))
             stream = ctypes.c_void_p(torch.cuda.current_stream(live[0].device).cuda_stream)
-            _lib.check(lib.pcgmix_sgd_clip_multi_f32(
-                len(live), tab[1], tab[4], tab[2], tab[3], ctypes.c_float(self.clip_value),
+            _lib.check(getattr(lib, self.EAGER_LAUNCH)(
+                len(live), *tab[1:], ctypes.c_float(self.clip_value),
                 ctypes.c_float(float(group["lr"])), ctypes.c_float(mom),
-                ctypes.c_float(group["weight_decay"]), stream), "pcgmix_sgd_clip_multi_f32")
+                ctypes.c_float(group["weight_decay"]), stream), self.EAGER_LAUNCH)
         return None
 
-    # ---- the update as a node of a captured training step: ClipAdam's protocol -----------------
-    # OneCycleLR moves lr AND momentum every step, so the captured launch reads {clip, wd, momentum,
-    # lr} from device memory (``pcgmix_sgd_clip_multi_dev_f32``); ``next_hyper`` writes them on the
-    # host for the coming replay.  SGD has no step count: nothing to carry between captures.
-    def can_capture(self) -> bool:
-        return len(self.param_groups) == 1
-
+    # ---- captured: SGD has no step count, nothing to carry between captures --------------------
     def prepare_capture(self, params):
         """Before the capture: allocate the momentum buffers of ``params`` when the group's momentum
         is not 0 (an allocation inside the capture would be re-zeroed by every replay)."""
@@ -450,39 +453,9 @@ class ClipSGD(torch.optim.SGD):
         self._cap_params = params
         self._cap_buffers = all(self._buf(p) is not None for p in params)
 
-    @torch.no_grad()
-    def capture_update(self, hyper_dev: torch.Tensor, deferred: Optional[dict] = None):
-        """Inside the capture, after backward: the update of all ``prepare_capture`` tensors, with
-        the Potes conv stack's deferred gradient reduction folded in under ClipAdam's conditions
-        (see ``ClipAdam.capture_update``), else launched on its own first."""
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        live = self._cap_params
-        if any(p.grad is None for p in live):
-            raise RuntimeError("ClipSGD.capture_update: a prepared parameter has no gradient")
-        self._cap_grads = self._dense_grads(live)            # keep graph memory referenced
-        tab = self._table(0, live, self._cap_grads, True)    # (NULL entries: captured without momentum)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(live[0].device).cuda_stream)
-        if deferred and "partial" in deferred:
-            grads, partial, G = deferred["grads"], deferred["partial"], int(deferred["G"])
-            lo, hi = grads.data_ptr(), grads.data_ptr() + grads.numel() * 4
-            covered = sum(g.numel() for g in self._cap_grads if lo <= g.data_ptr() < hi)
-            self._cap_deferred = (partial, grads)            # referenced by the graph
-            if covered == grads.numel() and len(live) <= 32:
-                _lib.check(lib.pcgmix_sgd_clip_multi_reduce_dev_f32(
-                    len(live), tab[1], tab[4], tab[2], tab[3], hyper_dev.data_ptr(),
-                    partial.data_ptr(), grads.data_ptr(), G, stream), self.REDUCE_LAUNCH)
-                return
-            _lib.check(lib.pcgmix_potes_reduce_f32(partial.data_ptr(), grads.data_ptr(), G, stream),
-                       "pcgmix_potes_reduce_f32")
-        _lib.check(lib.pcgmix_sgd_clip_multi_dev_f32(
-            len(live), tab[1], tab[4], tab[2], tab[3], hyper_dev.data_ptr(), stream),
-            "pcgmix_sgd_clip_multi_dev_f32")
-
     def next_hyper(self, out8) -> None:
-        """Host: the scalars of the NEXT update into ``out8`` (float32[8], numpy), from the param
-        group as the scheduler left it."""
+        """Host: {clip, wd, momentum, lr} of the NEXT update into ``out8`` (float32[8], numpy), from
+        the param group as the scheduler left it."""
         import ctypes
         from . import _lib
         g = self.param_groups[0]
@@ -490,7 +463,6 @@ class ClipSGD(torch.optim.SGD):
         if float(g["momentum"]) != 0.0 and not self._cap_buffers:
             raise RuntimeError("ClipSGD: momentum became non-zero on a step that was captured without "
                                "momentum buffers; capture the step again")
-        self._opt_called = True                  # what LRScheduler's wrapper of step() records
         _lib.check(_lib.load().pcgmix_sgd_hyper(
             ctypes.c_float(self.clip_value), ctypes.c_float(float(g["lr"])),
             ctypes.c_float(float(g["momentum"])), ctypes.c_float(g["weight_decay"]),
@@ -803,7 +775,7 @@ def selc_fused_model(model, criterion, data, target_ohe, epoch):
 
 def clips_outside_optimizer(args, optimizer) -> bool:
     """``clip_grad_value_`` as a pass of its own: ClipAdam and ClipSGD clip in their kernels."""
-    return bool(args.grad_clip) and not isinstance(optimizer, (ClipAdam, ClipSGD))
+    return bool(args.grad_clip) and not isinstance(optimizer, _ClipUpdate)
 
 
 def add_stats(stats: dict, loss, out, truth) -> None:
@@ -965,7 +937,7 @@ class GraphedTrainStep:
         # backward and update (no gradient all-reduce) and the optimiser can read its scalars
         # from the static block (ClipAdam, ClipSGD).
         # (``adam_in_graph``: the name is older than ClipSGD, which takes the same place)
-        self.adam_in_graph = isinstance(optimizer, (ClipAdam, ClipSGD)) and optimizer.can_capture() \
+        self.adam_in_graph = isinstance(optimizer, _ClipUpdate) and optimizer.can_capture() \
             and device.type == "cuda"
         self.graph_update = None        # with a sync: the update as a second graph behind the all-reduce
         self._warm_up()
@@ -1090,9 +1062,9 @@ class GraphedTrainStep:
     def _adopt_tape(self, tape, fold) -> None:
         """``self.tape``: the recorded launches when they are the whole capture, else None."""
         self.tape = None
-        # the fifth launch is the optimiser's own: ClipAdam's (in _TAPE_LAUNCHES) or ClipSGD's
-        want = self._TAPE_LAUNCHES[:4] + (getattr(self.opt, "REDUCE_LAUNCH", self._TAPE_LAUNCHES[4]),)
-        if tape is not None and [t[0] for t in tape] == list(want) \
+        # (a tape is recorded only with the update in the graph; the fifth launch is the optimiser's
+        # own — _TAPE_LAUNCHES names ClipAdam's)
+        if tape is not None and [t[0] for t in tape] == [*self._TAPE_LAUNCHES[:4], self.opt.REDUCE_LAUNCH] \
                 and self._tape_covers_capture(tape, fold):
             import ctypes
             # pointer tables are snapshotted: ClipAdam re-uses its ctypes arrays for the next capture
@@ -1128,7 +1100,7 @@ class GraphedTrainStep:
                     written.add(v)
                 elif isinstance(v, ctypes.c_void_p) and v.value:
                     written.add(v.value)
-        for p, g in zip(self.opt._cap_params, self.opt._cap_grads):
+        for p, g in self.opt._captured():
             # (gradients are views: the head's small ones of one block, the stack's of the deferred
             # block — compare the storage a launch was handed, not the view's own address)
             if g is not p.grad or g.untyped_storage().data_ptr() not in written:
