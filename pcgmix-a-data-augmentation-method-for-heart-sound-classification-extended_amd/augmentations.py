@@ -639,8 +639,7 @@ def _bind_native_step(*call):
     (without arguments: bind only)."""
     global _native_step
     mod = _lib.native_step_module({
-        "empty_like": torch.empty_like, "raw_stream": _get_raw_stream, "Tensor": torch.Tensor,
-        "float32": torch.float32, "int64": torch.int64, "np_random": np.random, "np_empty": np.empty,
+        "np_random": np.random, "np_empty": np.empty,
         "np_int64": np.dtype(np.int64), "ndarray": np.ndarray, "lib": _lib, "contexts": _CTX,
         "step_context": step_context, "check_splice": _check_splice, "check": _lib.check})
     _native_step = mod.step if mod is not None else None

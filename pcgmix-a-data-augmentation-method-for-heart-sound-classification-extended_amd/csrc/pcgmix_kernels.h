@@ -85,9 +85,11 @@ int launch_mix_karg(const float* x, float* y, const int16_t* frames16, const int
 // chain  previous splice -> label arg-max -> host (labels -> partners) -> splice,  and with two
 // launches the host's reaction includes a launch (3 us) and the time the command processor takes to
 // start it (3-4 us).  Armed, ONE kernel is enqueued at the start of the call: its block (0,0) does
-// the label arg-max (labels under the step's token to host-mapped memory), then every
-// sample's first block polls that sample's 64-byte RECORD in host-mapped memory until the host has
-// written it, relays it to device memory, and the sample's other blocks pick it up there.
+// the label arg-max (labels under the step's token to host-mapped memory), then wave 0 of every block
+// polls its sample's 64-byte RECORD in host-mapped memory until the host has written it and hands it to
+// the block's other waves through LDS (plain kernel: one wide block per sample slice, no block waits for
+// another).  The splice + warp kernel still has every sample's first block relay the record through
+// device memory (rec_d) to the sample's other blocks.
 // A record is six 8-byte words, each = (stamp << 32) | two int16 values; the stamp is the step's
 // sequence number, so a word is valid by itself (8-byte aligned loads and stores are single-copy
 // atomic on both sides): no flag, no ordering between words, no torn record.  Values: own
@@ -119,8 +121,10 @@ struct EdgePack {
   uint32_t w[kPackB];
   int n;
 };
-// Own quads a lane of the plain armed kernel holds in registers across the wait (16 VGPRs).
-constexpr int kArmedHold = 4;
+// Own quads a lane of the plain armed kernel holds in registers across the wait (24 VGPRs): three chunks of
+// two quads, which is a whole (4, 5000) sample in one block of kArmedThreads lanes.
+constexpr int kArmedHold = 6;
+constexpr int kArmedThreads = 1024;
 // frames_host: the (B,5) int64 boundaries on the host, or nullptr (no early phase).  A sample whose
 // edges are not 0 <= lo <= hi <= T gets [0, T): nothing of it is stored early.  edges_out (kPackB words):
 // the dwords the kernel got, for the caller to hold the records against.

@@ -510,20 +510,25 @@ __global__ __launch_bounds__(kThreads) void mix_warp_karg_kernel(
 
 // The plain splice armed before its index block exists (pcgmix_kernels.h, ArmedArgs).
 #ifdef PCGMIX_PHASE_CLOCK
-// probe build: per launch parity (seq & 1) and sample: block (0,b) entry | relay saw the host's record |
-// block (1,b) saw the relayed record | block (1,b) done | block (1,b) early phase done (plain kernel);
+// probe build: per launch parity (seq & 1) and sample: block (0,b) entry | its poll saw the host's record |
+// the block is past the barrier | the block is done (all waves: a barrier of the probe build) | its early
+// phase is done (plain kernel; the splice + warp kernel keeps its relay's points);
 // [..][kPackB] = block (0,0): entry | labels flagged
 __device__ long long g_armed_clock[2][kPackB + 1][8];
 #define PCGMIX_ACLOCK(b, i) g_armed_clock[a.seq & 1][b][i] = (long long)wall_clock64()
+#define PCGMIX_ACLOCK_BARRIER() __syncthreads()
 #else
 #define PCGMIX_ACLOCK(b, i)
+#define PCGMIX_ACLOCK_BARRIER()
 #endif
 template <int U>
-__global__ __launch_bounds__(kThreads) void mix_armed_kernel(
+__global__ __launch_bounds__(kArmedThreads) void mix_armed_kernel(
     const float* __restrict__ x, float* __restrict__ y, const ArmedArgs a, int B, int C, int T, int epb,
     int chunks, const PayPack pay, uint4* __restrict__ pay_dst, const EdgePack edges) {
+  __shared__ unsigned long long rec_s[kArmedRecWords];   // the sample's record, from wave 0 to the block
   const int b = blockIdx.y;
   const int lane = threadIdx.x & 63;
+  const int nt4 = (int)blockDim.x * 4;           // elements one row of the block's lanes covers (epb = nt4 * U)
   if ((blockIdx.x | blockIdx.y) == 0) {
     if (threadIdx.x == 0) { PCGMIX_ACLOCK(kPackB, 0); }
     if (pay.n16 && (int)threadIdx.x < pay.n16) pay_dst[threadIdx.x] = pay.w[threadIdx.x];
@@ -555,7 +560,7 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
     ehi = (int)(ew >> 16);
   }
   auto is_final = [&](int tq) { return tq + 4 <= elo || tq >= ehi; };
-  // (U = 1 is for planes below 8,192 elements: at most 8 chunks per sample, the grid holds them all, one each)
+  // (U = 1 is for planes below 8,192 elements: at most two chunks of a 1,024-lane block, one block each)
   constexpr int KJ = U == 1 ? 1 : kArmedHold / U;
   float4_a own[kArmedHold];
   int t0s[kArmedHold];                           // row position of the quad; -1: nothing left to do behind the record
@@ -564,7 +569,7 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
     const int chunk = (int)blockIdx.x + j * (int)gridDim.x;
 #pragma unroll
     for (int q = 0; q < U; ++q) {
-      const int i = chunk < chunks ? chunk * epb + q * kThreads * 4 + lane_off : plane;
+      const int i = chunk < chunks ? chunk * epb + q * nt4 + lane_off : plane;
       const bool valid = i < plane;
       const int ii = valid ? i : 0;
       own[j * U + q] = *reinterpret_cast<const float4_a*>(x + own_base + ii);
@@ -579,7 +584,7 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
       const int sl = j * U + q;
       if (t0s[sl] >= 0 && is_final(t0s[sl])) {
         __builtin_nontemporal_store(own[sl], reinterpret_cast<float4_a*>(y + own_base + chunk * epb +
-                                                                         q * kThreads * 4 + lane_off));
+                                                                         q * nt4 + lane_off));
         t0s[sl] = -1;
       }
     }
@@ -589,7 +594,7 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
     bool fin[U];
 #pragma unroll
     for (int q = 0; q < U; ++q) {
-      const int i = chunk * epb + q * kThreads * 4 + lane_off;
+      const int i = chunk * epb + q * nt4 + lane_off;
       fin[q] = i < plane && is_final(i - (i / T) * T);
       // not predicated (mix_body, phase 1): a lane without a final quad reads the sample's first quad
       size_t off = fin[q] ? own_base + i : own_base;
@@ -600,12 +605,15 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
     for (int q = 0; q < U; ++q)
       if (fin[q])
         __builtin_nontemporal_store(v[q], reinterpret_cast<float4_a*>(y + own_base + chunk * epb +
-                                                                      q * kThreads * 4 + lane_off));
+                                                                      q * nt4 + lane_off));
   }
-  if (blockIdx.x == 1 && threadIdx.x == 0) { PCGMIX_ACLOCK(b, 4); }
+  if (blockIdx.x == 0 && threadIdx.x == 0) { PCGMIX_ACLOCK(b, 4); }
   const uint32_t go = a.seq, stop = a.seq | kArmedAbort;
   const int word = lane < 7 ? lane : 6;          // six index words and lambda (word 6: float bits)
-  if (blockIdx.x == 0 && threadIdx.x < 64) {     // this sample's relay: host record -> device record
+  // Wave 0 of EVERY block polls its sample's record on the host and hands the seven words — or the give-up
+  // verdict in all of them — to the block's other waves through LDS: they wait at the barrier and poll
+  // nothing, and no block waits for another one.
+  if (threadIdx.x < 64) {
     const unsigned long long* src = a.rec_h + (size_t)b * kArmedRecWords + word;
     unsigned long long w;
     bool aborted = false;
@@ -620,23 +628,13 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
       w = (unsigned long long)stop << 32;
       if (lane == 0) __hip_atomic_store(a.abort_h, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    if (lane < 7)
-      __hip_atomic_store(a.rec_d + (size_t)b * kArmedRecWords + lane, w, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-    if (lane == 0) { PCGMIX_ACLOCK(b, 1); }
+    if (lane < 7) rec_s[lane] = w;
+    if (blockIdx.x == 0 && lane == 0) { PCGMIX_ACLOCK(b, 1); }
   }
-  unsigned long long w;
-  {                                              // every wave: the sample's record on the device
-    const unsigned long long* src = a.rec_d + (size_t)b * kArmedRecWords + word;
-    for (;;) {
-      w = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const uint32_t st = (uint32_t)(w >> 32);
-      if (__all(st == go)) break;
-      if (__any(st == stop) || wall_clock64() - t0 > 2 * a.timeout_ticks) return;
-      __builtin_amdgcn_s_sleep(12);
-    }
-  }
-  if (blockIdx.x == 1 && threadIdx.x == 0) { PCGMIX_ACLOCK(b, 2); }
+  __syncthreads();
+  if ((uint32_t)(rec_s[0] >> 32) != go) return;  // block-uniform: all seven words carry one verdict
+  const unsigned long long w = rec_s[word];
+  if (blockIdx.x == 0 && threadIdx.x == 0) { PCGMIX_ACLOCK(b, 2); }
   const int lo = (int)(uint32_t)w;
   int f1[5], f2[5], m, lam_bits;
   {
@@ -664,33 +662,35 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
     sm.n[k] = n;
     sm.delta[k] = s - a0;
   }
-  // ---- late phase: the quads that are not final.  (Two chunks of the sample per block at (256,4,5000):
-  // 2,560 chunks are more blocks than the chip holds at once — 2,048 of four waves — and the last fifth
-  // would start, and begin to wait, when the first ones leave.)
+  // ---- late phase: the quads that are not final.  (All three chunks of the sample in ONE block of 16 waves
+  // at (256,4,5000): 256 polling blocks, one per CU, five own quads per lane held across the wait.)
   // lambda travels with the record: a caller may launch before it has drawn it (pcgmix_augment_plain_begin)
   const float lam = __int_as_float(lam_bits), oml = 1.0f - lam;
   const size_t par_base = (size_t)m * plane;
   // held quads: the own values are in registers — ONE memory round trip, all partner loads of the lane in
-  // flight together.  A quad without a blended element (the unmatched part of a longer state) is stored
-  // as it is, without a load.
+  // flight together.  All plans first, then the loads in one straight line and not predicated (mix_body, phase 1):
+  // a quad without a blended element (the unmatched part of a longer state) reads the sample's first quad —
+  // one cached line per wave — and is stored as it is.  With the loads under their own branches the compiler
+  // put a full wait in front of every plan but the first: six round trips in a row.
   float4_u par[kArmedHold];
   int masks[kArmedHold];
+  size_t poffs[kArmedHold];
 #pragma unroll
   for (int j = 0; j < KJ; ++j) {
     const int chunk = (int)blockIdx.x + j * (int)gridDim.x;
 #pragma unroll
     for (int q = 0; q < U; ++q) {
       const int sl = j * U + q;
-      masks[sl] = 0;
-      if (t0s[sl] >= 0) {
-        int src0;
-        masks[sl] = quad_plan(sm, t0s[sl], T, src0);
-        if (masks[sl] & 0xf) {
-          const int row = chunk * epb + q * kThreads * 4 + lane_off - t0s[sl];   // c * T
-          par[sl] = *reinterpret_cast<const float4_u*>(x + par_base + row + src0);
-        }
-      }
+      int src0 = 0;
+      masks[sl] = t0s[sl] >= 0 ? quad_plan(sm, t0s[sl], T, src0) : 0;
+      const int row = chunk * epb + q * nt4 + lane_off - t0s[sl];   // c * T
+      poffs[sl] = (masks[sl] & 0xf) ? par_base + row + src0 : own_base;
     }
+  }
+#pragma unroll
+  for (int sl = 0; sl < KJ * U; ++sl) {
+    asm volatile("" : "+v"(poffs[sl]));
+    par[sl] = *reinterpret_cast<const float4_u*>(x + poffs[sl]);
   }
 #pragma unroll
   for (int j = 0; j < KJ; ++j) {
@@ -699,7 +699,7 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
     for (int q = 0; q < U; ++q) {
       const int sl = j * U + q;
       if (t0s[sl] < 0) continue;
-      const int i = chunk * epb + q * kThreads * 4 + lane_off;
+      const int i = chunk * epb + q * nt4 + lane_off;
       float4_a v = own[sl];
       if (masks[sl] & 0xf) {
         float out[4];
@@ -716,7 +716,7 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
     int tq[U], mk[U];
 #pragma unroll
     for (int q = 0; q < U; ++q) {
-      const int i = chunk * epb + q * kThreads * 4 + lane_off;
+      const int i = chunk * epb + q * nt4 + lane_off;
       const int t = i < plane ? i - (i / T) * T : -1;
       const bool live = t >= 0 && !is_final(t);
       int src0 = 0;
@@ -733,7 +733,7 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
 #pragma unroll
     for (int q = 0; q < U; ++q) {
       if (tq[q] < 0) continue;
-      const int i = chunk * epb + q * kThreads * 4 + lane_off;
+      const int i = chunk * epb + q * nt4 + lane_off;
       float4_a v = ow[q];
       if (mk[q] & 0xf) {
         float out[4];
@@ -743,7 +743,8 @@ __global__ __launch_bounds__(kThreads) void mix_armed_kernel(
       __builtin_nontemporal_store(v, reinterpret_cast<float4_a*>(y + own_base + i));
     }
   }
-  if (blockIdx.x == 1 && threadIdx.x == 0) { PCGMIX_ACLOCK(b, 3); }
+  PCGMIX_ACLOCK_BARRIER();
+  if (blockIdx.x == 0 && threadIdx.x == 0) { PCGMIX_ACLOCK(b, 3); }
 }
 
 // The splice + warp kernel armed the same way (PCGmix+ through the strict signature): the knots are known
@@ -1043,13 +1044,26 @@ int pcgmix::launch_mix_armed(const float* x, float* y, const ArmedArgs& a, int B
     memset(pay.w, 0, sizeof(pay.w));
     memcpy(pay.w, pay_host, (size_t)pay_bytes);
   }
-  const int U = choose_unroll(B, plane, false);
-  const int epb = kThreads * 4 * (U == 4 ? 2 : U);
+  // One wide block per sample slice: 1,024 lanes where the plane fills them (256 or 512 for the small ones),
+  // U quads per lane and chunk.  A block holds up to kArmedHold quads per lane across the wait, so a sample
+  // gets one block per kArmedHold / U chunks — ONE at (256,4,5000) — and fewer when that would make more
+  // than 2 * kPackB polling blocks: every block reads its record across the link, and many small reads early in
+  // the kernel delay the label words.  A block with more chunks than it holds takes chunks blockIdx.x,
+  // blockIdx.x + gridDim.x, ...  No block waits for another one, so the grid need not be resident.
+  const int U = choose_unroll(B, plane, false) >= 2 ? 2 : 1;
+  // (PCGMIX_ARMED_THREADS = 256 | 512 caps the block for tuning runs; read once)
+  static const int max_threads = [] {
+    const char* env = getenv("PCGMIX_ARMED_THREADS");
+    const int v = env ? atoi(env) : 0;
+    return (v == 256 || v == 512) ? v : kArmedThreads;
+  }();
+  int threads = kThreads;
+  while (threads < max_threads && (long long)threads * 4 < plane) threads *= 2;
+  const int epb = threads * 4 * U;
   const unsigned chunks = (unsigned)((plane + epb - 1) / epb);
-  // every block resident at once: at most 2,048 blocks of four waves, each taking its sample's chunks
-  // blockIdx.x, blockIdx.x + gridDim.x, ...
-  unsigned per_sample = chunks;
-  while (per_sample > 1 && per_sample * (unsigned)B > 2048u) per_sample = (per_sample + 1) / 2;
+  const unsigned held = U == 1 ? 1u : (unsigned)(kArmedHold / U);
+  unsigned per_sample = (chunks + held - 1) / held;
+  while (per_sample > 1 && per_sample * (unsigned)B > 2u * kPackB) per_sample = (per_sample + 1) / 2;
   // own cycle edges: saturation only (the boundaries are validated after the launch, beside the label wait)
   EdgePack edges;
   edges.n = 0;
@@ -1062,7 +1076,7 @@ int pcgmix::launch_mix_armed(const float* x, float* y, const ArmedArgs& a, int B
     edges.n = B;
     if (edges_out) memcpy(edges_out, edges.w, sizeof(uint32_t) * (size_t)B);
   }
-  dim3 grid(per_sample, (unsigned)B), block(kThreads);
+  dim3 grid(per_sample, (unsigned)B), block((unsigned)threads);
   if (U >= 2)
     hipLaunchKernelGGL((mix_armed_kernel<2>), grid, block, 0, s, x, y, a, B, C, T, epb,
                        (int)chunks, pay, static_cast<uint4*>(pay_dst), edges);

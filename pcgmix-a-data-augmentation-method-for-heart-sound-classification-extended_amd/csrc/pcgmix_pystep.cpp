@@ -2,15 +2,23 @@
 //
 // What augmentations.gate_passes() plus the armed branch of augmentations.splice_plain() do in Python —
 // eligibility, probability gate, output tensor, pcgmix_augment_plain_begin_edges, lambda from numpy's
-// global stream, partner buffer, pcgmix_augment_plain_finish — is done here with the plain CPython C API.
-// Nothing is linked: torch and numpy objects are reached through their Python methods, and the library
-// entry points are called through the addresses the binding takes out of the ctypes.CDLL that
+// global stream, partner buffer, pcgmix_augment_plain_finish — is done here.  The tensors are reached through
+// libtorch (THPVariable_Unpack and at::Tensor accessors, at::empty_like, c10's current HIP stream): some twenty
+// CPython attribute and method calls stood between the call and the launch otherwise, all of them on the
+// step's host-GPU loop.  The module therefore links torch's libraries and loads only into a process that has
+// imported torch.  numpy objects are reached through their Python methods (they run beside the kernel), and
+// the library entry points are called through the addresses the binding takes out of the ctypes.CDLL that
 // _lib.load() holds, so both callers use one library instance and one step context.
 //
 // step() never raises for an input it does not serve: it returns None ("declined") before anything is
 // launched and the Python path produces the result or the error it always did.
 #define PY_SSIZE_T_CLEAN
 #include <Python.h>
+
+#include <ATen/core/Tensor.h>
+#include <ATen/ops/empty_like.h>
+#include <c10/hip/HIPStream.h>
+#include <torch/csrc/autograd/python_variable.h>
 
 #include <cstdint>
 #include <cstdio>
@@ -26,11 +34,6 @@ decltype(&pcgmix_augment_plain_begin_edges) fn_begin = nullptr;
 decltype(&pcgmix_augment_plain_finish) fn_finish = nullptr;
 decltype(&pcgmix_augment_plain_abort) fn_abort = nullptr;
 
-PyObject* o_empty_like = nullptr;      // torch.empty_like
-PyObject* o_raw_stream = nullptr;      // torch._C._cuda_getCurrentRawStream (device index -> hipStream_t)
-PyObject* o_tensor_type = nullptr;     // torch.Tensor
-PyObject* o_float32 = nullptr;         // torch.float32
-PyObject* o_int64 = nullptr;           // torch.int64
 PyObject* o_np_random = nullptr;       // the numpy.random module (seed / beta are looked up per call)
 PyObject* o_np_empty = nullptr;        // numpy.empty
 PyObject* o_np_int64 = nullptr;        // numpy.dtype('int64')
@@ -43,8 +46,7 @@ PyObject* o_check = nullptr;           // _lib.check(err, what)
 bool bound = false;
 
 // interned attribute and method names
-PyObject *s_is_cuda, *s_dtype, *s_shape, *s_is_contiguous, *s_data_ptr, *s_device, *s_index, *s_seed, *s_beta,
-    *s_TAPE;
+PyObject *s_seed, *s_beta, *s_TAPE;
 PyObject *s_begin_name, *s_finish_name;
 
 struct Ref {                            // owned reference, released at scope exit
@@ -62,55 +64,19 @@ PyObject* declined() {                  // whatever made a probe fail is the Pyt
   Py_RETURN_NONE;
 }
 
-// True / False / -1 (error set) of a tensor's boolean method or attribute
-int truth_of_method(PyObject* t, PyObject* name) {
-  Ref r(PyObject_CallMethodNoArgs(t, name));
-  return r ? PyObject_IsTrue(r.p) : -1;
-}
-
-int truth_of_attr(PyObject* t, PyObject* name) {
-  Ref r(PyObject_GetAttr(t, name));
-  return r ? PyObject_IsTrue(r.p) : -1;
-}
-
-bool dtype_is(PyObject* t, PyObject* want) {
-  Ref r(PyObject_GetAttr(t, s_dtype));
-  return r && r.p == want;
-}
-
-// data_ptr() of a tensor; false with an error set when the call failed
-bool tensor_address(PyObject* t, void** out) {
-  Ref r(PyObject_CallMethodNoArgs(t, s_data_ptr));
-  if (!r) return false;
-  *out = PyLong_AsVoidPtr(r.p);
-  return !(*out == nullptr && PyErr_Occurred());
-}
-
-// sizes of a tensor of exactly `nd` dimensions out of its .shape (a tuple subclass)
-bool tensor_sizes(PyObject* t, int nd, long long* out, Ref& shape) {
-  shape.p = PyObject_GetAttr(t, s_shape);
-  if (!shape || !PyTuple_Check(shape.p) || PyTuple_GET_SIZE(shape.p) != nd) return false;
-  for (int i = 0; i < nd; ++i) {
-    out[i] = PyLong_AsLongLong(PyTuple_GET_ITEM(shape.p, i));
-    if (out[i] == -1 && PyErr_Occurred()) return false;
-  }
-  return true;
-}
-
-bool is_tensor(PyObject* o) { return PyObject_TypeCheck(o, reinterpret_cast<PyTypeObject*>(o_tensor_type)); }
+// A torch.Tensor of exactly that type (or a Parameter).  A subclass is declined: its methods may be
+// overridden (__torch_function__), and torch.empty_like would hand back the subclass.
+bool is_tensor(PyObject* o) { return THPVariable_CheckExact(o); }
 
 // The (B, 5) int64 boundaries on the host: a contiguous CPU int64 tensor's storage, or a C-contiguous int64
 // ndarray through the buffer protocol (`view` then holds the export until the step is over).
 bool frames_address(PyObject* frames, long long B, const int64_t** out, Py_buffer* view, bool* have_view) {
   if (is_tensor(frames)) {
-    long long s[2];
-    Ref shape;
-    void* p = nullptr;
-    if (!dtype_is(frames, o_int64) || truth_of_attr(frames, s_is_cuda) != 0 ||
-        truth_of_method(frames, s_is_contiguous) != 1 || !tensor_sizes(frames, 2, s, shape) || s[0] != B ||
-        s[1] != 5 || !tensor_address(frames, &p) || !p)
+    const at::Tensor& f = THPVariable_Unpack(frames);
+    if (!f.defined() || !f.is_cpu() || f.scalar_type() != at::kLong || f.dim() != 2 || f.size(0) != B ||
+        f.size(1) != 5 || !f.is_contiguous() || !f.data_ptr())
       return false;
-    *out = static_cast<const int64_t*>(p);
+    *out = static_cast<const int64_t*>(f.data_ptr());
     return true;
   }
   if (!PyObject_TypeCheck(frames, reinterpret_cast<PyTypeObject*>(o_ndarray_type))) return false;
@@ -184,25 +150,32 @@ PyObject* step(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
   if ((step_no == (unsigned long long)-1 && PyErr_Occurred()) || step_no > 0xFFFFFFFFull) return declined();
 
   if (!is_tensor(data) || !is_tensor(ohe)) return declined();
-  long long ds[3], os[2];
-  Ref dshape, oshape;
-  if (truth_of_attr(data, s_is_cuda) != 1 || !dtype_is(data, o_float32) || !tensor_sizes(data, 3, ds, dshape) ||
-      ds[0] <= 0 || truth_of_method(data, s_is_contiguous) != 1)
-    return declined();
-  if (truth_of_attr(ohe, s_is_cuda) != 1 || !dtype_is(ohe, o_int64) || !tensor_sizes(ohe, 2, os, oshape) ||
-      os[0] != ds[0] || truth_of_method(ohe, s_is_contiguous) != 1)
-    return declined();
-  const long long B = ds[0], C = ds[1], T = ds[2], K = os[1];
-  if (B > INT32_MAX || C > INT32_MAX || T > INT32_MAX || K > INT32_MAX) return declined();
+  long long B = 0, C = 0, T = 0, K = 0;
   BufferHold hold;
   const int64_t* fr = nullptr;
-  if (!frames_address(frames, B, &fr, &hold.view, &hold.have)) return declined();
   void *x = nullptr, *lab = nullptr;
-  if (!tensor_address(data, &x) || !tensor_address(ohe, &lab)) return declined();
-  Ref device(PyObject_GetAttr(data, s_device));
-  if (!device) return declined();
-  Ref index(PyObject_GetAttr(device.p, s_index));
-  if (!index || !PyLong_CheckExact(index.p)) return declined();
+  int device_index = -1;
+  try {                                   // whatever torch throws here is the Python path's to report
+    const at::Tensor& d = THPVariable_Unpack(data);
+    const at::Tensor& o = THPVariable_Unpack(ohe);
+    if (!d.defined() || !d.is_cuda() || d.scalar_type() != at::kFloat || d.dim() != 3 || d.size(0) <= 0 ||
+        !d.is_contiguous())
+      return declined();
+    if (!o.defined() || !o.is_cuda() || o.scalar_type() != at::kLong || o.dim() != 2 || o.size(0) != d.size(0) ||
+        !o.is_contiguous())
+      return declined();
+    B = d.size(0), C = d.size(1), T = d.size(2), K = o.size(1);
+    if (B > INT32_MAX || C > INT32_MAX || T > INT32_MAX || K > INT32_MAX) return declined();
+    if (!frames_address(frames, B, &fr, &hold.view, &hold.have)) return declined();
+    x = d.data_ptr();
+    lab = o.data_ptr();
+    device_index = d.device().index();
+  } catch (...) {
+    return declined();
+  }
+  if (device_index < 0) return declined();
+  Ref index(PyLong_FromLong(device_index));
+  if (!index) return declined();
   pcgmix_ctx* ctx = context_of(index.p);
   if (!ctx) return PyErr_Occurred() ? nullptr : declined();
 
@@ -214,14 +187,19 @@ PyObject* step(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
   }
 
   // 3. the output, the stream, the launch
-  Ref out(PyObject_CallOneArg(o_empty_like, data));
-  if (!out) return nullptr;
+  Ref out;
   void* y = nullptr;
-  if (!tensor_address(out.p, &y)) return nullptr;
-  Ref stream_obj(PyObject_CallOneArg(o_raw_stream, index.p));
-  if (!stream_obj) return nullptr;
-  pcgmix_stream_t stream = static_cast<pcgmix_stream_t>(PyLong_AsVoidPtr(stream_obj.p));
-  if (!stream && PyErr_Occurred()) return nullptr;
+  pcgmix_stream_t stream = nullptr;
+  try {
+    at::Tensor made = at::empty_like(THPVariable_Unpack(data));
+    y = made.data_ptr();
+    stream = static_cast<pcgmix_stream_t>(
+        c10::hip::getCurrentHIPStream(static_cast<c10::DeviceIndex>(device_index)).stream());
+    out.p = THPVariable_Wrap(std::move(made));         // wrapped once, for the return tuple
+  } catch (...) {
+    return declined();                                  // nothing launched: torch.empty_like reports it
+  }
+  if (!out) return nullptr;
   int err;
   Py_BEGIN_ALLOW_THREADS
   err = fn_begin(ctx, static_cast<const float*>(x), static_cast<float*>(y), static_cast<const int64_t*>(lab),
@@ -248,7 +226,9 @@ PyObject* step(PyObject*, PyObject* const* args, Py_ssize_t nargs) {
     const double lam64 = PyFloat_AsDouble(drawn.p);
     if (lam64 == -1.0 && PyErr_Occurred()) break;
     lam = (float)lam64;                                     // rounds like ctypes.c_float / np.float32
-    mix.p = PyObject_CallFunctionObjArgs(o_np_empty, PyTuple_GET_ITEM(dshape.p, 0), o_np_int64, nullptr);
+    Ref rows(PyLong_FromLongLong(B));
+    if (!rows) break;
+    mix.p = PyObject_CallFunctionObjArgs(o_np_empty, rows.p, o_np_int64, nullptr);
     if (!mix) break;
     if (PyObject_GetBuffer(mix.p, &mv, PyBUF_WRITABLE) != 0) break;
     have_mv = true;
@@ -317,15 +297,13 @@ PyObject* bind(PyObject*, PyObject* d) {
       !take_address(d, "pcgmix_augment_plain_begin_edges", &fn_begin) ||
       !take_address(d, "pcgmix_augment_plain_finish", &fn_finish) ||
       !take_address(d, "pcgmix_augment_plain_abort", &fn_abort) ||
-      !take(d, "empty_like", &o_empty_like) || !take(d, "raw_stream", &o_raw_stream) ||
-      !take(d, "Tensor", &o_tensor_type) || !take(d, "float32", &o_float32) || !take(d, "int64", &o_int64) ||
       !take(d, "np_random", &o_np_random) || !take(d, "np_empty", &o_np_empty) ||
       !take(d, "np_int64", &o_np_int64) || !take(d, "ndarray", &o_ndarray_type) || !take(d, "lib", &o_lib) ||
       !take(d, "contexts", &o_ctx) || !take(d, "step_context", &o_step_context) ||
       !take(d, "check_splice", &o_check_splice) || !take(d, "check", &o_check))
     return nullptr;
-  if (!PyType_Check(o_tensor_type) || !PyType_Check(o_ndarray_type) || !PyDict_Check(o_ctx)) {
-    PyErr_SetString(PyExc_TypeError, "_pcgmix_step.bind: Tensor and ndarray must be types, contexts a dict");
+  if (!PyType_Check(o_ndarray_type) || !PyDict_Check(o_ctx)) {
+    PyErr_SetString(PyExc_TypeError, "_pcgmix_step.bind: ndarray must be a type, contexts a dict");
     return nullptr;
   }
   bound = true;
@@ -353,10 +331,17 @@ PyMODINIT_FUNC PyInit__pcgmix_step(void) {
                  PY_MAJOR_VERSION, PY_MINOR_VERSION, Py_GetVersion());
     return nullptr;
   }
+  // torch's Python layer must be up: THPVariable_CheckExact compares against the classes `import torch` registers
+  {
+    Ref name(PyUnicode_FromString("torch"));
+    Ref torch_module(name ? PyImport_GetModule(name.p) : nullptr);
+    if (!torch_module) {
+      if (!PyErr_Occurred()) PyErr_SetString(PyExc_ImportError, "_pcgmix_step needs torch imported first");
+      return nullptr;
+    }
+  }
   struct { PyObject** slot; const char* text; } names[] = {
-      {&s_is_cuda, "is_cuda"}, {&s_dtype, "dtype"}, {&s_shape, "shape"}, {&s_is_contiguous, "is_contiguous"},
-      {&s_data_ptr, "data_ptr"}, {&s_device, "device"}, {&s_index, "index"}, {&s_seed, "seed"},
-      {&s_beta, "beta"}, {&s_TAPE, "TAPE"}, {&s_begin_name, "pcgmix_augment_plain_begin_edges"},
+      {&s_seed, "seed"}, {&s_beta, "beta"}, {&s_TAPE, "TAPE"}, {&s_begin_name, "pcgmix_augment_plain_begin_edges"},
       {&s_finish_name, "pcgmix_augment_plain_finish"}};
   for (auto& n : names)
     if (!(*n.slot = PyUnicode_InternFromString(n.text))) return nullptr;

@@ -1,8 +1,8 @@
 """The armed plain step as a timeline (probe build, -DPCGMIX_PHASE_CLOCK): 100 MHz clock at block (0,0)
-entry / labels flagged, and per sample: relay entry / relay saw the host's record / block (1,b) saw the
-relayed record / block (1,b) done / block (1,b) through its early phase (the loads and stores in front of
-the wait).  Two launches are kept (parity of the sequence number), so the gap
-between one kernel's last block and the next kernel's entry is visible.
+entry / labels flagged, and per sample, from the sample's first block: entry / its wave 0 saw the host's
+record / the block is past the barrier behind the LDS hand-over / the block is done (all its waves) / it is
+through its early phase (the loads and stores in front of the wait).  Two launches are kept (parity of the
+sequence number), so the gap between one kernel's last block and the next kernel's entry is visible.
 python profiles/probes/armed_phase_clock.py   (GPU box, repo root)"""
 import ctypes, glob, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -44,13 +44,14 @@ for (B, C, T) in [(256, 4, 5000), (256, 1, 5000)]:
         last = int(np.argmax(t[:, 256, 0])); prev = 1 - last
         L, P = t[last], t[prev]
         e0 = L[256, 0]
-        print((B, C, T), "kernel entry -> labels flagged %.2f | flagged -> relays saw records: median %.2f min %.2f max %.2f | "
-              "relay -> block 1 saw: median %.2f max %.2f | body (block 1): median %.2f max %.2f | entry -> last block done %.2f | "
-              "relay entry after kernel entry: median %.2f max %.2f | previous kernel's last block done -> this entry %.2f | "
-              "period (entry to entry) %.2f | block 1 early phase done after kernel entry: median %.2f max %.2f, "
-              "before the relay saw the record: median %.2f min %.2f" %
+        print((B, C, T), "kernel entry -> labels flagged %.2f | flagged -> polls saw records: median %.2f min %.2f max %.2f | "
+              "poll saw -> block past the barrier: median %.2f max %.2f | body (barrier -> block done): median %.2f max %.2f | "
+              "entry -> last block done %.2f (median block %.2f) | "
+              "block entry after kernel entry: median %.2f max %.2f | previous kernel's last block done -> this entry %.2f | "
+              "period (entry to entry) %.2f | early phase done after kernel entry: median %.2f max %.2f, "
+              "before the poll saw the record: median %.2f min %.2f" %
               (L[256, 1] - e0, np.median(L[:B, 1]) - L[256, 1], L[:B, 1].min() - L[256, 1], L[:B, 1].max() - L[256, 1],
                np.median(L[:B, 2] - L[:B, 1]), (L[:B, 2] - L[:B, 1]).max(), np.median(L[:B, 3] - L[:B, 2]),
-               (L[:B, 3] - L[:B, 2]).max(), L[:B, 3].max() - e0, np.median(L[:B, 0]) - e0, L[:B, 0].max() - e0,
-               e0 - P[:B, 3].max(), e0 - P[256, 0], np.median(L[:B, 4]) - e0, L[:B, 4].max() - e0,
+               (L[:B, 3] - L[:B, 2]).max(), L[:B, 3].max() - e0, np.median(L[:B, 3]) - e0, np.median(L[:B, 0]) - e0,
+               L[:B, 0].max() - e0, e0 - P[:B, 3].max(), e0 - P[256, 0], np.median(L[:B, 4]) - e0, L[:B, 4].max() - e0,
                np.median(L[:B, 1] - L[:B, 4]), (L[:B, 1] - L[:B, 4]).min()), flush=True)
