@@ -1167,7 +1167,11 @@ int pcgmix_bnrp_eval_bwd_f32(const float* y, const float* dz, const float* gamma
  *   np.interp restated exactly, including xp that decreases somewhere (numpy's search with the
  *   previous query's result as its guess).  workspace: device, pcgmix_time_warp_workspace_bytes
  *   (B, C, T) bytes (0 = none needed: the row lives in LDS); n_knots 2..64, T >= 2.
- * x and y are distinct (B, C, T) float32 tensors.                                             */
+ * x and y are distinct (B, C, T) float32 tensors.
+ * Refused with hipErrorInvalidValue, nothing launched: a NULL pointer among those named above,
+ * x == y, B < 0, C <= 0, T <= 0 (T < 2 for the two warps), n_knots outside 2..64, workspace NULL
+ * when pcgmix_time_warp_workspace_bytes is not 0.  Span ends outside [0, T] are clipped, a
+ * span with s1 <= s0 zeroes nothing.                                                          */
 int pcgmix_blend_rows_f32(const float* x, float* y, const int32_t* mix, float lam, int B, int C,
                           int T, pcgmix_stream_t stream);
 int pcgmix_warp_rows_f32(const float* x, float* y, const double* knots, const double* spline_op,
@@ -1204,6 +1208,8 @@ int pcgmix_time_warp_row_f64(const double* spline_op, const double* knots, int n
  *     x[b, c, rect[b][0] : rect[b][1], rect[b][2] : rect[b][3]] = 0   for every channel c;
  *   rect device int32 (B, 4), clipped to the plane; max_area an upper bound of the rectangles'
  *   clipped areas (it sizes the grid; F*W is always safe).  Only the zeroed elements are written.
+ *   max_area == 0 returns 0 and launches nothing; max_area < 0, F <= 0, W <= 0, C <= 0, B < 0 and a
+ *   NULL x or rect are refused with hipErrorInvalidValue.
  * pcgmix_piecewise_rows_f32 — cutmix (:574-597, cutmix_multidim_tensors :34-51) and
  *   durratiocutmix (:599-617, cutmix_keepdur_multidim_tensors :223-249):
  *     y (B, C, F, Wo) from x (B, C, F, W).  segs device int32 (B, PCGMIX_PIECE_SEGS, 4), per

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(kThreadsB) void zero_spans_kernel(float* __restrict
   const long long row = blockIdx.x;
   const int b = (int)(row / C);
   int s0 = spans[2 * b], s1 = spans[2 * b + 1];
-  s0 = s0 < 0 ? 0 : s0;
+  s0 = s0 < 0 ? 0 : (s0 > T ? T : s0);  // above as well: s0 + threadIdx.x must not wrap
   s1 = s1 > T ? T : s1;
   float* xr = x + (size_t)row * T;
   for (int t = s0 + threadIdx.x; t < s1; t += kThreadsB) xr[t] = 0.f;
