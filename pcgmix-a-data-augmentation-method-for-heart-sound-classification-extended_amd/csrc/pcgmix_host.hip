@@ -260,60 +260,173 @@ struct SeededBlock {
   }
 };
 
-// Random(seed).sample(members, k = n) -> out[0 .. n-1], bit-identical to Lib/random.py's pool branch
+// The partner draw: every label group, in order of first appearance, permuted by a FRESH
+//     Random(seed).sample(members, k = n)
+// bit-identical to Lib/random.py's pool branch
 //     for i in range(n): j = _randbelow(n - i); result[i] = pool[j]; pool[j] = pool[n - i - 1]
 // with _randbelow(m) = the first getrandbits(m.bit_length()) below m (one 32-bit word each: n < 2^31).
 // About 30 % of the words are rejected, unpredictably: the loop has no branch on the draw — a word
-// advances i by its accept bit, and a rejected one (r < 2^k <= 2 m <= 2 n) reads and rewrites a pool entry
-// that does not matter.  pool: scratch of 2 n entries.  A group that needs more than the block's 624 words
-// (in expectation at about 430 members) goes on with an ordinary generator from the stored state.
-void py_sample_all(const SeededBlock& sb, const int64_t* members, size_t n, int64_t* pool, int64_t* out) {
-  std::memcpy(pool, members, n * sizeof(int64_t));
-  std::memset(pool + n, 0, n * sizeof(int64_t));
-  size_t i = 0;
-  int pos = 0;
-  while (i < n && pos < 624) {
-    const uint64_t m = n - i;
-    const uint64_t r = sb.temp[pos++] >> (__builtin_clzll(m) - 32);      // getrandbits(m.bit_length())
-    const int64_t acc = (int64_t)(r < m);
-    const int64_t at = pool[r], last = pool[m - 1];
-    out[i] = at;
-    pool[r] = at ^ ((at ^ last) & -acc);
-    i += (size_t)acc;
+// advances i by its accept bit, and a rejected one (r < 2^k <= 2 m <= 2 n) reads a pool entry that does
+// not matter and writes it where the accepted one will land.
+// The groups are independent and all read the same words temp[0..]: up to kDrawLanes of them advance in
+// LOCK STEP, one word per iteration applied to each, so the dependent chain i -> m -> clz -> shift ->
+// compare -> i is as deep as the largest group of a round and not as the sum of them.
+// Scratch of one draw; lives in the step context (no allocation per step once it has its size).
+constexpr int kDrawLanes = 4;
+
+struct DrawScratch {
+  std::vector<int32_t> gid, start, fill;   // group of sample b | members of g: start[g] .. start[g + 1] of the order
+  std::vector<int32_t> buf;                // the order (B entries) and the pools (2 B), int16 or int32 entries
+  std::vector<int64_t> wide;               // labels outside 0 .. 255 in order of first appearance, and
+  std::vector<int32_t> wide_gid;           //   their groups
+  int16_t first[256];                      // label 0 .. 255 -> group, -1: not seen in this step
+  uint8_t seen[256];
+  DrawScratch() { std::memset(first, 0xff, sizeof(first)); }
+};
+
+// Groups of equal label in order of first appearance (augmentations.py:500-510) in one counting pass:
+// gid[b], and the members' count of group g in start[g + 1].  Returns the number of groups.
+template <class L>
+int label_groups(const L* labels, int B, DrawScratch& d) {
+  d.gid.resize((size_t)B);
+  d.start.resize((size_t)B + 2);
+  d.wide.clear();
+  d.wide_gid.clear();
+  int n_groups = 0, n_seen = 0;
+  d.start[0] = 0;
+  for (int b = 0; b < B; ++b) {
+    const L v = labels[b];
+    int g;
+    if ((uint64_t)v < 256u) {
+      g = d.first[(size_t)v];
+      if (g < 0) {
+        g = n_groups++;
+        d.first[(size_t)v] = (int16_t)g;          // (at most 256 groups come through this table)
+        d.seen[n_seen++] = (uint8_t)v;
+        d.start[(size_t)g + 1] = 0;
+      }
+    } else {
+      size_t k = 0;
+      while (k < d.wide.size() && d.wide[k] != (int64_t)v) ++k;
+      if (k == d.wide.size()) {
+        d.wide.push_back((int64_t)v);
+        d.wide_gid.push_back(n_groups++);
+        d.start[(size_t)d.wide_gid[k] + 1] = 0;
+      }
+      g = d.wide_gid[k];
+    }
+    d.gid[(size_t)b] = g;
+    ++d.start[(size_t)g + 1];
   }
-  if (i < n) {
-    PyRandom g = sb.st;
-    g.idx = 624;                                     // the block is used up: regenerate on the next word
-    for (; i < n; ++i) {
-      const uint64_t m = n - i, j = g.randbelow(m);
-      out[i] = pool[j];
-      pool[j] = pool[m - 1];
+  for (int k = 0; k < n_seen; ++k) d.first[d.seen[k]] = -1;
+  return n_groups;
+}
+
+template <class P>
+struct DrawLane {
+  P* pool;            // 2 n entries: the members, then zeros
+  const P* mem;       // the group's members in ascending order
+  uint32_t i, n;
+};
+
+// N unfinished groups, one word of the block per iteration for all of them, until one of them is done
+// or the block is used up.  Returns the position in the block.
+template <int N, class P, bool W16>
+int sample_lockstep(const uint32_t* temp, int pos, DrawLane<P>* lane, int64_t* mix_out, int16_t* mix16) {
+  P* pool[N];
+  const P* mem[N];
+  uint32_t i[N], n[N];
+  for (int k = 0; k < N; ++k) { pool[k] = lane[k].pool; mem[k] = lane[k].mem; i[k] = lane[k].i; n[k] = lane[k].n; }
+  for (;;) {
+    bool go = pos < 624;
+    for (int k = 0; k < N; ++k) go &= i[k] < n[k];
+    if (!go) break;
+    const uint32_t w = temp[pos++];
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      const uint32_t m = n[k] - i[k];
+      const uint32_t r = w >> __builtin_clz(m);              // getrandbits(m.bit_length())
+      const uint32_t acc = (uint32_t)(r < m);
+      const P at = pool[k][r], last = pool[k][m - 1];
+      const P b = mem[k][i[k]];
+      mix_out[b] = (int64_t)at;
+      if (W16) mix16[b] = (int16_t)at;
+      pool[k][r] = acc ? last : at;
+      i[k] += acc;
+    }
+  }
+  for (int k = 0; k < N; ++k) lane[k].i = i[k];
+  return pos;
+}
+
+// mix_out[b] (and mix16[b]) for every sample: gid[b] in [0, n_groups), members' counts in d.start[g + 1].
+// A group that needs more than the block's 624 words (in expectation at about 430 members) goes on alone
+// with an ordinary generator from the stored state.
+template <class P, bool W16>
+void draw_groups_as(const SeededBlock& sb, DrawScratch& d, const int32_t* gid, int B, int n_groups,
+                    int64_t* mix_out, int16_t* mix16) {
+  d.fill.resize((size_t)n_groups + 1);
+  d.start[0] = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    d.fill[(size_t)g] = d.start[(size_t)g];
+    d.start[(size_t)g + 1] += d.start[(size_t)g];
+  }
+  d.buf.resize((size_t)3 * B + 4);
+  P* order = reinterpret_cast<P*>(d.buf.data());
+  P* pools = order + B;
+  for (int b = 0; b < B; ++b) order[d.fill[(size_t)gid[b]]++] = (P)b;
+  for (int g0 = 0; g0 < n_groups; g0 += kDrawLanes) {
+    DrawLane<P> lane[kDrawLanes];
+    int na = 0;
+    for (int g = g0; g < n_groups && g < g0 + kDrawLanes; ++g) {
+      const size_t at = (size_t)d.start[(size_t)g], n = (size_t)d.start[(size_t)g + 1] - at;
+      if (!n) continue;
+      P* pool = pools + 2 * at;
+      std::memcpy(pool, order + at, n * sizeof(P));
+      std::memset(pool + n, 0, n * sizeof(P));
+      lane[na++] = DrawLane<P>{pool, order + at, 0u, (uint32_t)n};
+    }
+    int pos = 0;
+    while (na) {
+      switch (na) {
+        case 1: pos = sample_lockstep<1, P, W16>(sb.temp, pos, lane, mix_out, mix16); break;
+        case 2: pos = sample_lockstep<2, P, W16>(sb.temp, pos, lane, mix_out, mix16); break;
+        case 3: pos = sample_lockstep<3, P, W16>(sb.temp, pos, lane, mix_out, mix16); break;
+        default: pos = sample_lockstep<4, P, W16>(sb.temp, pos, lane, mix_out, mix16); break;
+      }
+      int left = 0;
+      for (int k = 0; k < na; ++k)
+        if (lane[k].i < lane[k].n) lane[left++] = lane[k];
+      na = left;
+      if (pos >= 624) break;
+    }
+    for (int k = 0; k < na; ++k) {                     // the block is used up: regenerate on the next word
+      PyRandom g = sb.st;
+      g.idx = 624;
+      const DrawLane<P>& l = lane[k];
+      for (uint32_t i = l.i; i < l.n; ++i) {
+        const uint64_t m = l.n - i, j = g.randbelow(m);
+        const P b = l.mem[i];
+        mix_out[b] = (int64_t)l.pool[j];
+        if (W16) mix16[b] = (int16_t)l.pool[j];
+        l.pool[j] = l.pool[m - 1];
+      }
     }
   }
 }
 
-// Members of every group in ascending order, group after group, in ONE pass over the batch behind a count:
-// start[g] .. start[g + 1] of `order`.  gid[b] in [0, n_groups).
-void group_members(const int* gid, int B, int n_groups, std::vector<int64_t>& order, std::vector<size_t>& start) {
-  start.assign((size_t)n_groups + 1, 0);
-  for (int b = 0; b < B; ++b) ++start[(size_t)gid[b] + 1];
-  for (int g = 0; g < n_groups; ++g) start[(size_t)g + 1] += start[(size_t)g];
-  order.resize((size_t)B);
-  std::vector<size_t> fill(start.begin(), start.end() - 1);
-  for (int b = 0; b < B; ++b) order[fill[(size_t)gid[b]]++] = b;
-}
-
-// groups of equal key in order of first appearance (augmentations.py:500-510): gid[b], returns their number
-int group_ids(const int64_t* keys_in, int B, std::vector<int64_t>& keys, std::vector<int>& gid) {
-  keys.clear();
-  gid.resize((size_t)B);
-  for (int b = 0; b < B; ++b) {
-    size_t g = 0;
-    while (g < keys.size() && keys[g] != keys_in[b]) ++g;
-    if (g == keys.size()) keys.push_back(keys_in[b]);
-    gid[(size_t)b] = (int)g;
+// The pool holds sample indices: int16 up to B = 32767 (512 bytes at B = 256), int32 beyond.
+void draw_groups(const SeededBlock& sb, DrawScratch& d, const int32_t* gid, int B, int n_groups,
+                 int64_t* mix_out, int16_t* mix16) {
+  if (B > 32767) {
+    draw_groups_as<int32_t, false>(sb, d, gid, B, n_groups, mix_out, nullptr);
+    if (mix16)
+      for (int b = 0; b < B; ++b) mix16[b] = (int16_t)mix_out[b];
+  } else if (mix16) {
+    draw_groups_as<int16_t, true>(sb, d, gid, B, n_groups, mix_out, mix16);
+  } else {
+    draw_groups_as<int16_t, false>(sb, d, gid, B, n_groups, mix_out, nullptr);
   }
-  return (int)keys.size();
 }
 
 }  // namespace
@@ -334,17 +447,12 @@ extern "C" int pcgmix_partner_permutation_i64(const int32_t* group_id, int B, in
   if (!group_id || !mix || B < 0 || n_groups < 0) return hipErrorInvalidValue;
   for (int b = 0; b < B; ++b)
     if (group_id[b] < 0 || group_id[b] >= n_groups) return hipErrorInvalidValue;
-  std::vector<int64_t> order, pool((size_t)2 * B + 2), perm((size_t)B + 1);
-  std::vector<size_t> start;
-  group_members(group_id, B, n_groups, order, start);
+  static thread_local DrawScratch d;               // (the step context has its own)
+  d.start.assign((size_t)n_groups + 2, 0);
+  for (int b = 0; b < B; ++b) ++d.start[(size_t)group_id[b] + 1];
   SeededBlock* sb = static_cast<SeededBlock*>(::operator new(sizeof(SeededBlock)));
   sb->make(seed);                                   // a fresh Random(seed) per group, as the reference
-  for (int g = 0; g < n_groups; ++g) {
-    const size_t n = start[(size_t)g + 1] - start[(size_t)g];
-    const int64_t* idx = order.data() + start[(size_t)g];
-    py_sample_all(*sb, idx, n, pool.data(), perm.data());
-    for (size_t i = 0; i < n; ++i) mix[idx[i]] = perm[i];
-  }
+  draw_groups(*sb, d, group_id, B, n_groups, mix, nullptr);
   ::operator delete(sb);
   return hipSuccess;
 }
@@ -407,10 +515,10 @@ extern "C" int pcgmix_splice_same_label_f32(const float* x, float* y, const int6
       T <= 0 || (knots && (!spline_op || n_knots < 2)))
     return hipErrorInvalidValue;
   {
-    std::vector<int64_t> keys;
-    std::vector<int> gid;
-    const int n_groups = group_ids(labels, B, keys, gid);
-    const int perr = pcgmix_partner_permutation_i64(gid.data(), B, n_groups, step, mix_out);
+    DrawScratch d;
+    const int n_groups = label_groups(labels, B, d);
+    for (int g = 0; g < n_groups; ++g) d.start[(size_t)g + 1] = 0;     // (the entry point counts for itself)
+    const int perr = pcgmix_partner_permutation_i64(d.gid.data(), B, n_groups, step, mix_out);
     if (perr) return perr;
   }
   int32_t* st = static_cast<int32_t*>(staging);
@@ -610,9 +718,7 @@ struct pcgmix_ctx {
   std::map<std::pair<int, int>, double*> ops;   // (T, n_knots) -> device operator
   uint64_t gate_step = ~0ull;      // generator seeded for this step (pcgmix_ctx_gate), reusable
   SeededBlock* seeded = nullptr;
-  std::vector<int64_t> keys, pool, idx, perm;   // per-step scratch of the partner draw
-  std::vector<int> gid;
-  std::vector<size_t> gstart;
+  DrawScratch draw;                // per-step scratch of the partner draw
   std::vector<char> payload;       // pcgmix_ctx_set_payload: rides with the next index block
   void* payload_dst = nullptr;
   void* ws = nullptr;              // displacement-search workspace of the saliency-guided step
@@ -942,26 +1048,16 @@ int pack_frames16(const int64_t* frames, int B, int T, int16_t* fr16) {
 }
 
 // Groups of equal label in order of first appearance (augmentations.py:500-510), each permuted by
-// a fresh Random(step).sample: one initialisation (c->seeded, its first block tempered), read per group.  Scratch
-// lives in the context (no allocation per step): gid[b] = group of sample b, members of group g =
-// the samples b with gid[b] == g in ascending order.
-void draw_partners(pcgmix_ctx* c, const int64_t* labels, int B, int64_t* mix_out, int32_t* mixp,
+// a fresh Random(step).sample: one initialisation (c->seeded, its first block tempered), read by all groups.
+// labels: int64 class labels, or the bytes the label kernel left (labels_wait_armed).
+template <class L>
+void draw_partners(pcgmix_ctx* c, const L* labels, int B, int64_t* mix_out, int32_t* mixp,
                    int16_t* mixp16 = nullptr) {
-  const int n_groups = group_ids(labels, B, c->keys, c->gid);
-  group_members(c->gid.data(), B, n_groups, c->idx, c->gstart);
-  c->pool.resize((size_t)2 * B + 2);
-  c->perm.resize((size_t)B + 1);
-  for (int g = 0; g < n_groups; ++g) {
-    const size_t n = c->gstart[(size_t)g + 1] - c->gstart[(size_t)g];
-    const int64_t* idx = c->idx.data() + c->gstart[(size_t)g];
-    py_sample_all(*c->seeded, idx, n, c->pool.data(), c->perm.data());
-    for (size_t i = 0; i < n; ++i) {
-      const int64_t v = c->perm[i];
-      mix_out[idx[i]] = v;
-      if (mixp16) mixp16[idx[i]] = (int16_t)v;
-      else mixp[idx[i]] = (int32_t)v;
-    }
-  }
+  DrawScratch& d = c->draw;
+  const int n_groups = label_groups(labels, B, d);
+  draw_groups(*c->seeded, d, d.gid.data(), B, n_groups, mix_out, mixp16);
+  if (!mixp16)
+    for (int b = 0; b < B; ++b) mixp[b] = (int32_t)mix_out[b];
 }
 
 // An event per GROUP of kSlotGroup slots: recorded behind the group's last enqueued work, waited
@@ -1040,7 +1136,8 @@ hipError_t labels_wait(pcgmix_ctx* c, hipStream_t s) {
 
 // The same wait while an ARMED kernel sits behind the label write on `s`: a stream synchronisation
 // would wait for that kernel, which waits for us.  Spin, then poll politely; give up after a minute.
-hipError_t labels_wait_armed(pcgmix_ctx* c, int B, int64_t* labels) {
+// labels: one byte per sample, room for B rounded up to a multiple of 4.
+hipError_t labels_wait_armed(pcgmix_ctx* c, int B, uint8_t* labels) {
   const uint32_t want = c->token;
   const unsigned long long* w = reinterpret_cast<const unsigned long long*>(c->lab);
   const int n = (B + 3) / 4;
@@ -1052,7 +1149,8 @@ hipError_t labels_wait_armed(pcgmix_ctx* c, int B, int64_t* labels) {
     while (have < n) {
       const unsigned long long v = __atomic_load_n(w + have, __ATOMIC_RELAXED);
       if ((uint32_t)(v >> 32) != want) break;
-      for (int j = 0; j < 4 && 4 * have + j < B; ++j) labels[4 * have + j] = (int64_t)((v >> (8 * j)) & 0xff);
+      const uint32_t four = (uint32_t)v;       // four labels, one byte each, as the draw reads them
+      std::memcpy(labels + 4 * have, &four, 4);
       ++have;
     }
     if (have == n) return hipSuccess;
@@ -1071,6 +1169,8 @@ hipError_t labels_wait_armed(pcgmix_ctx* c, int B, int64_t* labels) {
 hipError_t armed_prepare(pcgmix_ctx* c, hipStream_t s) {
   if (!c->rec_h) {
     const size_t bytes = sizeof(unsigned long long) * pcgmix::kPackB * pcgmix::kArmedRecWords;
+    // (The records in fine-grained device memory behind a large BAR — posted writes from the host, polls that
+    // stay on the device — were measured and not kept: DESIGN.md 3.6, profiles/r12_draw_records_ab.txt.)
     hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&c->rec_h), bytes,
                                  hipHostMallocMapped | hipHostMallocCoherent);
     if (e != hipSuccess) { c->rec_h = nullptr; return e; }
@@ -1098,21 +1198,27 @@ hipError_t armed_prepare(pcgmix_ctx* c, hipStream_t s) {
 // stamp = seq: the step's records; stamp = seq | kArmedAbort: every relay gives up
 void armed_write(pcgmix_ctx* c, uint32_t stamp, const int16_t* fr16, const int16_t* mix16, int B, float lam = 0.f) {
   const unsigned long long hi = (unsigned long long)stamp << 32;
+  uint32_t lam_bits;
+  std::memcpy(&lam_bits, &lam, 4);
+  // word = stamp | two 16-bit fields: own boundaries 0..4, partner, the partner's boundaries 0..4, 0
+  const auto word = [hi](int16_t lo, int16_t up) {
+    return hi | ((unsigned long long)(uint16_t)up << 16) | (uint16_t)lo;
+  };
   for (int b = 0; b < B; ++b) {
     unsigned long long* r = c->rec_h + (size_t)b * pcgmix::kArmedRecWords;
-    uint16_t v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     if (fr16) {
       const int m = (mix16[b] < 0 || mix16[b] >= B) ? b : mix16[b];
-      for (int k = 0; k < 5; ++k) {
-        v[k] = (uint16_t)fr16[b * 5 + k];
-        v[6 + k] = (uint16_t)fr16[m * 5 + k];
-      }
-      v[5] = (uint16_t)mix16[b];
+      const int16_t* f = fr16 + b * 5;
+      const int16_t* q = fr16 + m * 5;
+      __atomic_store_n(r + 0, word(f[0], f[1]), __ATOMIC_RELAXED);
+      __atomic_store_n(r + 1, word(f[2], f[3]), __ATOMIC_RELAXED);
+      __atomic_store_n(r + 2, word(f[4], mix16[b]), __ATOMIC_RELAXED);
+      __atomic_store_n(r + 3, word(q[0], q[1]), __ATOMIC_RELAXED);
+      __atomic_store_n(r + 4, word(q[2], q[3]), __ATOMIC_RELAXED);
+      __atomic_store_n(r + 5, word(q[4], 0), __ATOMIC_RELAXED);
+    } else {
+      for (int i = 0; i < 6; ++i) __atomic_store_n(r + i, hi, __ATOMIC_RELAXED);
     }
-    for (int i = 0; i < 6; ++i)
-      __atomic_store_n(r + i, hi | ((unsigned long long)v[2 * i + 1] << 16) | v[2 * i], __ATOMIC_RELAXED);
-    uint32_t lam_bits;
-    std::memcpy(&lam_bits, &lam, 4);
     __atomic_store_n(r + 6, hi | lam_bits, __ATOMIC_RELAXED);
   }
 }
@@ -1311,8 +1417,15 @@ int armed_finish(PlainStep& p) {
   p.lap(1);
   seed_for_step(c, p.step);
   p.lap(2);
-  int64_t lab64a[pcgmix::kPackB];
-  if (bad16 || (e = labels_wait_armed(c, B, lab64a)) != hipSuccess) {
+  uint8_t lab8[pcgmix::kPackB + 4];
+  // the rare ways out through the unarmed path take int64 labels
+  const auto unarmed = [&](const double* knots, int n_knots) {
+    int64_t lab64a[pcgmix::kPackB];
+    for (int b = 0; b < B; ++b) lab64a[b] = lab8[b];
+    return pcgmix_augment_plain_f32(c, o.x, o.y, nullptr, 0, lab64a, p.frames, p.step, p.lam, knots, n_knots,
+                                    p.mix_out, B, C, T, reinterpret_cast<pcgmix_stream_t>(s));
+  };
+  if (bad16 || (e = labels_wait_armed(c, B, lab8)) != hipSuccess) {
     armed_write(c, o.seq | pcgmix::kArmedAbort, nullptr, nullptr, B);
     if (o.warp) (void)slot_commit(c, o.my_slot, s);        // the kernel may still read the slot's knots
     return bad16 ? bad16 : (int)e;
@@ -1321,10 +1434,9 @@ int armed_finish(PlainStep& p) {
   if (moved) {                               // give the kernel up; the unarmed splice rewrites all of y behind it
     armed_write(c, o.seq | pcgmix::kArmedAbort, nullptr, nullptr, B);
     ++c->armed_aborted;
-    return pcgmix_augment_plain_f32(c, o.x, o.y, nullptr, 0, lab64a, p.frames, p.step, p.lam, nullptr, 0,
-                                    p.mix_out, B, C, T, reinterpret_cast<pcgmix_stream_t>(s));
+    return unarmed(nullptr, 0);
   }
-  draw_partners(c, lab64a, B, p.mix_out, nullptr, mix16);
+  draw_partners(c, lab8, B, p.mix_out, nullptr, mix16);
   p.lap(4);
   if (c->armed_stall_ms > 0) {
     timespec ts{c->armed_stall_ms / 1000, (long)(c->armed_stall_ms % 1000) * 1000000L};
@@ -1344,8 +1456,7 @@ int armed_finish(PlainStep& p) {
     if ((e = hipStreamSynchronize(s)) != hipSuccess) return (int)e;
     if (__atomic_load_n(c->flag + 8, __ATOMIC_ACQUIRE) == o.seq) {
       ++c->armed_aborted;
-      return pcgmix_augment_plain_f32(c, o.x, o.y, nullptr, 0, lab64a, p.frames, p.step, p.lam, p.knots,
-                                      p.n_knots, p.mix_out, B, C, T, reinterpret_cast<pcgmix_stream_t>(s));
+      return unarmed(p.knots, p.n_knots);
     }
   }
   p.lap(7);
