@@ -1267,6 +1267,35 @@ int pcgmix_mix_scale_f32(const float* x, float* y, const int32_t* frames, const 
                          const int32_t* off, float lam, const double* row, int B, int C, int T,
                          pcgmix_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Conv1d(k = 3, pad = 1, stride 1) of ResNet9-1D, channels innermost.              [device]
+ * csrc/pcgmix_conv3.hip (conv3_kernel).
+ *
+ * Replaces nn.Conv1d(c_in, c_out, kernel_size=3, padding=1) of conv_block (models.py:468-473)
+ * where its weights are frozen: the evaluation pass (train_model.py:591-670) and the frozen
+ * saliency pass (saliency.py:26-61).  No bias (the BatchNorm kernels above take it).
+ *   x (B, L, Cin)     the memory of a (B, Cin, 1, L) channels_last tensor
+ *   w (Cout, 3, Cin)  [o][tap][i], the memory ResNet9_myrtle gives its Conv1d weights
+ *   y (B, L, Cout)    y[b,l,o] = sum over tap, i of x[b, l+tap-1, i] * w[o,tap,i], zeros beyond
+ *                     both ends of every sample
+ * The input gradient of the layer is the same call on dy with w'[i][tap][o] = w[o][2-tap][i].
+ * One launch.  Every output element is ONE float32 fmaf chain over the 3*Cin products in a fixed
+ * order (groups of 16 input channels; in a group tap 0, 1, 2; in a tap the channels ascending) on
+ * v_mfma_f32_32x32x2_f32: no split-K, no atomics, so a sample's result is the same bits in every
+ * launch, at every B and at every place in the batch.
+ * pcgmix_conv3_supported: 1 for Cin % 4 == 0, 4 <= Cin <= 1024 and Cout == 4 or Cout % 16 == 0,
+ *   Cout <= 1024, else 0.  Host only: no device is touched.
+ * Refused with hipErrorInvalidValue, nothing launched and y untouched: unsupported widths, a NULL
+ * pointer, a pointer that is not 16-byte aligned, B < 0, L < 1, L * max(Cin, Cout) > INT_MAX.
+ * B == 0 returns 0 and launches nothing.  x and y may not overlap.
+ * pcgmix_conv3_tile: the kernel's tile constants, for tests that place shapes at tile edges:
+ *   which = 0 the positions of one M tile (128), 1 the input channels of one K group (16), else 0.
+ *   Host only.                                                                                  */
+int pcgmix_conv3_supported(int Cin, int Cout);
+int pcgmix_conv3_tile(int which);
+int pcgmix_conv3_nlc_f32(const float* x, const float* w, float* y, int B, int L, int Cin, int Cout,
+                         pcgmix_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -199,6 +199,9 @@ SIGNATURES = {
                                           _c_int, _c_int, _c_int, _c_int, _c_int, _ptr]),
     "pcgmix_bnrp_eval_bwd_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _c_float, _ptr, _ptr, _c_int,
                                           _c_int, _c_int, _c_int, _c_int, _c_int, _ptr]),
+    "pcgmix_conv3_supported": (_c_int, [_c_int, _c_int]),
+    "pcgmix_conv3_tile": (_c_int, [_c_int]),
+    "pcgmix_conv3_nlc_f32": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr]),
 }
 
 _lib = None

@@ -6,7 +6,8 @@
 
 Both keep the reference's ``forward(x, depth=None, pass_part=None)`` signature; the training
 loop calls ``model(data, depth=0, pass_part='second')`` (train_model.py:537), which is the plain
-full forward pass.  Convolutions run through MIOpen (MFMA paths for the ResNet9 GEMMs).
+full forward pass.  Convolutions run through MIOpen (MFMA paths for the ResNet9 GEMMs), except the
+frozen Conv1d(k=3) layers of ResNet9-1D (``Conv3Function``: the project's own fixed-order kernel).
 ``depth`` > 0 splits the pass for 1D latentmixup (augmentations.py:1494-1495): 'first' returns the
 hidden features, 'second' continues from them; for CNN_potes on the fused head the blend of those
 features can also happen inside the head's tail kernel (``loss_and_logits(..., latent=...)``).
@@ -14,11 +15,13 @@ features can also happen inside the head's tail kernel (``loss_and_logits(..., l
 from __future__ import annotations
 
 import ctypes
+import weakref
 from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -851,6 +854,98 @@ class BNReLUPoolEvalFunction(torch.autograd.Function):
         return (dx, None, None, None, None, None, None, None, (dz if has_skip else None), None)
 
 
+FUSED_CONV = True          # frozen Conv1d(k=3, pad=1) through the HIP kernel (False: MIOpen everywhere)
+FUSED_CONV_NOGRAD = True   # ... also where no gradient is wanted at all (the evaluation call)
+
+_CONV3_WT = {}             # id(weight) -> (weakref, data_ptr, _version, w'): see Conv3Function._transposed
+
+
+class Conv3Function(torch.autograd.Function):
+    """Conv1d(k=3, pad=1, stride 1, no bias) with FROZEN weights on a (B, Cin, 1, L) channels_last
+    activation through ``pcgmix_conv3_nlc_f32``: every output element is one float32 fmaf chain in
+    a fixed order, so the result — and the input gradient, which is the same kernel on ``dy`` with
+    the weights transposed and flipped — is the same bits in every run and at every batch size.
+    ``weight4`` is the Conv1d weight viewed as (Cout, Cin, 1, 3); it gets no gradient.  Nothing
+    here synchronises, so the frozen saliency pass can be captured into a graph."""
+
+    @staticmethod
+    def supported(h: torch.Tensor, weight4: torch.Tensor, padding, need_input_grad: bool) -> bool:
+        if not (h.is_cuda and h.dtype == torch.float32 and h.dim() == 4 and h.shape[2] == 1
+                and h.numel() > 0 and h.is_contiguous(memory_format=torch.channels_last)
+                and h.data_ptr() % 16 == 0):
+            return False
+        if not (weight4.dtype == torch.float32 and weight4.device == h.device and weight4.dim() == 4
+                and tuple(weight4.shape[2:]) == (1, 3) and weight4.shape[1] == h.shape[1]
+                and tuple(padding) == (0, 1) and weight4.data_ptr() % 16 == 0):
+            return False
+        lib = _lib.load()
+        cout, cin = int(weight4.shape[0]), int(weight4.shape[1])
+        return bool(lib.pcgmix_conv3_supported(cin, cout)) and (
+            not need_input_grad or bool(lib.pcgmix_conv3_supported(cout, cin)))
+
+    @staticmethod
+    def _rows(weight4):
+        """The weight as the kernel reads it: (Cout, 3, Cin) contiguous — the memory ResNet9_myrtle
+        gives its Conv1d weights, so no copy there."""
+        return weight4.detach().squeeze(2).permute(0, 2, 1).contiguous()
+
+    @staticmethod
+    def _transposed(weight4):
+        """w'[i][tap][o] = w[o][2-tap][i], built with torch ops once per weight tensor and kept until
+        the tensor is written to or moved (data_ptr, _version).  While a stream capture is under way
+        the cache is neither read nor written: w' is built inside the capture, so its memory belongs
+        to the graph's pool (the graph keeps it alive) and every replay rebuilds it from the weights
+        as they are then — a replay never reads a w' that the cache has dropped since, nor one that
+        an in-place write to the weights has made stale (16 small launches per pass)."""
+        if torch.cuda.is_current_stream_capturing():
+            return Conv3Function._rows(weight4).flip(1).permute(2, 1, 0).contiguous()
+        base = weight4._base if weight4._base is not None else weight4
+        ent = _CONV3_WT.get(id(base))
+        if ent is not None and ent[0]() is base and ent[1] == base.data_ptr() and ent[2] == base._version:
+            return ent[3]
+        wt = Conv3Function._rows(weight4).flip(1).permute(2, 1, 0).contiguous()
+        if len(_CONV3_WT) >= 64:
+            for k in [k for k, e in _CONV3_WT.items() if e[0]() is None]:
+                del _CONV3_WT[k]
+        _CONV3_WT[id(base)] = (weakref.ref(base), base.data_ptr(), base._version, wt)
+        return wt
+
+    @staticmethod
+    def _launch(x, w, cout):
+        B, cin, _, L = x.shape
+        y = torch.empty((B, cout, 1, L), dtype=torch.float32, device=x.device,
+                        memory_format=torch.channels_last)
+        _lib.check(_lib.load().pcgmix_conv3_nlc_f32(x.data_ptr(), w.data_ptr(), y.data_ptr(), B, L, cin,
+                                                    cout, _stream(x.device)), "pcgmix_conv3_nlc_f32")
+        return y
+
+    @staticmethod
+    def forward(ctx, h, weight4):
+        ctx.weight4 = weight4            # frozen, no gradient: not a saved tensor; backward reads it as it is then
+        return Conv3Function._launch(h, Conv3Function._rows(weight4), int(weight4.shape[0]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        w4 = ctx.weight4
+        return Conv3Function._launch(dy, Conv3Function._transposed(w4), int(w4.shape[1])), None
+
+
+def _conv3_route(h, weight4, padding) -> bool:
+    """Whether this convolution runs on the HIP kernel: frozen weights, and either the input wants a
+    gradient (the frozen saliency pass) or no gradient is recorded at all (evaluation)."""
+    if not FUSED_CONV or not h.is_cuda:
+        return False
+    grad = torch.is_grad_enabled()
+    if grad and weight4.requires_grad:
+        return False
+    want_dx = grad and h.requires_grad
+    if not want_dx and not (FUSED_CONV_NOGRAD and not grad):
+        return False
+    return Conv3Function.supported(h, weight4, padding, want_dx)
+
+
 def _window_and_skip(pool, skip):
     """What the fused Functions take: the pooling window as two ints, ``skip`` channels_last."""
     ph, pw = (1, 1) if pool is None else ((pool, pool) if isinstance(pool, int) else tuple(pool))
@@ -870,7 +965,11 @@ def conv_bn_relu_pool(h, weight4, conv_bias, padding, bn, training: bool, pool, 
     applies weight decay to it, as it does in the reference.  In eval mode the running mean is
     shifted by b instead.  Saves a bias-add pass over the activation and a (B, L) reduction for the
     bias gradient per layer (2.7 ms of a 42 ms ResNet9-1D step)."""
-    h = F.conv2d(h, weight4, None, padding=padding)
+    if _conv3_route(h, weight4, padding):
+        # frozen Conv1d(k=3, pad=1): the deterministic HIP kernel, forward and input gradient
+        h = Conv3Function.apply(h, weight4)
+    else:
+        h = F.conv2d(h, weight4, None, padding=padding)
     batch_stats = training or not bn.track_running_stats
     if bn.momentum is None or bn.momentum >= 1.0 or conv_bias is None:    # no fold
         if conv_bias is not None:

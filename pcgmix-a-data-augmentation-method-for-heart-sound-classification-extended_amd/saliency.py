@@ -230,6 +230,12 @@ def input_gradient_seeded(model: torch.nn.Module, data: torch.Tensor, seed: torc
     # within 1e-6 everywhere and bit-reproducible (maps 4e-7) but 40x (1D) / 77x (2D) slower at
     # bs 256 (1427 vs 36 ms, 5970 vs 78 ms), so it is opt-in: PCGMIX_SALIENCY_DETERMINISTIC=1 or
     # saliency.DETERMINISTIC_FROZEN_PASS = True (parity runs, the golden tests).
+    # ResNet9-1D no longer depends on it: its frozen Conv1d(k=3) layers run on the project's own
+    # fixed-order kernel in both directions (models.Conv3Function, csrc/pcgmix_conv3.hip), so the
+    # DEFAULT pass is bit-reproducible, its maps 5e-7 from the reference's CPU maps
+    # (tests/test_conv3_model_gpu.py), at 14.4 ms against MIOpen-default's 11.2 ms at bs 256
+    # (profiles/conv3_time.txt).  The switch below now matters only for convolutions that still go
+    # to MIOpen: ResNet9-2D, widths the kernel does not take, models.FUSED_CONV = False.
     det = DETERMINISTIC_FROZEN_PASS
     if det is None:
         det = os.environ.get("PCGMIX_SALIENCY_DETERMINISTIC", "0") not in ("", "0")
