@@ -1296,6 +1296,43 @@ int pcgmix_conv3_tile(int which);
 int pcgmix_conv3_nlc_f32(const float* x, const float* w, float* y, int B, int L, int Cin, int Cout,
                          pcgmix_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Weight gradient of the same Conv1d(k = 3, pad = 1, stride 1), channels innermost.   [device]
+ * csrc/pcgmix_conv3_wgrad.hip (wgrad_kernel, reduce_kernel).
+ *
+ * The weight gradient of nn.Conv1d(c_in, c_out, kernel_size=3, padding=1) of conv_block
+ * (models.py:468-473) in the training step; with it models.Conv3TrainFunction runs all three GEMMs
+ * of a trainable layer on the project's kernels (opt-in: models.FUSED_CONV_TRAIN).
+ *   x  (B, L, Cin)     the layer's input, as pcgmix_conv3_nlc_f32 takes it
+ *   dy (B, L, Cout)    the gradient of the layer's output
+ *   dw (Cout, 3, Cin)  [o][tap][i], the layout of w above
+ *   dw[o][tap][i] = sum over b, l of dy[b][l][o] * x[b][l + tap - 1][i], x zero outside [0, L).
+ * The sum over the B * L positions is cut into K tiles of 64 consecutive positions of one sample,
+ * numbered sample-major; `splits` blocks per output tile each add a contiguous ascending range of
+ * them on v_mfma_f32_32x32x2_f32 and write one partial into the caller's workspace; a second launch
+ * adds the partials in ascending order with plain float32 adds.  No atomics, no grid-wide wait, no
+ * allocation: dw's bits are a function of x, dy and (B, L, Cin, Cout) alone, the same on every
+ * device and in every run.  Unlike y above they DO depend on B (B sets the splits).
+ * pcgmix_conv3_wgrad_supported (models.py:468-473): the widths pcgmix_conv3_supported takes.  Host only.
+ * pcgmix_conv3_wgrad_tile (models.py:468-473): the kernel's tile constants, for tests that place
+ *   shapes at tile edges: which = 0 the positions of one K tile (64), 1 the output channels of a
+ *   block tile (128), 2 the input channels of a block tile (64; 32 where Cin <= 32), else 0.  Host only.
+ * pcgmix_conv3_wgrad_plan (models.py:468-473): *splits (1 <= splits <= number of K tiles, 1 for an
+ *   empty batch) and *workspace_bytes (splits * Cout * 3 * Cin * 4, or 0 when splits == 1) for a call
+ *   of these arguments; either pointer may be NULL.  0, or hipErrorInvalidValue for unsupported widths,
+ *   B < 0 or L < 1.  Host only.
+ * pcgmix_conv3_wgrad_nlc_f32 (models.py:468-473): refused with hipErrorInvalidValue, nothing launched
+ *   and dw and the workspace untouched: unsupported widths, a NULL x, dy or dw, a NULL workspace when
+ *   the plan needs bytes, a pointer that is not 16-byte aligned, workspace_bytes below the plan's,
+ *   B < 0, L < 1, L * max(Cin, Cout) > INT_MAX.  B == 0 writes zeros to dw and returns 0.  The
+ *   workspace is never read before the same call has written it, and nothing beyond the planned
+ *   bytes is touched.  dw and the workspace may not overlap x, dy or each other.               */
+int pcgmix_conv3_wgrad_supported(int Cin, int Cout);
+int pcgmix_conv3_wgrad_tile(int which);
+int pcgmix_conv3_wgrad_plan(int B, int L, int Cin, int Cout, int* splits, size_t* workspace_bytes);
+int pcgmix_conv3_wgrad_nlc_f32(const float* x, const float* dy, float* dw, void* workspace,
+                               size_t workspace_bytes, int B, int L, int Cin, int Cout, pcgmix_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@ features can also happen inside the head's tail kernel (``loss_and_logits(..., l
 from __future__ import annotations
 
 import ctypes
+import os
 import weakref
 from typing import NamedTuple, Optional
 
@@ -932,6 +933,85 @@ class Conv3Function(torch.autograd.Function):
         return Conv3Function._launch(dy, Conv3Function._transposed(w4), int(w4.shape[1])), None
 
 
+# TRAINABLE Conv1d(k=3, pad=1) through the HIP kernels as well (Conv3TrainFunction): forward, input
+# gradient and weight gradient in a fixed order of summation, so a seeded training run is the same
+# bits from step to step and from run to run.  None: the environment variable
+# PCGMIX_TRAIN_DETERMINISTIC decides (default off: MIOpen's default selection).
+FUSED_CONV_TRAIN: Optional[bool] = None
+
+
+def _conv_train_on() -> bool:
+    if FUSED_CONV_TRAIN is not None:
+        return bool(FUSED_CONV_TRAIN)
+    return os.environ.get("PCGMIX_TRAIN_DETERMINISTIC", "0") not in ("", "0")
+
+
+class Conv3TrainFunction(torch.autograd.Function):
+    """Conv1d(k=3, pad=1, stride 1, no bias) with TRAINABLE weights on a (B, Cin, 1, L) channels_last
+    activation: the forward is ``pcgmix_conv3_nlc_f32`` on the live weights, the input gradient the same
+    kernel on the flipped, transposed weights (``_flipped``: built from the live weights in every
+    backward), the weight gradient ``pcgmix_conv3_wgrad_nlc_f32`` — split-K with a fixed split
+    and a fixed order, no atomics — returned as the (Cout, Cin, 1, 3) view of its (Cout, 3, Cin) memory.
+    A gradient that nobody wants is not computed (the first layer's input gradient in training).
+    Nothing here synchronises; workspace and outputs are ``torch.empty`` tensors, so a captured step
+    keeps them in the graph's pool."""
+
+    @staticmethod
+    def supported(h: torch.Tensor, weight4: torch.Tensor, padding, need_input_grad: bool) -> bool:
+        if not Conv3Function.supported(h, weight4, padding, need_input_grad):
+            return False
+        return bool(_lib.load().pcgmix_conv3_wgrad_supported(int(weight4.shape[1]), int(weight4.shape[0])))
+
+    @staticmethod
+    def _flipped(weight4):
+        """w'[i][tap][o] = w[o][2-tap][i] of the weights as they are NOW, built in every backward.
+        ``Conv3Function._transposed`` keeps w' per weight on (data_ptr, _version), which is right for
+        frozen weights; ClipAdam / ClipSGD write the parameters through their pointers and leave
+        ``_version`` alone, so for trainable weights that cache would hand an eager step the w' of the
+        step before.  Weights that move every step have nothing to cache anyway."""
+        return Conv3Function._rows(weight4).flip(1).permute(2, 1, 0).contiguous()
+
+    @staticmethod
+    def _wgrad(h, dy):
+        B, cin, _, L = h.shape
+        cout = int(dy.shape[1])
+        lib = _lib.load()
+        splits, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
+        _lib.check(lib.pcgmix_conv3_wgrad_plan(B, L, cin, cout, ctypes.byref(splits), ctypes.byref(nbytes)),
+                   "pcgmix_conv3_wgrad_plan")
+        dw = torch.empty((cout, 3, cin), dtype=torch.float32, device=h.device)
+        ws = torch.empty(nbytes.value // 4, dtype=torch.float32, device=h.device) if nbytes.value else None
+        _lib.check(lib.pcgmix_conv3_wgrad_nlc_f32(h.data_ptr(), dy.data_ptr(), dw.data_ptr(), _ptr(ws),
+                                                  nbytes.value, B, L, cin, cout, _stream(h.device)),
+                   "pcgmix_conv3_wgrad_nlc_f32")
+        return dw.permute(0, 2, 1).unsqueeze(2)              # (Cout, Cin, 1, 3): a view, no copy
+
+    @staticmethod
+    def forward(ctx, h, weight4):
+        ctx.save_for_backward(h, weight4)
+        return Conv3Function._launch(h, Conv3Function._rows(weight4), int(weight4.shape[0]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        h, weight4 = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = Conv3Function._launch(dy, Conv3TrainFunction._flipped(weight4), int(weight4.shape[1]))
+        if ctx.needs_input_grad[1]:
+            dw = Conv3TrainFunction._wgrad(h, dy)
+        return dx, dw
+
+
+def _conv3_train_route(h, weight4, padding) -> bool:
+    """Whether this convolution runs on Conv3TrainFunction: the switch is on, gradients are recorded,
+    the weights want one, and the kernels take the widths of all the GEMMs the backward will run."""
+    if not h.is_cuda or not torch.is_grad_enabled() or not weight4.requires_grad or not _conv_train_on():
+        return False
+    return Conv3TrainFunction.supported(h, weight4, padding, h.requires_grad)
+
+
 def _conv3_route(h, weight4, padding) -> bool:
     """Whether this convolution runs on the HIP kernel: frozen weights, and either the input wants a
     gradient (the frozen saliency pass) or no gradient is recorded at all (evaluation)."""
@@ -968,6 +1048,9 @@ def conv_bn_relu_pool(h, weight4, conv_bias, padding, bn, training: bool, pool, 
     if _conv3_route(h, weight4, padding):
         # frozen Conv1d(k=3, pad=1): the deterministic HIP kernel, forward and input gradient
         h = Conv3Function.apply(h, weight4)
+    elif _conv3_train_route(h, weight4, padding):
+        # trainable Conv1d(k=3, pad=1), opt-in: the same kernel forward, and both gradients in a fixed order
+        h = Conv3TrainFunction.apply(h, weight4)
     else:
         h = F.conv2d(h, weight4, None, padding=padding)
     batch_stats = training or not bn.track_running_stats
