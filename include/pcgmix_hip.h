@@ -1333,6 +1333,43 @@ int pcgmix_conv3_wgrad_plan(int B, int L, int Cin, int Cout, int* splits, size_t
 int pcgmix_conv3_wgrad_nlc_f32(const float* x, const float* dy, float* dw, void* workspace,
                                size_t workspace_bytes, int B, int L, int Cin, int Cout, pcgmix_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Conv2d(k = 3x3, pad = 1, stride 1) of ResNet9-2D, channels innermost.             [device]
+ * csrc/pcgmix_conv3x3.hip (conv3x3_kernel, first_kernel, last_kernel).
+ *
+ * Replaces nn.Conv2d(c_in, c_out, kernel_size=3, padding=1) of conv_block (models2d.py:6-11)
+ * where its weights are frozen: the evaluation pass (train_model.py:591-670) and the frozen
+ * saliency pass on spectrograms (saliency.py:26-61, 93-113).  No bias (the BatchNorm kernels
+ * above take it).
+ *   x (B, H, W, Cin)     the memory of a (B, Cin, H, W) channels_last tensor
+ *   w (Cout, 3, 3, Cin)  [o][kh][kw][i], the memory models2d.ResNet9_myrtle gives its Conv2d weights
+ *   y (B, H, W, Cout)    y[b][h][v][o] = sum over kh, kw, i of x[b][h+kh-1][v+kw-1][i] * w[o][kh][kw][i],
+ *                        x zero outside [0, H) x [0, W) of every sample
+ * The layer's input gradient is the same call on dy with w'[i][kh][kw][o] = w[o][2-kh][2-kw][i].
+ * One launch.  Every output element is summed in ONE fixed order that is a function of (Cin, Cout)
+ * alone — no split-K, no atomics — so a sample's result is the same bits in every launch, at every B
+ * and at every place in the batch:
+ *   Cin % 16 == 0 and Cout % 16 == 0: one float32 fmaf chain from +0 on v_mfma_f32_32x32x2_f32 over
+ *     groups of 16 input channels ascending; in a group kh = 0, 1, 2; in a kh kw = 0, 1, 2; in a tap
+ *     the channels ascending.
+ *   Cin == 1: one fmaf chain from +0 over the nine taps, (kh, kw) = (0,0), (0,1) .. (2,2).
+ *   Cout == 1: per input pixel and tap, sixteen fmaf chains (chain l: channels 4q .. 4q+3 of the quads
+ *     q = l, l+16, .. ascending) added in a butterfly (distance 8, 4, 2, 1); then the nine taps' values
+ *     are added to +0 in (kh, kw) order with float32 adds, +0 for a tap outside the sample.
+ * pcgmix_conv3x3_supported (models2d.py:6-11): 1 for (Cin == 1 or Cin % 16 == 0, Cin <= 1024) and
+ *   (Cout == 1 or Cout % 16 == 0, Cout <= 1024), not both 1; else 0.  Host only: no device is touched.
+ * pcgmix_conv3x3_tile (models2d.py:6-11): the matrix kernel's tile constants, for tests that place
+ *   shapes at tile edges: which = 0 the rows of one tile of output pixels (8), 1 its columns (16),
+ *   2 the input channels of one K group (16), else 0.  Host only.
+ * pcgmix_conv3x3_nhwc_f32 (models2d.py:6-11; saliency.py:26-61, 93-113; train_model.py:591-670):
+ *   refused with hipErrorInvalidValue, nothing launched and y untouched: unsupported widths, a NULL
+ *   pointer, a pointer that is not 16-byte aligned, B < 0, H < 1, W < 1, H * W * max(Cin, Cout) >
+ *   INT_MAX, more than INT_MAX blocks.  B == 0 returns 0 and launches nothing.  x and y may not overlap. */
+int pcgmix_conv3x3_supported(int Cin, int Cout);
+int pcgmix_conv3x3_tile(int which);
+int pcgmix_conv3x3_nhwc_f32(const float* x, const float* w, float* y, int B, int H, int W, int Cin,
+                            int Cout, pcgmix_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

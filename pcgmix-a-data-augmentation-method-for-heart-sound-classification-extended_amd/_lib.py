@@ -202,6 +202,9 @@ SIGNATURES = {
     "pcgmix_conv3_supported": (_c_int, [_c_int, _c_int]),
     "pcgmix_conv3_tile": (_c_int, [_c_int]),
     "pcgmix_conv3_nlc_f32": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr]),
+    "pcgmix_conv3x3_supported": (_c_int, [_c_int, _c_int]),
+    "pcgmix_conv3x3_tile": (_c_int, [_c_int]),
+    "pcgmix_conv3x3_nhwc_f32": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _c_int, _ptr]),
     "pcgmix_conv3_wgrad_supported": (_c_int, [_c_int, _c_int]),
     "pcgmix_conv3_wgrad_tile": (_c_int, [_c_int]),
     "pcgmix_conv3_wgrad_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),

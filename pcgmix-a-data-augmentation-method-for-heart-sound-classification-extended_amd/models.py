@@ -7,7 +7,8 @@
 Both keep the reference's ``forward(x, depth=None, pass_part=None)`` signature; the training
 loop calls ``model(data, depth=0, pass_part='second')`` (train_model.py:537), which is the plain
 full forward pass.  Convolutions run through MIOpen (MFMA paths for the ResNet9 GEMMs), except the
-frozen Conv1d(k=3) layers of ResNet9-1D (``Conv3Function``: the project's own fixed-order kernel).
+frozen Conv1d(k=3) layers of ResNet9-1D (``Conv3Function``: the project's own fixed-order kernel) and
+the frozen Conv2d(3x3) layers of ResNet9-2D that ``conv_bn_relu_pool`` serves (``Conv3x3Function``).
 ``depth`` > 0 splits the pass for 1D latentmixup (augmentations.py:1494-1495): 'first' returns the
 hidden features, 'second' continues from them; for CNN_potes on the fused head the blend of those
 features can also happen inside the head's tail kernel (``loss_and_logits(..., latent=...)``).
@@ -858,7 +859,30 @@ class BNReLUPoolEvalFunction(torch.autograd.Function):
 FUSED_CONV = True          # frozen Conv1d(k=3, pad=1) through the HIP kernel (False: MIOpen everywhere)
 FUSED_CONV_NOGRAD = True   # ... also where no gradient is wanted at all (the evaluation call)
 
-_CONV3_WT = {}             # id(weight) -> (weakref, data_ptr, _version, w'): see Conv3Function._transposed
+_CONV3_WT = {}             # id(weight) -> (weakref, data_ptr, _version, w'): see _backward_weights
+
+
+def _backward_weights(weight4, build):
+    """``build(weight4)`` — the flipped, transposed weights w' with which the frozen backward is the
+    forward kernel again — built with torch ops once per weight tensor and kept until the tensor is
+    written to or moved (data_ptr, _version).  While a stream capture is under way the cache is
+    neither read nor written: w' is built inside the capture, so its memory belongs to the graph's
+    pool (the graph keeps it alive) and every replay rebuilds it from the weights as they are then —
+    a replay never reads a w' that the cache has dropped since, nor one that an in-place write to
+    the weights has made stale (16 small launches per pass).  One rule for Conv3Function (1D) and
+    Conv3x3Function (2D): a weight tensor belongs to one of them, so they share the table."""
+    if torch.cuda.is_current_stream_capturing():
+        return build(weight4)
+    base = weight4._base if weight4._base is not None else weight4
+    ent = _CONV3_WT.get(id(base))
+    if ent is not None and ent[0]() is base and ent[1] == base.data_ptr() and ent[2] == base._version:
+        return ent[3]
+    wt = build(weight4)
+    if len(_CONV3_WT) >= 64:
+        for k in [k for k, e in _CONV3_WT.items() if e[0]() is None]:
+            del _CONV3_WT[k]
+    _CONV3_WT[id(base)] = (weakref.ref(base), base.data_ptr(), base._version, wt)
+    return wt
 
 
 class Conv3Function(torch.autograd.Function):
@@ -891,25 +915,14 @@ class Conv3Function(torch.autograd.Function):
         return weight4.detach().squeeze(2).permute(0, 2, 1).contiguous()
 
     @staticmethod
+    def _flip(weight4):
+        return Conv3Function._rows(weight4).flip(1).permute(2, 1, 0).contiguous()
+
+    @staticmethod
     def _transposed(weight4):
-        """w'[i][tap][o] = w[o][2-tap][i], built with torch ops once per weight tensor and kept until
-        the tensor is written to or moved (data_ptr, _version).  While a stream capture is under way
-        the cache is neither read nor written: w' is built inside the capture, so its memory belongs
-        to the graph's pool (the graph keeps it alive) and every replay rebuilds it from the weights
-        as they are then — a replay never reads a w' that the cache has dropped since, nor one that
-        an in-place write to the weights has made stale (16 small launches per pass)."""
-        if torch.cuda.is_current_stream_capturing():
-            return Conv3Function._rows(weight4).flip(1).permute(2, 1, 0).contiguous()
-        base = weight4._base if weight4._base is not None else weight4
-        ent = _CONV3_WT.get(id(base))
-        if ent is not None and ent[0]() is base and ent[1] == base.data_ptr() and ent[2] == base._version:
-            return ent[3]
-        wt = Conv3Function._rows(weight4).flip(1).permute(2, 1, 0).contiguous()
-        if len(_CONV3_WT) >= 64:
-            for k in [k for k, e in _CONV3_WT.items() if e[0]() is None]:
-                del _CONV3_WT[k]
-        _CONV3_WT[id(base)] = (weakref.ref(base), base.data_ptr(), base._version, wt)
-        return wt
+        """w'[i][tap][o] = w[o][2-tap][i], cached per weight tensor and rebuilt inside a stream
+        capture: ``_backward_weights``."""
+        return _backward_weights(weight4, Conv3Function._flip)
 
     @staticmethod
     def _launch(x, w, cout):
@@ -931,6 +944,75 @@ class Conv3Function(torch.autograd.Function):
         dy = dy.contiguous(memory_format=torch.channels_last)
         w4 = ctx.weight4
         return Conv3Function._launch(dy, Conv3Function._transposed(w4), int(w4.shape[1])), None
+
+
+# The same for the frozen Conv2d(3x3, pad=1) layers of ResNet9-2D (Conv3x3Function).  FUSED_CONV = False
+# switches both off.  Defaults by measurement at (256, 1, 128, 128), profiles/conv3x3_time.txt: the frozen
+# pass goes to the kernel if it costs at most 2x MIOpen's default selection (it buys a bit-reproducible
+# pass inside the 1e-4 parity contract); the evaluation forward only if it is faster, nothing but speed
+# arguing for it there.
+FUSED_CONV2D = True          # the frozen pass with an input gradient (saliency on spectrograms)
+FUSED_CONV2D_NOGRAD = False  # where no gradient is wanted at all (the evaluation call)
+
+
+class Conv3x3Function(torch.autograd.Function):
+    """Conv2d(k=3x3, pad=1, stride 1, no bias) with FROZEN weights on a (B, Cin, H, W) channels_last
+    activation through ``pcgmix_conv3x3_nhwc_f32``: every output element is summed in one fixed order,
+    so the result — and the input gradient, which is the same kernel on ``dy`` with the weights
+    transposed and flipped — is the same bits in every run and at every batch size.  ``weight4`` is the
+    Conv2d weight (Cout, Cin, 3, 3); it gets no gradient.  Nothing here synchronises, so the frozen
+    saliency pass can be captured into a graph."""
+
+    @staticmethod
+    def supported(h: torch.Tensor, weight4: torch.Tensor, padding, need_input_grad: bool) -> bool:
+        if not (h.is_cuda and h.dtype == torch.float32 and h.dim() == 4 and h.numel() > 0
+                and h.is_contiguous(memory_format=torch.channels_last) and h.data_ptr() % 16 == 0):
+            return False
+        if not (weight4.dtype == torch.float32 and weight4.device == h.device and weight4.dim() == 4
+                and tuple(weight4.shape[2:]) == (3, 3) and weight4.shape[1] == h.shape[1]
+                and tuple(padding) == (1, 1) and weight4.data_ptr() % 16 == 0):
+            return False
+        lib = _lib.load()
+        cout, cin = int(weight4.shape[0]), int(weight4.shape[1])
+        return bool(lib.pcgmix_conv3x3_supported(cin, cout)) and (
+            not need_input_grad or bool(lib.pcgmix_conv3x3_supported(cout, cin)))
+
+    @staticmethod
+    def _rows(weight4):
+        """The weight as the kernel reads it: (Cout, 3, 3, Cin) contiguous — the memory of a
+        channels_last Conv2d weight, which models2d.ResNet9_myrtle keeps, so no copy there."""
+        return weight4.detach().permute(0, 2, 3, 1).contiguous()
+
+    @staticmethod
+    def _flip(weight4):
+        return Conv3x3Function._rows(weight4).flip(1, 2).permute(3, 1, 2, 0).contiguous()
+
+    @staticmethod
+    def _transposed(weight4):
+        """w'[i][kh][kw][o] = w[o][2-kh][2-kw][i], cached per weight tensor and rebuilt inside a stream
+        capture: ``_backward_weights``."""
+        return _backward_weights(weight4, Conv3x3Function._flip)
+
+    @staticmethod
+    def _launch(x, w, cout):
+        B, cin, H, W = x.shape
+        y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device,
+                        memory_format=torch.channels_last)
+        _lib.check(_lib.load().pcgmix_conv3x3_nhwc_f32(x.data_ptr(), w.data_ptr(), y.data_ptr(), B, H, W, cin,
+                                                       cout, _stream(x.device)), "pcgmix_conv3x3_nhwc_f32")
+        return y
+
+    @staticmethod
+    def forward(ctx, h, weight4):
+        ctx.weight4 = weight4            # frozen, no gradient: not a saved tensor; backward reads it as it is then
+        return Conv3x3Function._launch(h, Conv3x3Function._rows(weight4), int(weight4.shape[0]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dy):
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        w4 = ctx.weight4
+        return Conv3x3Function._launch(dy, Conv3x3Function._transposed(w4), int(w4.shape[1])), None
 
 
 # TRAINABLE Conv1d(k=3, pad=1) through the HIP kernels as well (Conv3TrainFunction): forward, input
@@ -969,7 +1051,7 @@ class Conv3TrainFunction(torch.autograd.Function):
         frozen weights; ClipAdam / ClipSGD write the parameters through their pointers and leave
         ``_version`` alone, so for trainable weights that cache would hand an eager step the w' of the
         step before.  Weights that move every step have nothing to cache anyway."""
-        return Conv3Function._rows(weight4).flip(1).permute(2, 1, 0).contiguous()
+        return Conv3Function._flip(weight4)
 
     @staticmethod
     def _wgrad(h, dy):
@@ -1012,18 +1094,32 @@ def _conv3_train_route(h, weight4, padding) -> bool:
     return Conv3TrainFunction.supported(h, weight4, padding, h.requires_grad)
 
 
-def _conv3_route(h, weight4, padding) -> bool:
-    """Whether this convolution runs on the HIP kernel: frozen weights, and either the input wants a
-    gradient (the frozen saliency pass) or no gradient is recorded at all (evaluation)."""
+def _frozen_route(h, weight4, with_dx: bool, without_grad: bool) -> Optional[bool]:
+    """The rule both frozen-convolution routes share.  None: MIOpen (trainable weights, a CPU tensor,
+    FUSED_CONV off, or the switch of this case — ``with_dx`` for a pass whose input wants a gradient,
+    ``without_grad`` for one that records none — off); else whether the input gradient is wanted."""
     if not FUSED_CONV or not h.is_cuda:
-        return False
+        return None
     grad = torch.is_grad_enabled()
     if grad and weight4.requires_grad:
-        return False
+        return None
     want_dx = grad and h.requires_grad
-    if not want_dx and not (FUSED_CONV_NOGRAD and not grad):
-        return False
-    return Conv3Function.supported(h, weight4, padding, want_dx)
+    if not (with_dx if want_dx else (without_grad and not grad)):
+        return None
+    return want_dx
+
+
+def _conv3_route(h, weight4, padding) -> bool:
+    """Whether this convolution runs on the 1D HIP kernel: frozen weights, and either the input wants
+    a gradient (the frozen saliency pass) or no gradient is recorded at all (evaluation)."""
+    want_dx = _frozen_route(h, weight4, True, FUSED_CONV_NOGRAD)
+    return want_dx is not None and Conv3Function.supported(h, weight4, padding, want_dx)
+
+
+def _conv3x3_route(h, weight4, padding) -> bool:
+    """The same for the 3x3 kernel, on its own two switches."""
+    want_dx = _frozen_route(h, weight4, FUSED_CONV2D, FUSED_CONV2D_NOGRAD)
+    return want_dx is not None and Conv3x3Function.supported(h, weight4, padding, want_dx)
 
 
 def _window_and_skip(pool, skip):
@@ -1048,6 +1144,9 @@ def conv_bn_relu_pool(h, weight4, conv_bias, padding, bn, training: bool, pool, 
     if _conv3_route(h, weight4, padding):
         # frozen Conv1d(k=3, pad=1): the deterministic HIP kernel, forward and input gradient
         h = Conv3Function.apply(h, weight4)
+    elif _conv3x3_route(h, weight4, padding):
+        # frozen Conv2d(3x3, pad=1) of ResNet9-2D: the same contract, csrc/pcgmix_conv3x3.hip
+        h = Conv3x3Function.apply(h, weight4)
     elif _conv3_train_route(h, weight4, padding):
         # trainable Conv1d(k=3, pad=1), opt-in: the same kernel forward, and both gradients in a fixed order
         h = Conv3TrainFunction.apply(h, weight4)

@@ -1,7 +1,9 @@
 """ResNet9 (Myrtle) on 128x128 log-mel images — reference models2d.py:13-87, same
 ``state_dict`` keys (conv1, conv2, res1.{0,1}, conv3, conv4, res2.{0,1}, linear) and the same
 ``forward(x, depth=None, pass_part=None)`` signature.  This is the one place on the hot path
-where the MFMA units matter (6.05 GMAC forward per sample); the convolutions go through MIOpen.
+where the MFMA units matter (6.05 GMAC forward per sample); the convolutions go through MIOpen,
+except with frozen weights in the saliency pass (and, opt-in, in evaluation), where
+``models.conv_bn_relu_pool`` sends them to the project's fixed-order kernel (``models.Conv3x3Function``).
 """
 from __future__ import annotations
 

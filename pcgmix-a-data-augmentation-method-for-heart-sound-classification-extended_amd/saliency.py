@@ -234,8 +234,12 @@ def input_gradient_seeded(model: torch.nn.Module, data: torch.Tensor, seed: torc
     # fixed-order kernel in both directions (models.Conv3Function, csrc/pcgmix_conv3.hip), so the
     # DEFAULT pass is bit-reproducible, its maps 5e-7 from the reference's CPU maps
     # (tests/test_conv3_model_gpu.py), at 14.4 ms against MIOpen-default's 11.2 ms at bs 256
-    # (profiles/conv3_time.txt).  The switch below now matters only for convolutions that still go
-    # to MIOpen: ResNet9-2D, widths the kernel does not take, models.FUSED_CONV = False.
+    # (profiles/conv3_time.txt).  ResNet9-2D likewise where models.FUSED_CONV2D is on: its eight
+    # frozen Conv2d(3x3) layers run on models.Conv3x3Function (csrc/pcgmix_conv3x3.hip) in both
+    # directions, the pass is bit-reproducible and its maps within 1e-5 of the reference's
+    # (tests/test_conv3x3_model_gpu.py; the times and the default are in profiles/conv3x3_time.txt).
+    # The switch below matters only for convolutions that still go to MIOpen: widths the kernels do
+    # not take, models.FUSED_CONV = False, ResNet9-2D with models.FUSED_CONV2D = False.
     det = DETERMINISTIC_FROZEN_PASS
     if det is None:
         det = os.environ.get("PCGMIX_SALIENCY_DETERMINISTIC", "0") not in ("", "0")
@@ -305,10 +309,12 @@ class _SaliencyGraph:
     kernel of the step context writes it as a by-product, ``pcgmix_ctx_labels_begin``), ``fr``
     (int32 boundaries, uploaded straight into place)."""
 
-    def __init__(self, model, shape, num_classes, device, gauss_k_n):
-        B, C, T = shape
-        self.model, self.k = model, gauss_k_n
-        self.x = torch.zeros(B, C, T, device=device)
+    def __init__(self, model, shape, num_classes, device, gauss_k_n, dim=1):
+        # dim == 2: a (B, 1, F, W) spectrogram batch, maps (B, W) from saliency_post2d (its own
+        # constants: gauss_k_n is not used); everything else is the same capture
+        B, T = shape[0], shape[-1]
+        self.model, self.k, self.dim = model, gauss_k_n, dim
+        self.x = torch.zeros(shape, device=device)
         self.seed = torch.zeros(B, num_classes, device=device)
         self.seed[:, 0] = 1
         self.fr = torch.zeros(B, 5, dtype=torch.int32, device=device)
@@ -316,7 +322,7 @@ class _SaliencyGraph:
         # eagerly on the caller's tensor and everything behind it is captured; other models get
         # the batch copied into the static input and the whole pass captured.
         m = _potes_direct(model, self.x)
-        self.chain = _PotesChain(m, (B, C, T), device) if m is not None else None
+        self.chain = _PotesChain(m, tuple(shape), device) if m is not None else None
         # The direct Potes chain is five plain launches with no autograd in between: replaying
         # them as a hipGraph saves ~20 us of host time per step but costs a stream -> graph ->
         # stream hand-over on the GPU (~9 us of idle queue behind the graph's last kernel,
@@ -327,7 +333,7 @@ class _SaliencyGraph:
             self.graph = None
             # one library call per pass into buffers owned here (valid until the next pass)
             self.sal = torch.empty((B, T), dtype=torch.float32, device=device)
-            self.gx = torch.empty((B, C, T), dtype=torch.float32, device=device)
+            self.gx = torch.empty(tuple(shape), dtype=torch.float32, device=device)
             self.chain.pass_into(self.x, self.seed, self.fr.data_ptr(), self.k, self.sal, self.gx)
             return
         side = torch.cuda.Stream(device)
@@ -346,6 +352,8 @@ class _SaliencyGraph:
     def _run(self):
         grad = self.chain.backward(self.seed) if self.chain is not None \
             else input_gradient_seeded(self.model, self.x, self.seed)
+        if self.dim == 2:
+            return saliency_post2d(grad, self.fr.data_ptr())
         return saliency_post(grad, self.fr.data_ptr(), self.k)
 
     def _enqueue(self, data):
@@ -381,20 +389,24 @@ def step_graph(args, data, num_classes: int, dim: int = 1, gauss_k_n: int = 101,
     """The captured saliency pass for this model and batch shape (captured on first use), or None
     when graphs are off or the stream is capturing."""
     if dim != 1:
-        return None          # spectrograms: the pass is 25 ms of MIOpen convolutions, run eagerly
+        # spectrograms: captured where the frozen Conv2d layers run on the project's own kernel
+        # (models.Conv3x3Function); a pass of MIOpen convolutions is run eagerly, as before
+        from . import models
+        if dim != 2 or not (models.FUSED_CONV and models.FUSED_CONV2D) or data.dim() != 4:
+            return None
     if not data.is_cuda:
         raise ValueError("data must live on a HIP device")
     if not USE_GRAPHS or torch.cuda.is_current_stream_capturing():
         return None
     model = model_sal or _INJECTED or _baseline_model(args, data.device, dim)
-    key = (id(model), tuple(data.shape), int(num_classes), gauss_k_n, str(data.device))
+    key = (id(model), tuple(data.shape), int(num_classes), gauss_k_n, str(data.device), dim)
     g = _GRAPHS.get(key)
     if g is None:
         if len(_GRAPHS) >= 8:
             _GRAPHS.clear()
         with torch.cuda.device(data.device):
             g = _GRAPHS[key] = _SaliencyGraph(model, tuple(data.shape), int(num_classes), data.device,
-                                              gauss_k_n)
+                                              gauss_k_n, dim)
     return g
 
 
@@ -411,6 +423,10 @@ def get_saliency_maps(args, device, data, target_ohe, frames, dim=1, gauss_k_n=1
     frames_np = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
     if dim == 2:
         with torch.cuda.device(data.device):
+            g = step_graph(args, data, target_ohe.shape[1], 2, gauss_k_n, model_sal) \
+                if target_ohe.dtype == torch.int64 else None
+            if g is not None:
+                return g.run(data, frames_np, target_ohe)
             from .augmentations import upload_array
             model = model_sal or _INJECTED or _baseline_model(args, data.device, 2)
             fr = upload_array(frames_np.astype(np.int32), data.device)
