@@ -1334,6 +1334,43 @@ int pcgmix_conv3_wgrad_nlc_f32(const float* x, const float* dy, float* dw, void*
                                size_t workspace_bytes, int B, int L, int Cin, int Cout, pcgmix_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The same Conv1d(k = 3, pad = 1, stride 1) and its weight gradient for the narrow layers of
+ * resnet9-5k .. resnet9-50k, channels innermost, on the vector ALU.                  [device]
+ * csrc/pcgmix_conv3_narrow.hip (fwd_kernel, wgrad_kernel, reduce_kernel).
+ *
+ * nn.Conv1d(c_in, c_out, kernel_size=3, padding=1) of conv_block (models.py:468-473) at the widths the
+ * two blocks above refuse: Cin and Cout both in {2, 4, 8, 16} with Cin == 2 or Cout in {2, 8} — the
+ * ten pairs (2,2) (2,4) (2,8) (2,16) (4,2) (8,2) (16,2) (4,8) (8,8) (16,8).  The two sets are
+ * disjoint.  x, w, y, dy and dw are laid out as above; models.FUSED_CONV_NARROW routes to them.
+ * pcgmix_conv3_narrow_supported (models.py:468-473): 1 on exactly those ten pairs, else 0.  Host only.
+ * pcgmix_conv3_narrow_tile (models.py:468-473): which = 0 the positions of one forward tile (256),
+ *   1 the positions of one weight-gradient K tile (256), else 0.  Host only.
+ * pcgmix_conv3_narrow_nlc_f32 (models.py:468-473; saliency.py:26-61; train_model.py:591-670): one
+ *   launch, one position a thread.  Every output element is ONE float32 fmaf chain from +0 over the
+ *   3*Cin products: tap 0, 1, 2, in a tap the channels ascending (the rule of pcgmix_conv3_nlc_f32
+ *   for a single K group).  No split-K, no atomics: a sample's result is the same bits in every
+ *   launch, at every B and at every place in the batch.  A row outside the sample is zeros by a
+ *   select on a clamped load.  The input gradient is the same call on dy with
+ *   w'[i][tap][o] = w[o][2-tap][i].  Refusals and B == 0 as for pcgmix_conv3_nlc_f32.
+ * pcgmix_conv3_narrow_wgrad_plan (models.py:468-473): as pcgmix_conv3_wgrad_plan, with K tiles of
+ *   256 positions: *splits = min(1024, K tiles / 2), at least 1 — a function of (B, L) alone.
+ * pcgmix_conv3_narrow_wgrad_nlc_f32 (models.py:468-473): the contract of
+ *   pcgmix_conv3_wgrad_nlc_f32.  Split s adds the K tiles [s U / S, (s + 1) U / S) in ascending
+ *   order; inside a block the thread groups combine through a fixed LDS tree (the file's header
+ *   has it); a second launch adds the partials in ascending order with plain float32 adds.  No
+ *   atomics, no grid-wide wait, no allocation; the workspace is never read before the same call
+ *   has written it and nothing beyond the planned bytes is touched.  Refusals and B == 0 (zeros
+ *   to dw) as for pcgmix_conv3_wgrad_nlc_f32.                                                    */
+int pcgmix_conv3_narrow_supported(int Cin, int Cout);
+int pcgmix_conv3_narrow_tile(int which);
+int pcgmix_conv3_narrow_nlc_f32(const float* x, const float* w, float* y, int B, int L, int Cin, int Cout,
+                                pcgmix_stream_t stream);
+int pcgmix_conv3_narrow_wgrad_plan(int B, int L, int Cin, int Cout, int* splits, size_t* workspace_bytes);
+int pcgmix_conv3_narrow_wgrad_nlc_f32(const float* x, const float* dy, float* dw, void* workspace,
+                                      size_t workspace_bytes, int B, int L, int Cin, int Cout,
+                                      pcgmix_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Conv2d(k = 3x3, pad = 1, stride 1) of ResNet9-2D, channels innermost.             [device]
  * csrc/pcgmix_conv3x3.hip (conv3x3_kernel, first_kernel, last_kernel).
  *

@@ -210,6 +210,12 @@ SIGNATURES = {
     "pcgmix_conv3_wgrad_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),
     "pcgmix_conv3_wgrad_nlc_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _c_int, _c_int, _c_int,
                                            _c_int, _ptr]),
+    "pcgmix_conv3_narrow_supported": (_c_int, [_c_int, _c_int]),
+    "pcgmix_conv3_narrow_tile": (_c_int, [_c_int]),
+    "pcgmix_conv3_narrow_nlc_f32": (_c_int, [_ptr, _ptr, _ptr, _c_int, _c_int, _c_int, _c_int, _ptr]),
+    "pcgmix_conv3_narrow_wgrad_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _ptr, _ptr]),
+    "pcgmix_conv3_narrow_wgrad_nlc_f32": (_c_int, [_ptr, _ptr, _ptr, _ptr, ctypes.c_size_t, _c_int, _c_int,
+                                                  _c_int, _c_int, _ptr]),
 }
 
 _lib = None

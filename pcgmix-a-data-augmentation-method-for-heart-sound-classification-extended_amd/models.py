@@ -858,6 +858,11 @@ class BNReLUPoolEvalFunction(torch.autograd.Function):
 
 FUSED_CONV = True          # frozen Conv1d(k=3, pad=1) through the HIP kernel (False: MIOpen everywhere)
 FUSED_CONV_NOGRAD = True   # ... also where no gradient is wanted at all (the evaluation call)
+# The widths the matrix kernels refuse but csrc/pcgmix_conv3_narrow.hip takes (2 and 8 channels, in
+# resnet9-5k .. resnet9-50k) go to the narrow kernels on every Conv1d(k=3) route that is taken at all.
+# None: follow _conv_train_on(), so that PCGMIX_TRAIN_DETERMINISTIC=1 alone covers the whole ladder and
+# every default path keeps MIOpen there (timings: profiles/conv3_narrow_time.txt).
+FUSED_CONV_NARROW: Optional[bool] = None
 
 _CONV3_WT = {}             # id(weight) -> (weakref, data_ptr, _version, w'): see _backward_weights
 
@@ -885,6 +890,24 @@ def _backward_weights(weight4, build):
     return wt
 
 
+def _conv_narrow_on() -> bool:
+    return bool(FUSED_CONV_NARROW) if FUSED_CONV_NARROW is not None else _conv_train_on()
+
+
+def _conv3_entry(cin: int, cout: int, wgrad: bool = False) -> Optional[str]:
+    """The entry-point family for one GEMM of a Conv1d(k=3) layer — ``cin`` and ``cout`` as the kernel
+    call takes them (the forward pair, the input-gradient pair (Cout, Cin), or with ``wgrad`` the
+    weight-gradient pair): "pcgmix_conv3" where the matrix kernel takes the pair, else
+    "pcgmix_conv3_narrow" where the narrow kernel does and FUSED_CONV_NARROW is on, else None (MIOpen).
+    The family's calls are name + "_nlc_f32", + "_wgrad_plan" and + "_wgrad_nlc_f32"."""
+    lib = _lib.load()
+    if (lib.pcgmix_conv3_wgrad_supported if wgrad else lib.pcgmix_conv3_supported)(cin, cout):
+        return "pcgmix_conv3"
+    if _conv_narrow_on() and lib.pcgmix_conv3_narrow_supported(cin, cout):
+        return "pcgmix_conv3_narrow"
+    return None
+
+
 class Conv3Function(torch.autograd.Function):
     """Conv1d(k=3, pad=1, stride 1, no bias) with FROZEN weights on a (B, Cin, 1, L) channels_last
     activation through ``pcgmix_conv3_nlc_f32``: every output element is one float32 fmaf chain in
@@ -903,10 +926,9 @@ class Conv3Function(torch.autograd.Function):
                 and tuple(weight4.shape[2:]) == (1, 3) and weight4.shape[1] == h.shape[1]
                 and tuple(padding) == (0, 1) and weight4.data_ptr() % 16 == 0):
             return False
-        lib = _lib.load()
         cout, cin = int(weight4.shape[0]), int(weight4.shape[1])
-        return bool(lib.pcgmix_conv3_supported(cin, cout)) and (
-            not need_input_grad or bool(lib.pcgmix_conv3_supported(cout, cin)))
+        return _conv3_entry(cin, cout) is not None and (
+            not need_input_grad or _conv3_entry(cout, cin) is not None)
 
     @staticmethod
     def _rows(weight4):
@@ -929,8 +951,9 @@ class Conv3Function(torch.autograd.Function):
         B, cin, _, L = x.shape
         y = torch.empty((B, cout, 1, L), dtype=torch.float32, device=x.device,
                         memory_format=torch.channels_last)
-        _lib.check(_lib.load().pcgmix_conv3_nlc_f32(x.data_ptr(), w.data_ptr(), y.data_ptr(), B, L, cin,
-                                                    cout, _stream(x.device)), "pcgmix_conv3_nlc_f32")
+        name = str(_conv3_entry(cin, cout)) + "_nlc_f32"     # a pair nobody takes: a missing symbol, an error
+        _lib.check(getattr(_lib.load(), name)(x.data_ptr(), w.data_ptr(), y.data_ptr(), B, L, cin, cout,
+                                              _stream(x.device)), name)
         return y
 
     @staticmethod
@@ -1042,7 +1065,7 @@ class Conv3TrainFunction(torch.autograd.Function):
     def supported(h: torch.Tensor, weight4: torch.Tensor, padding, need_input_grad: bool) -> bool:
         if not Conv3Function.supported(h, weight4, padding, need_input_grad):
             return False
-        return bool(_lib.load().pcgmix_conv3_wgrad_supported(int(weight4.shape[1]), int(weight4.shape[0])))
+        return _conv3_entry(int(weight4.shape[1]), int(weight4.shape[0]), wgrad=True) is not None
 
     @staticmethod
     def _flipped(weight4):
@@ -1057,15 +1080,15 @@ class Conv3TrainFunction(torch.autograd.Function):
     def _wgrad(h, dy):
         B, cin, _, L = h.shape
         cout = int(dy.shape[1])
-        lib = _lib.load()
+        lib, name = _lib.load(), str(_conv3_entry(cin, cout, wgrad=True))
         splits, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
-        _lib.check(lib.pcgmix_conv3_wgrad_plan(B, L, cin, cout, ctypes.byref(splits), ctypes.byref(nbytes)),
-                   "pcgmix_conv3_wgrad_plan")
+        _lib.check(getattr(lib, name + "_wgrad_plan")(B, L, cin, cout, ctypes.byref(splits), ctypes.byref(nbytes)),
+                   name + "_wgrad_plan")
         dw = torch.empty((cout, 3, cin), dtype=torch.float32, device=h.device)
         ws = torch.empty(nbytes.value // 4, dtype=torch.float32, device=h.device) if nbytes.value else None
-        _lib.check(lib.pcgmix_conv3_wgrad_nlc_f32(h.data_ptr(), dy.data_ptr(), dw.data_ptr(), _ptr(ws),
-                                                  nbytes.value, B, L, cin, cout, _stream(h.device)),
-                   "pcgmix_conv3_wgrad_nlc_f32")
+        _lib.check(getattr(lib, name + "_wgrad_nlc_f32")(h.data_ptr(), dy.data_ptr(), dw.data_ptr(), _ptr(ws),
+                                                         nbytes.value, B, L, cin, cout, _stream(h.device)),
+                   name + "_wgrad_nlc_f32")
         return dw.permute(0, 2, 1).unsqueeze(2)              # (Cout, Cin, 1, 3): a view, no copy
 
     @staticmethod

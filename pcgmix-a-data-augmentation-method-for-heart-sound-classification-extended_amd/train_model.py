@@ -502,7 +502,12 @@ def build_model(args) -> nn.Module:
     'PotesBig*' models on the f32-matrix-instruction ones (csrc/pcgmix_potes_big.hip).  Every
     ResNet9 width of the ladder (2 ... 1024) runs its BatchNorm + ReLU + pool through the HIP
     kernels, in training and in eval mode: they take C = 2 and every multiple of 4 up to 1024
-    (``pcgmix_bnrp_supported``), so no ResNet9 name warns."""
+    (``pcgmix_bnrp_supported``), so no ResNet9 name warns.  With PCGMIX_TRAIN_DETERMINISTIC=1 (or
+    ``models.FUSED_CONV_TRAIN``) every Conv1d(k=3) of every ladder name runs on the project's
+    fixed-order kernels: the matrix ones (csrc/pcgmix_conv3.hip, pcgmix_conv3_wgrad.hip), and for the
+    2- and 8-channel layers of 'resnet9-5k' ... 'resnet9-50k' the narrow ones
+    (csrc/pcgmix_conv3_narrow.hip, ``models.FUSED_CONV_NARROW``).  Without the switch those narrow
+    layers keep MIOpen on every route."""
     sig_len = getattr(args, "sig_len", 2500)
     if args.dataset in SPECTROGRAM_DATASETS:
         if args.model != "resnet9":
